@@ -18,6 +18,8 @@ definition of the metric:  value = sum over instances of the iterations they exe
 terminate stop counting (and stop working).  With an explicit --steps K the same formula covers K iterations after
 W warm-up iterations.  `iteration_throughput` (extra key) is the same ratio over the first 25 timed iterations, where every
 instance is still running -- the round-1 headline figure.
+`--dump-outputs DIR` writes what the timed iterations computed (dump_outputs) as DIR/<name>.npy, so that two builds can be compared
+output for output on the same seeded inputs.
 Extra keys: jacobian_nnz_per_sec (batched MOI Jacobian callback), roofline (dominant kernel of the step,
 HIP events on the launch stream), cpu_baseline (oracle C port on the host, rank 0, N = 1 only), solve (how the
 instances ended), full_solves (T = 101, the reference example's horizon), dense_blocks (configs[4]).
@@ -48,7 +50,7 @@ class _LazyTorch:
 
 torch = _LazyTorch()
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec
 
 
 def make_guesses(s, p, B, seed, rng=None):
@@ -249,6 +251,37 @@ def _limited_by_from_counters(kernel, B):
     return None
 
 
+DUMP_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE = 512
+
+
+def dump_outputs(out_dir, s, B, dev, st, zout=None, seed=0):
+    """--dump-outputs: what the timed iterations left, as a caller of the solver receives it (dto_solver_end + the per-instance
+    scalars): status and iteration count of every instance, the iterate z and the multipliers of a sample of instances drawn with a
+    fixed seed (`instance`: their indices), under DUMP_BYTES in all.  z and the multipliers are unpacked one array at a time (into
+    `zout` when the caller already holds z), so the dump never needs more HBM than the bench's own high-water mark."""
+    nz, nc = s.nlp.num_variables, s.nlp.num_constraint
+    rows = min(B, DUMP_SAMPLE, (DUMP_BYTES - 2 * 4 * B) // (8 * (nz + nc + 1)))
+    if rows < 1:
+        raise SystemExit(f"--dump-outputs: {B} instances of {nz} + {nc} doubles do not fit {DUMP_BYTES} bytes")
+    idx = np.sort(np.random.default_rng(seed).choice(B, rows, replace=False))
+    sel = torch.as_tensor(idx, device=dev)
+    out = dict(instance=idx.astype(np.float64), status=s.scalar_batch("status").astype(np.float32),
+               iterations=s.scalar_batch("iter").astype(np.float32))
+    for name, width in (("z", nz), ("multipliers", nc)):
+        buf = zout if name == "z" else None
+        if buf is None:
+            buf = torch.empty((B, width), device=dev, dtype=torch.float64)
+            ptr = buf.data_ptr()
+            s.end_batch(ptr if name == "z" else None, nz, ptr if name == "multipliers" else None, nc, stream=st)
+        out[name] = buf[sel].cpu().numpy()
+        del buf
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return dict(dir=out_dir, instances_sampled=int(rows), arrays=sorted(out), bytes=int(sum(v.nbytes for v in out.values())))
+
+
 def cpu_baseline(a):
     """The oracle's C port on the host cores, in its own process (started before torch / HIP are loaded here)."""
     import subprocess
@@ -317,7 +350,12 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="(tests) ranks only join a gloo group on the CPU, all-reduce their rank and rank 0 prints one line: "
                          "exercises the self-launch path of --gpus N without a GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed as DIR/<name>.npy (rank 0's shard): status and iterations "
+                         "of every instance, z and multipliers of a fixed seeded sample of instances, at most 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as CHILD processes
@@ -469,10 +507,15 @@ def main():
     if dist is not None:
         dist.all_reduce(thr0, op=dist.ReduceOp.SUM)
     if a.loop_only:
+        dumped = None
+        if a.dump_outputs and rank == 0:
+            del z0
+            dumped = dump_outputs(a.dump_outputs, s, B, dev, st)
         if rank == 0:
             print(json.dumps(dict(value=iters_done / dt, unit="SQP iterations/s", n_gpus=world, steps=a.steps, warmup=a.warmup,
                                   ms_per_step=dt / a.steps * 1e3, instances_per_gpu=B, time_partitions=s.partitions(), engine=s.engine(),
-                                  factorizations_per_iteration=round(facts_done / max(iters_done, 1.0), 3))), flush=True)
+                                  factorizations_per_iteration=round(facts_done / max(iters_done, 1.0), 3),
+                                  **({"dumped_outputs": dumped} if dumped else {}))), flush=True)
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -612,6 +655,7 @@ def main():
     time_partitions = s.partitions()
     engine_name = s.engine()
     del jout, z0, jfn
+    dumped = dump_outputs(a.dump_outputs, s, B, dev, st, zout=zout) if a.dump_outputs and rank == 0 else None
     s.close()
     torch.cuda.empty_cache()
     # bounded exchange (dto_amd/parallel.py): <= 8 GiB of receive buffer per collective, every chunk consumed at once (here: a
@@ -664,6 +708,7 @@ def main():
             gathered_trajectories=n_gathered, gathered_status_sum=float(gsum), hbm_free_min_gb=hbm_free_min_gb, engine=engine_name,
             roofline=roofline, cpu_baseline=cpu, full_solves=full, dense_blocks=dense,
             **({f"full_solves_T{T}": full_T} if full_T is not None else {}),
+            **({"dumped_outputs": dumped} if dumped else {}),
         )
         print(json.dumps(out), flush=True)
     if dist is not None:

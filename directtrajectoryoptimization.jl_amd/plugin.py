@@ -749,8 +749,10 @@ def _prepare_plugin(st: Structure, name: str):
         return so, None
     src = generate_source(st, name)
     hip_src = base + ".hip"
-    with open(hip_src, "w") as f:
+    # written under a private name and renamed: build() runs several processes that may generate the same plugin at once
+    with open(hip_src + f".tmp{os.getpid()}", "w") as f:
         f.write(src)
+    os.replace(hip_src + f".tmp{os.getpid()}", hip_src)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     tmp = so + f".tmp{os.getpid()}"
     cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-I", CSRC,

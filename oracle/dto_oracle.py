@@ -3,8 +3,8 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the
 product (directtrajectoryoptimization.jl_amd/) never does, and has no CPU path of its own.
 
-Every function follows the reference function named in its docstring (file:line under
-/root/reference).  The reference's serial stage loops, index algebra (including its O(T^2) prefix
+Every function follows the reference function named in its docstring (file:line in
+the reference package).  The reference's serial stage loops, index algebra (including its O(T^2) prefix
 sums, kept here as plain prefix sums) and `.+=` accumulation order are preserved; 1-based index
 values are produced exactly as Julia would, and converted only at the point of numpy indexing.
 

@@ -2,7 +2,7 @@
 
 Independent restatement, in sympy, of the model equations the reference examples/tests define, and
 of what Symbolics.jl does with them in the reference constructors (Symbolics.jl 0.1.29-0.1.32 is a
-third-party dependency that is NOT vendored under /root/reference; Project.toml:14,22):
+third-party dependency that is NOT vendored in the reference package; Project.toml:14,22):
 
     Symbolics.gradient / sparsejacobian / sparsehessian + build_function
         call sites: src/costs.jl:18-28, src/dynamics.jl:23-36, src/constraints.jl:27-41,

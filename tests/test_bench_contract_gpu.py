@@ -75,6 +75,24 @@ def test_loop_only_line():
     assert d["steps"] == 3 and d["instances_per_gpu"] == 8192 and d["value"] > 0 and d["engine"] == "soa"
 
 
+def test_dump_outputs(tmp_path):
+    """--dump-outputs DIR writes what the timed steps computed: status and iterations of every instance, z and multipliers of a
+    seeded sample, float32 / float64, within 64 MB; an instance still running has done exactly warmup + steps iterations."""
+    import numpy as np
+    d = _run(["--loop-only", "--steps", "3", "--warmup", "1", "--batch", "8192", "--horizon", "200", "--dump-outputs", str(tmp_path)])
+    o = {k: np.load(tmp_path / f"{k}.npy") for k in ("instance", "status", "iterations", "z", "multipliers")}
+    assert sorted(d["dumped_outputs"]["arrays"]) == sorted(o) and sorted(p.name for p in tmp_path.iterdir()) == sorted(f"{k}.npy" for k in o)
+    assert all(v.dtype in (np.float32, np.float64) for v in o.values())
+    assert sum(v.nbytes for v in o.values()) <= 64 * 10 ** 6
+    idx = o["instance"].astype(np.int64)
+    assert len(idx) == d["dumped_outputs"]["instances_sampled"] > 0 and np.all(np.diff(idx) > 0) and idx[-1] < 8192
+    assert o["status"].shape == o["iterations"].shape == (8192,)
+    assert o["z"].shape == (len(idx), 5 * 200 - 1) and o["multipliers"].shape[0] == len(idx)
+    assert np.all(np.isfinite(o["z"])) and np.all(np.isfinite(o["multipliers"]))
+    running = o["status"] == 0
+    assert running.any() and np.all(o["iterations"][running] == 1 + 3)
+
+
 def test_cpu_baseline_object():
     """The `cpu_baseline` leg (oracle's C port in a child process started before torch / HIP) on a short horizon."""
     d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4096", "--horizon", "200", "--no-full-solves", "--no-dense-blocks"])

@@ -1,6 +1,6 @@
 """Iterations of the quasi-Newton (per-stage SR1) mode on the four models: python tools/gn_check.py"""
 import sys, os
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import dto_amd
 from dto_amd import problems as P

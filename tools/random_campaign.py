@@ -1,7 +1,8 @@
 """One-off randomized campaign (GPU): 22 random heterogeneous problems -- structures, J/H values and a KKT step against the oracle.
 Round 1 result: 22/22, J/H errors ~1e-16, KKT step errors <= 2e-12 of the step norm.  python tools/random_campaign.py"""
 import sys, os
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import dto_amd
 from oracle import dto_oracle as O
