@@ -1,7 +1,7 @@
 """Headline benchmark: SQP iterations/sec + Jacobian nnz/sec, acrobot T=1000, 1 -> 8 GPU (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one interior-point/SQP iteration of the whole batch resident on this rank's GPU:
 derivative blocks (value, gradient, Jacobian, Hessian of the Lagrangian) -> KKT assembly ->
@@ -20,9 +20,12 @@ W warm-up iterations.  `iteration_throughput` (extra key) is the same ratio over
 instance is still running -- the round-1 headline figure.
 `--dump-outputs DIR` writes what the timed iterations computed (dump_outputs) as DIR/<name>.npy, so that two builds can be compared
 output for output on the same seeded inputs.
-Extra keys: jacobian_nnz_per_sec (batched MOI Jacobian callback), roofline (dominant kernel of the step,
-HIP events on the launch stream), cpu_baseline (oracle C port on the host, rank 0, N = 1 only), solve (how the
-instances ended), full_solves (T = 101, the reference example's horizon), dense_blocks (configs[4]).
+A plain run does only what the headline figure needs: set-up, warm-up, the timed iterations, the dump, the result line (with
+`iteration_throughput` and `solve`, how the instances ended: both read from counters the loop keeps anyway).
+`--full` adds what is measured beside it: jacobian_nnz_per_sec (batched MOI Jacobian callback), roofline (dominant kernel of the
+step, HIP events on the launch stream of every timed launch), cpu_baseline (oracle C port on the host, rank 0, N = 1 only), the
+all-gather of the trajectories, full_solves (T = 101, the reference example's horizon), full_solves_T<horizon> (--steps form) and
+dense_blocks (configs[4]).
 """
 import argparse
 import json
@@ -69,14 +72,77 @@ def make_guesses(s, p, B, seed, rng=None):
     return Z
 
 
-def make_guesses_device(s, p, B, seed, dev, chunk=32768):
-    """The same guesses (one seeded stream, instance after instance) built on the device chunk by chunk: the host never
-    holds more than `chunk` trajectories (1.3 GB) however large the batch is."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    z0 = torch.empty((B, s.nlp.num_variables), device=dev, dtype=torch.float64)
+class ControlDraws:
+    """The u ~ N(0,1) of make_guesses for instances 0 .. B-1 of the stream PCG64(seed), drawn ahead by a background thread,
+    `chunk` instances at a time, into one host array (8 (T-1) m bytes per instance).  bench.py starts it before torch / HIP are
+    loaded, so that the draw (a few seconds at the default batch, sequential: one stream) overlaps their start-up."""
+
+    def __init__(self, B, T, nu, seed, chunk=32768):
+        import threading
+        self.U = np.empty((B, T - 1, nu))
+        self.chunk, self.seed = chunk, seed
+        self.done, self.error, self.stop = 0, None, False
+        self.cv = threading.Condition()
+        self.thread = threading.Thread(target=self._draw, daemon=True)
+        self.thread.start()
+
+    def _draw(self):
+        try:
+            rng = np.random.Generator(np.random.PCG64(self.seed))
+            for b0 in range(0, len(self.U), self.chunk):
+                if self.stop:
+                    return
+                nb = min(self.chunk, len(self.U) - b0)
+                rng.standard_normal(out=self.U[b0:b0 + nb])      # the GIL is released while it fills
+                with self.cv:
+                    self.done = b0 + nb
+                    self.cv.notify_all()
+        except Exception as e:     # handed to the consumer: take() raises it
+            with self.cv:
+                self.error = e
+                self.cv.notify_all()
+
+    def take(self, b0, nb):
+        """Instances b0 .. b0+nb-1 (waits until they are drawn)."""
+        with self.cv:
+            self.cv.wait_for(lambda: self.done >= b0 + nb or self.error is not None)
+        if self.done < b0 + nb:
+            raise self.error
+        return self.U[b0:b0 + nb]
+
+    def close(self):
+        self.stop = True
+        self.thread.join()
+        self.U = None
+
+
+def make_guesses_device(s, p, B, seed, dev, chunk=32768, draws=None):
+    """The same guesses as make_guesses (one seeded stream, instance after instance) built on the device chunk by chunk: the
+    host draws only the controls (from `draws`, a ControlDraws of the same seed, or here, `chunk` instances at a time); the
+    device writes the straight-line states of a template row and places the controls -- copies of the same doubles, so the
+    batch is bit-identical to make_guesses."""
+    n = s.nlp
+    T, nx, nu = p["T"], p["n"], p["m"]
+    nz = n.num_variables
+    row = np.zeros(nz)
+    ucols = []
+    for t in range(T):
+        o = t * (nx + nu)
+        row[o:o + nx] = (p["xT"] - p["x1"]) / (T - 1) * t + p["x1"]       # src/utils.jl:1-10, as make_guesses
+        if t < T - 1:
+            ucols.extend(range(o + nx, o + nx + nu))
+    row = torch.from_numpy(row).to(dev)
+    ucols = torch.as_tensor(ucols, device=dev)
+    if draws is not None and (draws.seed != seed or len(draws.U) < B or draws.U.shape[1:] != (T - 1, nu)):
+        raise ValueError("make_guesses_device: the drawn controls are not those of this stream and batch")
+    rng = np.random.Generator(np.random.PCG64(seed)) if draws is None else None
+    z0 = torch.empty((B, nz), device=dev, dtype=torch.float64)
     for b0 in range(0, B, chunk):
         nb = min(chunk, B - b0)
-        z0[b0:b0 + nb] = torch.from_numpy(make_guesses(s, p, nb, seed, rng=rng)).to(dev)
+        U = rng.standard_normal((nb, T - 1, nu)) if draws is None else draws.take(b0, nb)
+        zc = z0[b0:b0 + nb]
+        zc.copy_(row.expand(nb, nz))
+        zc[:, ucols] = torch.from_numpy(U.reshape(nb, (T - 1) * nu)).to(dev)
     return z0
 
 
@@ -295,13 +361,13 @@ def cpu_baseline(a):
 
 
 def self_launch(a):
-    """`python bench.py --gpus N` with no launcher around it: run the CPU baseline once, then N ranks as children of this
+    """`python bench.py --gpus N` with no launcher around it: run the CPU baseline once (--full), then N ranks as children of this
     process (`python -m torch.distributed.run`, rendezvous on 127.0.0.1), forward their output and return their exit code.
     This process never imports torch."""
     import socket
     import subprocess
     env = dict(os.environ)
-    if not a.no_cpu_baseline and not a.loop_only:
+    if a.extras and not a.no_cpu_baseline:
         env["DTO_BENCH_CPU_BASELINE"] = json.dumps(cpu_baseline(a))
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     with socket.socket() as sk:
@@ -340,13 +406,18 @@ def main():
                     help="instances per GPU (default sized for the 288 GB of an MI355X: ~0.36 MB of solver state per instance, ~70 GB stay free; "
                          "> 65536 instances run the plain sequential sweeps, one wavefront per SIMD = 1024 tiles at a time; the larger batch keeps the "
                          "GPU filled while instances converge and leave, DESIGN.md sections 4.2, 7)")
-    ap.add_argument("--no-full-solves", action="store_true", help="skip the T=101 time-to-solution side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the CPU baseline, the launch trace of the timed "
+                         "iterations (roofline), the Jacobian callback, the gather of the trajectories, the full-solve and "
+                         "dense-block side measurements.  Without it a run sets up, warms up, times the steps, dumps (--dump-outputs) "
+                         "and prints the result line")
+    ap.add_argument("--no-full-solves", action="store_true", help="(--full) skip the T=101 time-to-solution side measurement")
     ap.add_argument("--loop-only", action="store_true",
-                    help="run only the headline loop (warm-up + timed iterations) and print value / ms_per_step: the command "
-                         "profiled under rocprofv3 so that the kernel statistics contain nothing but that loop")
+                    help="run only the headline loop (warm-up + timed iterations), even with --full: what a run without --full does, "
+                         "the command profiled under rocprofv3 so that the kernel statistics contain nothing but that loop")
     ap.add_argument("--horizon", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dense-blocks", action="store_true", help="skip the configs[4] (dense 129x129 blocks) side measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-dense-blocks", action="store_true", help="(--full) skip the configs[4] (dense 129x129 blocks) side measurement")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="(tests) ranks only join a gloo group on the CPU, all-reduce their rank and rank 0 prints one line: "
                          "exercises the self-launch path of --gpus N without a GPU")
@@ -356,6 +427,7 @@ def main():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    a.extras = a.full and not a.loop_only
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as CHILD processes
@@ -370,11 +442,20 @@ def main():
     cpu = None
     if rank == 0 and os.environ.get("DTO_BENCH_CPU_BASELINE"):      # measured by the self-launching parent
         cpu = json.loads(os.environ["DTO_BENCH_CPU_BASELINE"])
-    elif rank == 0 and world == 1 and not a.no_cpu_baseline and not a.loop_only:
+    elif rank == 0 and world == 1 and a.extras and not a.no_cpu_baseline:
         cpu = cpu_baseline(a)
     if a.launcher_selftest:
         launcher_selftest(rank, world, cpu)
         return
+
+    import dto_amd
+    from dto_amd import problems as P
+    from dto_amd.parallel import gather_trajectories
+
+    T = a.horizon
+    p = P.build_acrobot(T=T, evaluate_hessian=True)
+    # the controls of this rank's guesses are drawn on the host while torch and HIP start (after the CPU baseline: not beside it)
+    draws = ControlDraws(a.batch, T, p["m"], 1000 + rank)
     dist = None
     # DTO_BENCH_FORCE_DIST=1: initialise RCCL and run every collective of the N > 1 path with ONE rank too (what a 1-GPU box can show
     # of the multi-GPU path on hardware: process-group set-up, the sizing all-reduces, the chunked all-gather of the trajectories)
@@ -391,11 +472,7 @@ def main():
         torch.cuda.set_device(0)
     dev = torch.device("cuda", torch.cuda.current_device())
 
-    import dto_amd
-    from dto_amd import problems as P
-    from dto_amd.parallel import gather_trajectories
-
-    T, B = a.horizon, a.batch
+    B = a.batch
     # Safety net for the memory-sized default: solver state (~0.36 MB per instance at T = 1000, 0.49 MB when the batch may
     # switch to the chunked form) + z0, zout (0.08 MB) must fit what is free on this GPU with 5 GB to spare (the estimate is the
     # measured high-water mark); shrink by whole residencies of the sequential sweep (131 072 instances) if another process
@@ -419,7 +496,6 @@ def main():
         B = int(bt[0])
     if B != a.batch and rank == 0:
         print(f"[bench] batch reduced from {a.batch} to {B} instances: only {free_b / 1e9:.0f} GB of HBM free", file=sys.stderr, flush=True)
-    p = P.build_acrobot(T=T, evaluate_hessian=True)
     s = dto_amd.Solver(p["dynamics"], p["objective"], p["constraints"], p["bounds"], evaluate_hessian=True, name="acrobot")
     n = s.nlp
     nz, nc, nj, nh = n.num_variables, n.num_constraint, n.num_jacobian, int(n.sizes.nnz_hess_key)
@@ -435,7 +511,7 @@ def main():
         try:
             # (inside the try: after a failed allocation HIP's last-error state used to outlive the failure and the next torch
             #  launch tripped over it -- hip_fail now reads it, and a failure here is retried like one in begin: ADVICE r5)
-            z0 = make_guesses_device(s, p, B, 1000 + rank, dev)
+            z0 = make_guesses_device(s, p, B, 1000 + rank, dev, draws=draws)
             s.begin_batch(z0.data_ptr(), B, nz, stream=st)
         except RuntimeError:
             ok = 0
@@ -453,14 +529,16 @@ def main():
         if rank == 0:
             print(f"[bench] dto_solver_begin failed at {B} instances; retrying with {B - 131072}", file=sys.stderr, flush=True)
         B -= 131072
+    draws.close()
+    del draws
     if a.warmup:
         s.iterate_batch(a.warmup, stream=st)
     torch.cuda.synchronize()
     it0 = s.scalar_batch("iter").copy()
     nf0 = s.scalar_batch("nfact").copy()
     # every kernel launch of the TIMED iterations carries a HIP event pair on the stream it is launched on (include/dto.h:
-    # dto_solver_trace; read after the timed region): the `roofline` object below describes exactly the iterations `value` counts
-    if not a.loop_only:
+    # dto_solver_trace; read after the timed region): the `roofline` object of --full describes exactly the iterations `value` counts
+    if a.extras:
         s.trace(True)
     if dist is not None:
         dist.barrier()
@@ -506,19 +584,6 @@ def main():
     thr0 = torch.tensor([B * first_k / first_t], device=dev, dtype=torch.float64)
     if dist is not None:
         dist.all_reduce(thr0, op=dist.ReduceOp.SUM)
-    if a.loop_only:
-        dumped = None
-        if a.dump_outputs and rank == 0:
-            del z0
-            dumped = dump_outputs(a.dump_outputs, s, B, dev, st)
-        if rank == 0:
-            print(json.dumps(dict(value=iters_done / dt, unit="SQP iterations/s", n_gpus=world, steps=a.steps, warmup=a.warmup,
-                                  ms_per_step=dt / a.steps * 1e3, instances_per_gpu=B, time_partitions=s.partitions(), engine=s.engine(),
-                                  factorizations_per_iteration=round(facts_done / max(iters_done, 1.0), 3),
-                                  **({"dumped_outputs": dumped} if dumped else {}))), flush=True)
-        if dist is not None:
-            dist.destroy_process_group()
-        return
     solve_info = dict(converged=int(np.sum(status_end == 1)), acceptable=int(np.sum(status_end == 4)),
                       iteration_limit=int(np.sum(status_end == 2)), failed=int(np.sum((status_end == 3) | (status_end == 5))),
                       still_running=int(np.sum(status_end == 0)), instances=B,
@@ -527,6 +592,34 @@ def main():
                       profile=[dict(iterations=int(k), seconds=round(t, 3), running=r) for k, t, r in profile[:: max(1, len(profile) // 10)]]
                       + [dict(iterations=int(profile[-1][0]), seconds=round(profile[-1][1], 3), running=int(np.sum(status_end == 0)))],
                       note="rank 0's shard; status per instance after the timed iterations")
+
+    # the result line: what a plain run prints, and the head of --full's
+    head = dict(
+        metric="SQP iterations/sec + Jacobian nnz/sec, acrobot T=1000, 1->8 GPU",
+        value=iters_done / dt, unit="SQP iterations/s", n_gpus=world, steps=a.steps, warmup=a.warmup,
+        ms_per_step=dt / a.steps * 1e3, higher_is_better=True, scaling="weak", vs_baseline=None,
+        dtype="f64", data="synthetic",
+        config=dict(workload=f"acrobot swing-up, implicit midpoint h=0.05, T={T}, exact Hessians, "
+                             f"{B} independent instances per GPU (BASELINE.json configs[2])",
+                    horizon=T, instances_per_gpu=B, instances_total=B * world, num_variables=nz, num_constraint=nc,
+                    jacobian_nnz=nj, hessian_key=nh,
+                    parallelism=f"instance sharding x{world}" + (", all-gather of trajectories" if a.extras else ""),
+                    collective_backend=("nccl (RCCL)" if dist is not None else None)))
+    iteration_throughput = dict(value=float(thr0[0]), unit="SQP iterations/s",
+                                note=f"first {first_k} timed iterations, every instance still running")
+    if not a.extras:
+        dumped = None
+        if a.dump_outputs and rank == 0:
+            del z0
+            dumped = dump_outputs(a.dump_outputs, s, B, dev, st)
+        if rank == 0:
+            print(json.dumps(dict(head, iteration_throughput=iteration_throughput, solve=solve_info,
+                                  factorizations_per_iteration=round(facts_done / max(iters_done, 1.0), 3), instances_per_gpu=B,
+                                  time_partitions=s.partitions(), engine=s.engine(),
+                                  **({"dumped_outputs": dumped} if dumped else {}))), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel durations OF THE TIMED ITERATIONS (the launch trace recorded above)
     fp = s.footprint()
@@ -691,18 +784,9 @@ def main():
 
     if rank == 0:
         out = dict(
-            metric="SQP iterations/sec + Jacobian nnz/sec, acrobot T=1000, 1->8 GPU",
-            value=iters_done / dt, unit="SQP iterations/s", n_gpus=world, steps=a.steps, warmup=a.warmup,
-            ms_per_step=dt / a.steps * 1e3, higher_is_better=True, scaling="weak", vs_baseline=None,
-            dtype="f64", data="synthetic",
-            config=dict(workload=f"acrobot swing-up, implicit midpoint h=0.05, T={T}, exact Hessians, "
-                                 f"{B} independent instances per GPU (BASELINE.json configs[2])",
-                        horizon=T, instances_per_gpu=B, instances_total=B * world, num_variables=nz, num_constraint=nc,
-                        jacobian_nnz=nj, hessian_key=nh, parallelism=f"instance sharding x{world}, all-gather of trajectories",
-                        collective_backend=("nccl (RCCL)" if dist is not None else None)),
+            head,
             jacobian_nnz_per_sec=float(jt[0]), jacobian=jac,
-            iteration_throughput=dict(value=float(thr0[0]), unit="SQP iterations/s",
-                                      note=f"first {first_k} timed iterations, every instance still running"),
+            iteration_throughput=iteration_throughput,
             solve=solve_info,
             factorizations_per_iteration=round(nfact_per_iter, 3), time_partitions=time_partitions,
             gathered_trajectories=n_gathered, gathered_status_sum=float(gsum), hbm_free_min_gb=hbm_free_min_gb, engine=engine_name,

@@ -1,6 +1,6 @@
 """bench.py prints ONE JSON line with the fields the driver reads (metric, value, unit, n_gpus, steps, warmup, ms_per_step,
-higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus the `roofline` and `cpu_baseline` objects.  Run here
-on a small batch (8 192 instances, T = 200, a few iterations) as a child process, the way the driver starts it."""
+higher_is_better, scaling, vs_baseline, dtype, data, config.workload); with --full also the `roofline` and `cpu_baseline`
+objects.  Run here on a small batch (8 192 instances, T = 200, a few iterations) as a child process, the way the driver starts it."""
 import json
 import os
 import subprocess
@@ -22,7 +22,7 @@ def _run(args, timeout=900):
 
 
 def test_bench_line_has_the_contract_fields():
-    d = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "8192", "--horizon", "200", "--no-full-solves",
+    d = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "8192", "--horizon", "200", "--full", "--no-full-solves",
               "--no-dense-blocks", "--no-cpu-baseline"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline"):
@@ -48,10 +48,37 @@ def test_bench_line_has_the_contract_fields():
     assert r["limited_by"] is None or r["limited_by"]["source"].startswith("profiles/")
 
 
+def test_plain_run_prints_the_contract_fields_and_nothing_it_did_not_measure():
+    """Without --full a run sets up, warms up, times the steps and prints the result line: the contract fields mean what they
+    mean with --full, and none of the side measurements is taken."""
+    d = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "8192", "--horizon", "200"])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "iteration_throughput", "solve"):
+        assert k in d, k
+    assert d["metric"] == "SQP iterations/sec + Jacobian nnz/sec, acrobot T=1000, 1->8 GPU" and d["unit"] == "SQP iterations/s"
+    assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 8192 * 4 / (d["ms_per_step"] * 4e-3)) <= 0.02 * d["value"]
+    for k in ("roofline", "cpu_baseline", "jacobian", "jacobian_nnz_per_sec", "gathered_trajectories", "full_solves",
+              "full_solves_T200", "dense_blocks"):
+        assert k not in d, k
+    assert d["solve"]["instances"] == 8192 and d["solve"]["iterations_median"] > 0
+
+
+def test_plain_and_full_runs_compute_the_same(tmp_path):
+    """The timed steps of a plain run and of a --full run (launch trace on) leave the same state: the dumps are identical."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8192", "--horizon", "200"]
+    _run(args + ["--dump-outputs", str(tmp_path / "plain")])
+    _run(args + ["--full", "--no-full-solves", "--no-dense-blocks", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    for k in ("instance", "status", "iterations", "z", "multipliers"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f"{k}.npy"), np.load(tmp_path / "full" / f"{k}.npy")), k
+
+
 def test_bench_steps_form_carries_full_solves_of_the_headline_workload():
     """`--steps K` (the driver's form) times K iterations; the full solves SURVEY section 8(d) defines the metric over ride along as
     `full_solves_T<horizon>` (here on a short horizon and a small batch)."""
-    d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2048", "--horizon", "101", "--no-dense-blocks", "--no-cpu-baseline"])
+    d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2048", "--horizon", "101", "--full", "--no-dense-blocks",
+              "--no-cpu-baseline"])
     f = d["full_solves_T101"]
     for k in ("instances", "seconds", "converged", "converged_fraction", "iterations_median_converged", "iterations_p99_converged",
               "converged_solves_per_sec", "iteration_limit"):
@@ -62,7 +89,7 @@ def test_bench_steps_form_carries_full_solves_of_the_headline_workload():
 def test_roofline_of_a_run_with_several_slices_is_taken_over_the_first():
     """More than 25 timed iterations (the default run times 1000): the batch is repacked between slices and instances leave, so the
     `roofline` object describes the first slice -- every instance running -- and says so."""
-    d = _run(["--gpus", "1", "--steps", "30", "--warmup", "0", "--batch", "8192", "--horizon", "200", "--no-full-solves",
+    d = _run(["--gpus", "1", "--steps", "30", "--warmup", "0", "--batch", "8192", "--horizon", "200", "--full", "--no-full-solves",
               "--no-dense-blocks", "--no-cpu-baseline"])
     r = d["roofline"]
     assert r["iterations_traced"] == 25 and "first 25 of the 30" in r["window"]
@@ -95,7 +122,8 @@ def test_dump_outputs(tmp_path):
 
 def test_cpu_baseline_object():
     """The `cpu_baseline` leg (oracle's C port in a child process started before torch / HIP) on a short horizon."""
-    d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4096", "--horizon", "200", "--no-full-solves", "--no-dense-blocks"])
+    d = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4096", "--horizon", "200", "--full", "--no-full-solves",
+              "--no-dense-blocks"])
     c = d["cpu_baseline"]
     for k in ("value", "unit", "cores", "kind", "sample", "value_1core", "scaling_vs_1core", "all_cores", "host"):
         assert k in c, k
@@ -111,7 +139,7 @@ def test_collective_path_with_one_rank_over_rccl():
     env = dict(os.environ, DTO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29537", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "131072",
-           "--no-full-solves", "--no-dense-blocks", "--no-cpu-baseline"]
+           "--full", "--no-full-solves", "--no-dense-blocks", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -6,6 +6,7 @@ import sys
 import textwrap
 
 import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -89,6 +90,39 @@ def test_chunked_guess_generation_is_the_same_stream():
     for chunk in (1, 7, 23, 100):
         got = make_guesses_device(s, p, 23, 5, torch.device("cpu"), chunk=chunk).numpy()
         assert np.array_equal(got, whole), chunk
+
+
+def test_guesses_from_controls_drawn_ahead_are_the_same_stream():
+    """bench.py draws the controls of its guesses in a background thread while torch and HIP start (ControlDraws, its own chunk
+    size) and places them on the device: the batch is bit-identical to make_guesses, whatever the two chunk sizes."""
+    import numpy as np
+    import torch
+    from conftest import product_solver
+    from bench import ControlDraws, make_guesses, make_guesses_device
+    s, p = product_solver("acrobot", 12)
+    whole = make_guesses(s, p, 23, seed=5)
+    for draw_chunk, chunk in ((1, 23), (4, 7), (30, 1), (8, 100)):
+        d = ControlDraws(30, 12, p["m"], 5, chunk=draw_chunk)
+        got = make_guesses_device(s, p, 23, 5, torch.device("cpu"), chunk=chunk, draws=d).numpy()
+        d.close()
+        assert np.array_equal(got, whole), (draw_chunk, chunk)
+    d = ControlDraws(23, 12, p["m"], 6)
+    with pytest.raises(ValueError):           # controls of another stream are refused
+        make_guesses_device(s, p, 23, 5, torch.device("cpu"), draws=d)
+    d.close()
+
+
+def test_plain_run_leaves_out_the_cpu_baseline():
+    """Without --full the self-launching parent runs no CPU baseline (it is one of --full's side measurements)."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launcher-selftest"],
+                         capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["launcher_selftest"] is True and d["n_gpus"] == 2 and d["cpu_baseline"] is None
 
 
 def test_bench_starts_its_own_ranks_when_no_launcher_did():

@@ -1,5 +1,5 @@
 for B in 8192 12288 18432 24576 65536; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --batch $B --no-full-solves --no-dense-blocks --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --gpus 1 --steps 20 --warmup 5 --batch $B --full --no-full-solves --no-dense-blocks --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):
