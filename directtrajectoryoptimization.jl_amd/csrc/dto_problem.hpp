@@ -16,6 +16,7 @@ int hip_fail(hipError_t e, const char* what);
 
 struct SolverState;  // dto_solver.cpp
 struct ImState;      // dto_solver.cpp: instance-major engine
+struct WideState;    // dto_solver.cpp: solver state of the tile (MFMA) path
 
 // dto_solver_trace: a HIP event pair around every kernel launch of the solver entry points, on the stream the kernel is launched
 // on (the caller's, or the low-priority one of the early back substitutions) -- so that a caller can report what each kernel
@@ -58,6 +59,8 @@ struct Problem {
   hipStream_t stream = nullptr;
   SolverState* solver = nullptr;
   ImState* im = nullptr;
+  WideState* wide = nullptr;   // tile path: iterate, multipliers and host records of the batch begun last
+  int* d_shift_keep = nullptr; // dto_solver_shift_keep_rows: [Nc] 1 = the multiplier of this row stays with its knot (NULL: none)
   LaunchTrace* trace = nullptr;   // dto_solver_trace
   int hessian_mode_last = -1;     // dto_solver_hessian_mode: what the last solve / begun batch used
   int engine_req = 0;      // dto_solver_set_engine: 0 automatic, 1 SoA tiles, 2 instance-major

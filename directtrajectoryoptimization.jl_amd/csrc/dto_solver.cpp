@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -144,7 +145,10 @@ struct ImState {
   }
 };
 
+static void release_wide(Problem* p);
+
 void Problem::free_solver() {
+  release_wide(this);
   if (solver) {
     solver->release();
     delete solver;
@@ -196,7 +200,7 @@ static void default_opts(dto_solver_opts& o, const dto_options& u) {
 
 struct BorderStats;
 // Ipopt's scaled optimality error (Waechter & Biegler 2006, (5)-(6)) and monotone barrier update (7), shared by the two host-driven
-// barrier loops of this file (tile path: wide_solve_batch; bordered path: general_solve_batch) -- the in-kernel iteration has the
+// barrier loops of this file (tile path: wide_outer; bordered path: general_solve_batch) -- the in-kernel iteration has the
 // same expressions in conv_body (the two loops had drifted apart -- the bordered one left the slack multipliers out of
 // s_d and reset theta_max with the filter).  On a decrease of mu the FILTER is reset, theta_max / theta_min stay (Ipopt, step A-3).
 struct ErrScale { double sd, sc; };
@@ -276,12 +280,7 @@ static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t l
 }
 
 
-// ------------------------------------------------------------------------------------------------
-// Solver for wide-stage models (configs[4]): the same filter line-search SQP iteration as the register path, driven from
-// the host -- one iteration costs a dense block factorisation per instance (hundreds of milliseconds at T = 2000), so a
-// few stream synchronisations per iteration are free.  Scope: dynamics rows plus variables fixed by equal bounds (what
-// the model uses); no inequality rows / finite bounds (no barrier).
-// ------------------------------------------------------------------------------------------------
+// ---- wide-stage models: helpers of the host-driven solver below (wide_outer)
 constexpr int AXPY_BLOCKS_PER_ROW = 64;
 static __global__ void k_rows_axpy(double* y, const double* x, const double* alpha, int64_t n, int64_t ldy, int64_t ldx) {
   // grid.x = B * AXPY_BLOCKS_PER_ROW (the instance index lives in grid.x: grid.y is limited to 65535)
@@ -340,26 +339,173 @@ static __global__ void k_wide_update_bounds(const double* z, const double* dz, d
   }
 }
 
-static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
-                            double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations) {
+// warm start (dto_solver_begin_warm on the tile path): the rules of k_init's warm branch -- variables with lo == hi go to their
+// bound (whether or not the problem has other finite bounds), the others are pushed into the interior as at a cold start, positive
+// bound multipliers of the previous solve are kept and non-positive ones re-initialised to mu / gap with the instance's new mu.
+// zl / zu / mu are NULL when the problem has no finite bounds (no barrier).  The dynamics multipliers are not touched.
+static __global__ void k_wide_init_warm(double* z, double* zl, double* zu, const double* lo, const double* hi, const double* mu,
+                                        double bound_push, double bound_frac, int64_t n) {
+  const int64_t b = blockIdx.x / AXPY_BLOCKS_PER_ROW, blk = blockIdx.x % AXPY_BLOCKS_PER_ROW;
+  const double m = mu ? mu[b] : 0.0;
+  for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x) {
+    double v = z[b * n + i], l = 0.0, u = 0.0;
+    const double a = lo[i], c = hi[i];
+    if (a == c) v = a;
+    else {
+      const bool fl = a > -1e300, fh = c < 1e300;
+      if (fl && fh) {
+        const double pl = fmin(bound_push * fmax(1.0, fabs(a)), bound_frac * (c - a));
+        const double pu = fmin(bound_push * fmax(1.0, fabs(c)), bound_frac * (c - a));
+        v = fmin(fmax(v, a + pl), c - pu);
+      } else if (fl) v = fmax(v, a + bound_push * fmax(1.0, fabs(a)));
+      else if (fh) v = fmin(v, c - bound_push * fmax(1.0, fabs(c)));
+      if (zl) {
+        const double pl = zl[b * n + i], pu = zu[b * n + i];
+        if (fl) l = pl > 0.0 ? pl : m / (v - a);
+        if (fh) u = pu > 0.0 ? pu : m / (c - v);
+      }
+    }
+    z[b * n + i] = v;
+    if (zl) { zl[b * n + i] = l; zu[b * n + i] = u; }
+  }
+}
+
+// receding horizon on the tile path: out = in moved forward by k knots, instance-major [B][n] with a uniform stride per knot
+// (n + m variables, or n dynamics rows).  Block t of out = block min(t + k, T_blocks - 1) of in; in the blocks that enter at the
+// end the first last_len entries take the final state (the trailing short block: x_T without an action), the rest repeat the
+// last action.  Entries behind the blocks, and rows with keep[j] != 0 (the stage rows an embedded problem carries as dynamics
+// rows), keep their values.  One thread per entry, out of place: one read and one write of the array.
+static __global__ void k_wide_shift_knots(const double* in, double* out, int64_t n, int64_t total, int stride, int T_blocks,
+                                          int last_len, int k, const int* keep) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t b = idx / n, j = idx % n;
+  int64_t src = j;
+  const int64_t t = j / stride, r = j % stride;
+  if (t < T_blocks && !(keep && keep[j])) {
+    if (t + k < T_blocks) src = (t + k) * stride + r;
+    else if (r < last_len) src = (int64_t)T_blocks * stride + r;
+    else src = (int64_t)(T_blocks - 1) * stride + r;
+  }
+  out[b * n + j] = in[b * n + src];
+}
+
+// ---- the tile-path solver state (dto_solver_begin / iterate / run / end / begin_warm / shift on a wide plugin) ----------------
+// Host record of one instance: filter ring, inertia-ladder memory, barrier parameter, and the measures of the current iterate
+struct WideInst {
+  int status = 0, iter = 0, ls_fail = 0, full_streak = 0, attempt = 0, acc_count = 0;
+  double f_last = 1e300, mu = 0.0;
+  double dw = 0.0, dlast = 0.0, theta_max = -1.0, theta_min = -1.0, alpha = 0.0, gam = 1.0, gamma_acc = 1.0;
+  std::vector<double> filt;  // (theta, phi) pairs, ring of DTO_FILTER_CAP
+  int filter_n = 0;
+  double f = 0.0, thinf = 0.0, dinf = 0.0;   // at the last convergence test (dto_solver_stats)
+};
+
+struct WideState {
+  int64_t B = 0, len = 0, n_bnd = 0;  // len: doubles per instance of z / lam / zl / zu / tmp (max(Nz, Nc): the shift swaps them)
+  bool barrier = false, begun = false, any_running = false, timed_out = false;
+  double *z = nullptr, *lam = nullptr, *dz = nullptr, *dlam = nullptr, *lo = nullptr, *hi = nullptr, *dw = nullptr,
+         *stats = nullptr, *merit = nullptr, *alpha = nullptr, *gam = nullptr, *zl = nullptr, *zu = nullptr, *mu = nullptr,
+         *alphad = nullptr, *params = nullptr, *tmp = nullptr;
+  int *flags = nullptr, *active = nullptr;
+  bool own_params = false;            // the batch's per-instance parameters, copied at the begin ([B][Nw])
+  dto_options user{};
+  dto_solver_opts opt{};
+  std::vector<WideInst> I;
+  std::vector<int> h_active, h_flags;
+  std::vector<double> h_gam, h_dw, h_stats, h_merit, h_alpha, h_mu, h_alphad;
+  std::chrono::steady_clock::time_point t_start;
+  int dump_launch = 0, dump_merit = 0;
+
+  void release() {
+    for (void* q : {(void*)z, (void*)lam, (void*)dz, (void*)dlam, (void*)lo, (void*)hi, (void*)dw, (void*)stats, (void*)merit,
+                    (void*)alpha, (void*)gam, (void*)zl, (void*)zu, (void*)mu, (void*)alphad, (void*)params, (void*)tmp,
+                    (void*)flags, (void*)active})
+      if (q) (void)hipFree(q);
+    z = lam = dz = dlam = lo = hi = dw = stats = merit = alpha = gam = zl = zu = mu = alphad = params = tmp = nullptr;
+    flags = active = nullptr;
+    B = len = 0; begun = any_running = timed_out = own_params = false;
+    I.clear();
+  }
+};
+
+static void release_wide(Problem* p) {
+  if (p->wide) { p->wide->release(); delete p->wide; p->wide = nullptr; }
+}
+
+// device buffers for a batch of B (kept when the batch size is the same)
+static int wide_alloc(Problem* p, int64_t B, bool barrier) {
+  const Layout& L = p->L;
+  if (p->wide && p->wide->B == B && p->wide->z) return DTO_OK;
+  release_wide(p);
+  p->wide = new WideState();
+  WideState& W = *p->wide;
+  const int64_t len = std::max<int64_t>(L.Nz, std::max<int64_t>(1, L.Nc));
+  const size_t n = (size_t)B * (size_t)len;
+  auto fail = [&](hipError_t e, const char* what) { release_wide(p); return hip_fail(e, what); };
+#define WALLOC(ptr, count) do { hipError_t e_ = hipMalloc((void**)&(ptr), (size_t)(count) * sizeof(*(ptr))); if (e_ != hipSuccess) return fail(e_, "hipMalloc " #ptr); } while (0)
+  WALLOC(W.z, n); WALLOC(W.lam, n); WALLOC(W.tmp, n);
+  WALLOC(W.dz, (size_t)B * L.Nz); WALLOC(W.dlam, (size_t)B * std::max<int64_t>(1, L.Nc));
+  WALLOC(W.lo, L.Nz); WALLOC(W.hi, L.Nz);
+  WALLOC(W.dw, B); WALLOC(W.stats, (size_t)B * DTO_WIDE_NSTAT); WALLOC(W.merit, (size_t)B * 2 * DTO_WIDE_TRIALS);
+  WALLOC(W.alpha, B); WALLOC(W.gam, B); WALLOC(W.flags, B); WALLOC(W.active, B);
+  if (barrier) { WALLOC(W.zl, n); WALLOC(W.zu, n); WALLOC(W.mu, B); WALLOC(W.alphad, B); }
+  if (L.Nw > 0) WALLOC(W.params, (size_t)B * L.Nw);
+#undef WALLOC
+  W.B = B; W.len = len;
+  return DTO_OK;
+}
+
+static void wide_fill_args(Problem* p, dto_wide_args& a) {
+  const Layout& L = p->L;
+  WideState& W = *p->wide;
+  a.T = L.T; a.B = W.B;
+  a.kind = p->d_kind; a.zoff = p->d_zoff; a.woff = p->d_woff; a.cdoff = p->d_cdoff;
+  a.params = W.own_params ? W.params : p->d_params; a.ldw = W.own_params ? L.Nw : 0;
+  a.z = W.z; a.ldz = L.Nz; a.mu = W.lam; a.ldmu = L.Nc;
+  a.delta_w = 0.0; a.delta_c = W.opt.delta_c; a.piv_tol = W.opt.piv_tol;
+  a.dz = W.dz; a.lddz = L.Nz; a.dmu = W.dlam; a.lddmu = L.Nc;
+  a.fac = p->wide_fac; a.flags = W.flags; a.Nc = L.Nc; a.prof = nullptr;
+  a.fixed_lo = W.lo; a.fixed_hi = W.hi; a.dw_inst = W.dw; a.gam_inst = W.gam; a.active = W.active; a.stats = W.stats; a.merit = W.merit;
+  a.zl = W.zl; a.zu = W.zu; a.mu_inst = W.mu; a.tau_min = W.opt.tau_min;
+}
+
+// the batch's parameters: b->params (DEVICE [B][ldp]) copied into the state, NULL = the problem's shared ones
+static int wide_set_params(Problem* p, const dto_batch* b, hipStream_t st) {
+  WideState& W = *p->wide;
+  const int64_t Nw = p->L.Nw;
+  W.own_params = false;
+  if (!b->params || Nw == 0) return DTO_OK;
+  if (b->ldp < Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
+  HIP_TRY(hipMemcpy2DAsync(W.params, Nw * sizeof(double), b->params, b->ldp * sizeof(double), Nw * sizeof(double), W.B,
+                           hipMemcpyDeviceToDevice, st));
+  W.own_params = true;
+  return DTO_OK;
+}
+
+// begin (cold: exactly what dto_solve_batch did before the state existed) or begin_warm
+static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bool warm, double mu0) {
   int rc = p->ensure_device();
   if (rc) return rc;
   const Layout& L = p->L;
   if (L.Nstage != 0 || L.Ngen != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows and bounds only");
+  if (p->wide) p->wide->begun = false;
+  if (warm) {
+    if (!p->wide || !p->wide->z || p->wide->B != b->B)
+      return set_error(DTO_ERR_INVALID, "dto_solver_begin_warm needs the device state of a previous solve of the same batch size");
+  } else if (!b->x) {
+    return set_error(DTO_ERR_INVALID, "null argument");
+  }
+  if (b->x && b->ldx < L.Nz) return set_error(DTO_ERR_INVALID, "ldx < num_variables");
   // finite bounds (lo < hi, one side finite): primal-dual barrier, round 4; n_bnd = number of bound multipliers
   int64_t n_bnd = 0;
   for (int64_t i = 0; i < L.Nz; ++i)
     if (L.var_lo[i] != L.var_hi[i]) n_bnd += (std::isfinite(L.var_lo[i]) ? 1 : 0) + (std::isfinite(L.var_hi[i]) ? 1 : 0);
   const bool barrier = n_bnd > 0;
-  dto_options u;
-  if (opt) u = *opt; else dto_options_default(&u);
-  dto_solver_opts o;
-  default_opts(o, u);
   dto_wide_info info;
   p->vt->wide_info(&info);
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc;
   hipStream_t st = (hipStream_t)b->stream;
-  // device state
   const size_t need_fac = (size_t)B * (size_t)L.T * (size_t)info.fac_stage;
   if (p->wide_fac_len < need_fac) {
     if (p->wide_fac) (void)hipFree(p->wide_fac);
@@ -367,84 +513,91 @@ static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch*
     HIP_TRY(hipMalloc((void**)&p->wide_fac, need_fac * sizeof(double)));
     p->wide_fac_len = need_fac;
   }
-  double *z = nullptr, *lam = nullptr, *dz = nullptr, *dlam = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_dw = nullptr,
-         *d_stats = nullptr, *d_merit = nullptr, *d_alpha = nullptr, *d_gam = nullptr, *d_zl = nullptr, *d_zu = nullptr, *d_mu = nullptr,
-         *d_alphad = nullptr;
-  int *d_flags = nullptr, *d_active = nullptr;
-  auto cleanup = [&]() {
-    for (void* q : {(void*)z, (void*)lam, (void*)dz, (void*)dlam, (void*)d_lo, (void*)d_hi, (void*)d_dw, (void*)d_stats,
-                    (void*)d_merit, (void*)d_alpha, (void*)d_gam, (void*)d_flags, (void*)d_active, (void*)d_zl, (void*)d_zu, (void*)d_mu,
-                    (void*)d_alphad})
-      if (q) (void)hipFree(q);
-  };
-#define WTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return hip_fail(e_, #expr); } } while (0)
-  WTRY(hipMalloc((void**)&z, (size_t)B * Nz * sizeof(double)));
-  WTRY(hipMalloc((void**)&lam, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double)));
-  WTRY(hipMalloc((void**)&dz, (size_t)B * Nz * sizeof(double)));
-  WTRY(hipMalloc((void**)&dlam, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_lo, Nz * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_hi, Nz * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_dw, B * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_stats, (size_t)B * DTO_WIDE_NSTAT * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_merit, (size_t)B * 2 * DTO_WIDE_TRIALS * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_alpha, B * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_gam, B * sizeof(double)));
-  WTRY(hipMalloc((void**)&d_flags, B * sizeof(int)));
-  WTRY(hipMalloc((void**)&d_active, B * sizeof(int)));
-  WTRY(hipMemcpyAsync(d_lo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
-  WTRY(hipMemcpyAsync(d_hi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
-  WTRY(hipMemcpy2DAsync(z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st));
-  WTRY(hipMemsetAsync(lam, 0, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double), st));
-  WTRY(hipMemsetAsync(dz, 0, (size_t)B * Nz * sizeof(double), st));
-  WTRY(hipMemsetAsync(dlam, 0, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double), st));
-  if (barrier) {
-    WTRY(hipMalloc((void**)&d_zl, (size_t)B * Nz * sizeof(double)));
-    WTRY(hipMalloc((void**)&d_zu, (size_t)B * Nz * sizeof(double)));
-    WTRY(hipMalloc((void**)&d_mu, B * sizeof(double)));
-    WTRY(hipMalloc((void**)&d_alphad, B * sizeof(double)));
-    hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, d_zl, d_zu, (const double*)d_lo,
-                       (const double*)d_hi, o.mu_init, o.bound_push, o.bound_frac, Nz);
+  if ((rc = wide_alloc(p, B, barrier))) return rc;
+  WideState& W = *p->wide;
+  W.n_bnd = n_bnd; W.barrier = barrier;
+  if (opt) W.user = *opt; else dto_options_default(&W.user);
+  default_opts(W.opt, W.user);
+  if ((rc = wide_set_params(p, b, st))) return rc;
+  const dto_solver_opts& o = W.opt;
+  if (!warm) {
+    HIP_TRY(hipMemcpyAsync(W.lo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.hi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(W.z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(W.lam, 0, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(W.dz, 0, (size_t)B * Nz * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(W.dlam, 0, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double), st));
+    if (barrier) {
+      hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, W.z, W.zl, W.zu, (const double*)W.lo,
+                         (const double*)W.hi, o.mu_init, o.bound_push, o.bound_frac, Nz);
+      HIP_TRY(hipGetLastError());
+    }
+    W.I.assign((size_t)B, WideInst());
+    W.h_active.assign((size_t)B, 0); W.h_flags.assign((size_t)B, 0);
+    W.h_gam.assign((size_t)B, 1.0);
+    W.h_dw.assign((size_t)B, 0.0); W.h_stats.assign((size_t)B * DTO_WIDE_NSTAT, 0.0);
+    W.h_merit.assign((size_t)B * 2 * DTO_WIDE_TRIALS, 0.0); W.h_alpha.assign((size_t)B, 0.0);
+    W.h_mu.assign((size_t)B, barrier ? o.mu_init : 0.0); W.h_alphad.assign((size_t)B, 0.0);
+    for (auto& s : W.I) s.mu = barrier ? o.mu_init : 0.0;
+  } else {
+    // every host record starts afresh as k_init resets its scalars (status, iterations, filter, ladder memory, theta_max /
+    // theta_min, acceptable-level counter); the barrier parameter stays unless mu0 > 0
+    if (b->x) HIP_TRY(hipMemcpy2DAsync(W.z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st));
+    for (int64_t i = 0; i < B; ++i) {
+      WideInst& s = W.I[(size_t)i];
+      const double m = !barrier ? 0.0 : (mu0 > 0.0 ? mu0 : (s.mu > 0.0 ? s.mu : o.mu_init));
+      s = WideInst();
+      s.mu = m;
+      W.h_mu[(size_t)i] = m;
+      W.h_gam[(size_t)i] = 1.0;
+    }
+    if (barrier) HIP_TRY(hipMemcpyAsync(W.mu, W.h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_wide_init_warm, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, W.z, W.zl, W.zu, (const double*)W.lo,
+                       (const double*)W.hi, (const double*)W.mu, o.bound_push, o.bound_frac, Nz);
+    HIP_TRY(hipGetLastError());
   }
+  if (barrier && !warm) HIP_TRY(hipMemcpyAsync(W.mu, W.h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+  W.dump_launch = W.dump_merit = 0;
+  W.t_start = std::chrono::steady_clock::now();   // Options.max_cpu_time counts from here
+  W.timed_out = false;
+  W.any_running = true;
+  W.begun = true;
+  p->hessian_mode_last = DTO_HESSIAN_EXACT;
+  return DTO_OK;
+}
 
-  struct Inst {
-    int status = 0, iter = 0, ls_fail = 0, full_streak = 0, attempt = 0, acc_count = 0;
-    double f_last = 1e300, mu = 0.0;
-    double dw = 0.0, dlast = 0.0, theta_max = -1.0, theta_min = -1.0, alpha = 0.0, gam = 1.0, gamma_acc = 1.0;
-    std::vector<double> filt;  // (theta, phi) pairs, ring of DTO_FILTER_CAP
-    int filter_n = 0;
-  };
-  std::vector<Inst> I((size_t)B);
-  std::vector<int> h_active((size_t)B), h_flags((size_t)B);
-  std::vector<double> h_gam((size_t)B, 1.0);
-  std::vector<double> h_dw((size_t)B), h_stats((size_t)B * DTO_WIDE_NSTAT), h_merit((size_t)B * 2 * DTO_WIDE_TRIALS), h_alpha((size_t)B);
-  std::vector<double> h_mu((size_t)B, barrier ? o.mu_init : 0.0), h_alphad((size_t)B, 0.0);
-  for (auto& s : I) s.mu = barrier ? o.mu_init : 0.0;
-  if (barrier) WTRY(hipMemcpyAsync(d_mu, h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+// ------------------------------------------------------------------------------------------------
+// Solver for wide-stage models (configs[4]): the same filter line-search SQP iteration as the register path, driven from
+// the host -- one iteration costs a dense block factorisation per instance (hundreds of milliseconds at T = 2000), so a
+// few stream synchronisations per iteration are free.  One call = one outer iteration of every running instance.
+// ------------------------------------------------------------------------------------------------
+static int wide_outer(Problem* p, hipStream_t st) {
+  WideState& W = *p->wide;
+  const Layout& L = p->L;
+  const dto_solver_opts& o = W.opt;
+  const int64_t B = W.B, Nz = L.Nz, Nc = L.Nc;
+  const bool barrier = W.barrier;
+  const int64_t n_bnd = W.n_bnd;
+  std::vector<WideInst>& I = W.I;
+  std::vector<int>&h_active = W.h_active, &h_flags = W.h_flags;
+  std::vector<double>&h_gam = W.h_gam, &h_dw = W.h_dw, &h_stats = W.h_stats, &h_merit = W.h_merit, &h_alpha = W.h_alpha,
+                     &h_mu = W.h_mu, &h_alphad = W.h_alphad;
+  double *z = W.z, *lam = W.lam, *dz = W.dz, *dlam = W.dlam, *d_lo = W.lo, *d_hi = W.hi, *d_dw = W.dw, *d_stats = W.stats,
+         *d_merit = W.merit, *d_alpha = W.alpha, *d_gam = W.gam, *d_zl = W.zl, *d_zu = W.zu, *d_mu = W.mu, *d_alphad = W.alphad;
+  int *d_flags = W.flags, *d_active = W.active;
   dto_wide_args a;
-  a.T = L.T; a.B = B;
-  a.kind = p->d_kind; a.zoff = p->d_zoff; a.woff = p->d_woff; a.cdoff = p->d_cdoff;
-  a.params = b->params ? b->params : p->d_params; a.ldw = b->params ? b->ldp : 0;
-  a.z = z; a.ldz = Nz; a.mu = lam; a.ldmu = Nc;
-  a.delta_w = 0.0; a.delta_c = o.delta_c; a.piv_tol = o.piv_tol;
-  a.dz = dz; a.lddz = Nz; a.dmu = dlam; a.lddmu = Nc;
-  a.fac = p->wide_fac; a.flags = d_flags; a.Nc = Nc; a.prof = nullptr;
-  a.fixed_lo = d_lo; a.fixed_hi = d_hi; a.dw_inst = d_dw; a.gam_inst = d_gam; a.active = d_active; a.stats = d_stats; a.merit = d_merit;
-  a.zl = d_zl; a.zu = d_zu; a.mu_inst = d_mu; a.tau_min = o.tau_min;
+  wide_fill_args(p, a);
   auto launch = [&](int op) -> int {
     const int lrc = p->vt->launch_wide(op, &a, (void*)st);
     return lrc;
   };
-  const auto t_start = std::chrono::steady_clock::now();
-  bool timed_out = false;   // Options.max_cpu_time expired: the running instances come back with DTO_STATUS_CPU_TIME
   constexpr double G_TH = 1e-5, G_PHI = 1e-8, S_TH = 1.1, S_PHI = 2.3, ETA = 1e-8;
   const char* dump_prefix = getenv("DTO_WIDE_DUMP");   // debug: <prefix>_L<k>_<what>.bin of the first DTO_WIDE_DUMP_MAX launches
-  int dump_launch = 0, dump_merit = 0;
   const int dump_max = getenv("DTO_WIDE_DUMP_MAX") ? atoi(getenv("DTO_WIDE_DUMP_MAX")) : 1;
-  bool any_running = true;
-  while (any_running) {
+  {
     // ---- A: first factorisation attempt of every running instance
     for (int64_t i = 0; i < B; ++i) {
-      Inst& s = I[(size_t)i];
+      WideInst& s = I[(size_t)i];
       h_active[(size_t)i] = s.status == 0;
       if (s.status != 0) continue;
       s.attempt = 0;
@@ -457,23 +610,25 @@ static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch*
     }
     bool first_pass = true;
     for (;;) {
-      WTRY(hipMemcpyAsync(d_active, h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-      WTRY(hipMemcpyAsync(d_dw, h_dw.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
-      WTRY(hipMemcpyAsync(d_gam, h_gam.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
-      { const int lrc = launch(DTO_WIDE_STEP); if (lrc) { cleanup(); return hip_fail((hipError_t)lrc, "wide step"); } }
-      WTRY(hipMemcpyAsync(h_flags.data(), d_flags, B * sizeof(int), hipMemcpyDeviceToHost, st));
-      WTRY(hipMemcpyAsync(h_stats.data(), d_stats, h_stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      WTRY(hipStreamSynchronize(st));
-      if (dump_prefix && dump_launch < dump_max) {
+      HIP_TRY(hipMemcpyAsync(d_active, h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_dw, h_dw.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_gam, h_gam.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+      { const int lrc = launch(DTO_WIDE_STEP); if (lrc) return hip_fail((hipError_t)lrc, "wide step"); }
+      HIP_TRY(hipMemcpyAsync(h_flags.data(), d_flags, B * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(h_stats.data(), d_stats, h_stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (dump_prefix && W.dump_launch < dump_max) {
         // debug (tools/wide_debug.py): everything the launch produced -- factor records, step, statistics, flags -- plus its inputs
         auto wr = [&](const char* what, const void* dptr, size_t bytes) {
           std::vector<char> hb(bytes);
           if (hipMemcpy(hb.data(), dptr, bytes, hipMemcpyDeviceToHost) != hipSuccess) return;
           char fn[1024];
-          snprintf(fn, sizeof(fn), "%s_L%d_%s.bin", dump_prefix, dump_launch, what);
+          snprintf(fn, sizeof(fn), "%s_L%d_%s.bin", dump_prefix, W.dump_launch, what);
           if (FILE* f = fopen(fn, "wb")) { fwrite(hb.data(), 1, bytes, f); fclose(f); }
         };
-        wr("fac", p->wide_fac, need_fac * sizeof(double));
+        dto_wide_info info;
+        p->vt->wide_info(&info);
+        wr("fac", p->wide_fac, (size_t)B * (size_t)L.T * (size_t)info.fac_stage * sizeof(double));
         wr("dz", dz, (size_t)B * Nz * sizeof(double));
         wr("dlam", dlam, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double));
         wr("z", z, (size_t)B * Nz * sizeof(double));
@@ -482,16 +637,17 @@ static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch*
         wr("flags", d_flags, (size_t)B * sizeof(int));
         wr("dw", d_dw, (size_t)B * sizeof(double));
         wr("active", d_active, (size_t)B * sizeof(int));
-        ++dump_launch;
+        ++W.dump_launch;
       }
       bool again = false, mu_moved = false;
       for (int64_t i = 0; i < B; ++i) {
         if (!h_active[(size_t)i]) continue;
-        Inst& s = I[(size_t)i];
+        WideInst& s = I[(size_t)i];
         const double* sv = &h_stats[(size_t)i * DTO_WIDE_NSTAT];
         if (first_pass) {
           // ---- B: convergence test at the current iterate (Ipopt's scaled error, reference Options tolerances)
           const double f = sv[DTO_WIDE_F], th1 = sv[DTO_WIDE_TH1], thinf = sv[DTO_WIDE_THINF], dinf = sv[DTO_WIDE_DINF];
+          s.f = f; s.thinf = thinf; s.dinf = dinf;
           // Ipopt's scaling with the bound multipliers included; complementarity measured against mu_target (as k_conv does)
           const double sumz = barrier ? sv[DTO_WIDE_SUMZ] : 0.0;
           const ErrScale es = ipopt_scaling(o, sv[DTO_WIDE_SUMLAM], Nc, sumz, n_bnd);
@@ -525,13 +681,13 @@ static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch*
       if (first_pass && mu_moved) {
         // the barrier parameter of some instance moved: its step (and statistics) are re-evaluated with the new mu before the
         // inertia of that factorisation is judged; nothing of the ladder advances in this pass
-        WTRY(hipMemcpyAsync(d_mu, h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_mu, h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
         first_pass = false;
         continue;
       }
       for (int64_t i = 0; i < B; ++i) {
         if (!h_active[(size_t)i]) continue;
-        Inst& s = I[(size_t)i];
+        WideInst& s = I[(size_t)i];
         // ---- C: inertia (Algorithm IC, ladder on the exact Hessian)
         if (h_flags[(size_t)i] || s.attempt >= o.max_refactor) {
           if (s.dw > 0.0 && s.gam != 0.0) s.dlast = s.dw;
@@ -562,22 +718,22 @@ static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch*
     }
     // ---- D: filter line search over the trial steps 2^-k
     for (int64_t i = 0; i < B; ++i) h_active[(size_t)i] = (I[(size_t)i].status == 0);
-    any_running = false;
-    for (int64_t i = 0; i < B; ++i) any_running = any_running || h_active[(size_t)i];
-    if (!any_running) break;
-    WTRY(hipMemcpyAsync(d_active, h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-    { const int lrc = launch(DTO_WIDE_MERIT); if (lrc) { cleanup(); return hip_fail((hipError_t)lrc, "wide merit"); } }
-    WTRY(hipMemcpyAsync(h_merit.data(), d_merit, h_merit.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    WTRY(hipStreamSynchronize(st));
-    if (dump_prefix && dump_merit < dump_max) {   // debug: the line-search table of this iteration
+    W.any_running = false;
+    for (int64_t i = 0; i < B; ++i) W.any_running = W.any_running || h_active[(size_t)i];
+    if (!W.any_running) return DTO_OK;
+    HIP_TRY(hipMemcpyAsync(d_active, h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+    { const int lrc = launch(DTO_WIDE_MERIT); if (lrc) return hip_fail((hipError_t)lrc, "wide merit"); }
+    HIP_TRY(hipMemcpyAsync(h_merit.data(), d_merit, h_merit.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (dump_prefix && W.dump_merit < dump_max) {   // debug: the line-search table of this iteration
       char fn[1024];
-      snprintf(fn, sizeof(fn), "%s_M%d_merit.bin", dump_prefix, dump_merit++);
+      snprintf(fn, sizeof(fn), "%s_M%d_merit.bin", dump_prefix, W.dump_merit++);
       if (FILE* f = fopen(fn, "wb")) { fwrite(h_merit.data(), sizeof(double), h_merit.size(), f); fclose(f); }
     }
     for (int64_t i = 0; i < B; ++i) {
       h_alpha[(size_t)i] = 0.0;
       if (!h_active[(size_t)i]) continue;
-      Inst& s = I[(size_t)i];
+      WideInst& s = I[(size_t)i];
       const double* sv = &h_stats[(size_t)i * DTO_WIDE_NSTAT];
       const double* mv = &h_merit[(size_t)i * 2 * DTO_WIDE_TRIALS];
       // with finite bounds: phi = f - mu sum log(gaps) (the merit kernel adds the same terms at the trial points), trial steps
@@ -629,10 +785,10 @@ static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch*
       h_alpha[(size_t)i] = chosen;
     }
     // ---- E: take the steps (bound multipliers first: their update reads the old point)
-    WTRY(hipMemcpyAsync(d_alpha, h_alpha.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_alpha, h_alpha.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
     if (barrier) {
       for (int64_t i = 0; i < B; ++i) if (h_alpha[(size_t)i] == 0.0) h_alphad[(size_t)i] = 0.0;
-      WTRY(hipMemcpyAsync(d_alphad, h_alphad.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_alphad, h_alphad.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_wide_update_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (const double*)z, (const double*)dz,
                          d_zl, d_zu, (const double*)d_lo, (const double*)d_hi, (const double*)d_alpha, (const double*)d_alphad,
                          (const double*)d_mu, Nz);
@@ -640,18 +796,108 @@ static int wide_solve_batch(Problem* p, const dto_options* opt, const dto_batch*
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)d_alpha, Nz, Nz, Nz);
     if (Nc > 0)
       hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, lam, (const double*)dlam, (const double*)d_alpha, Nc, Nc, Nc);
-    if (u.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > u.max_cpu_time) { timed_out = true; break; }
+    if (W.user.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - W.t_start).count() > W.user.max_cpu_time)
+      W.timed_out = true;
   }
-  WTRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), z, Nz * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st));
-  if (mu_out && Nc > 0)
-    WTRY(hipMemcpy2DAsync(mu_out, ldmuo * sizeof(double), lam, Nc * sizeof(double), Nc * sizeof(double), B, hipMemcpyDeviceToDevice, st));
-  WTRY(hipStreamSynchronize(st));
-#undef WTRY
-  for (int64_t i = 0; i < B; ++i) {
-    if (status) status[i] = (I[(size_t)i].status == 0 && timed_out) ? DTO_STATUS_CPU_TIME : I[(size_t)i].status;
-    if (iterations) iterations[i] = I[(size_t)i].iter;
+  return DTO_OK;
+}
+
+// n outer iterations of the running instances (fewer when every instance has terminated or max_cpu_time has expired)
+static int wide_iterate(Problem* p, int64_t n, hipStream_t st) {
+  WideState& W = *p->wide;
+  for (int64_t k = 0; k < n && W.any_running && !W.timed_out; ++k) {
+    const int rc = wide_outer(p, st);
+    if (rc) { W.begun = false; return rc; }
   }
-  cleanup();
+  return DTO_OK;
+}
+
+static int wide_end(Problem* p, double* x_out, int64_t ldxo, double* mu_out, int64_t ldmuo, hipStream_t st) {
+  WideState& W = *p->wide;
+  const Layout& L = p->L;
+  if (x_out) {
+    if (ldxo < L.Nz) return set_error(DTO_ERR_INVALID, "ldxo < num_variables");
+    HIP_TRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), W.z, L.Nz * sizeof(double), L.Nz * sizeof(double), W.B, hipMemcpyDeviceToDevice, st));
+  }
+  if (mu_out && L.Nc > 0) {
+    if (ldmuo < L.Nc) return set_error(DTO_ERR_INVALID, "ldmuo < num_constraint");
+    HIP_TRY(hipMemcpy2DAsync(mu_out, ldmuo * sizeof(double), W.lam, L.Nc * sizeof(double), L.Nc * sizeof(double), W.B, hipMemcpyDeviceToDevice, st));
+  }
+  return DTO_OK;
+}
+
+static int wide_run(Problem* p, double* x_out, int64_t ldxo, double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations,
+                    hipStream_t st) {
+  WideState& W = *p->wide;
+  int rc = wide_iterate(p, INT64_MAX, st);
+  if (rc) return rc;
+  if ((rc = wide_end(p, x_out, ldxo, mu_out, ldmuo, st))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < W.B; ++i) {
+    // Options.max_cpu_time expired: the running instances come back with DTO_STATUS_CPU_TIME
+    if (status) status[i] = (W.I[(size_t)i].status == 0 && W.timed_out) ? DTO_STATUS_CPU_TIME : W.I[(size_t)i].status;
+    if (iterations) iterations[i] = W.I[(size_t)i].iter;
+  }
+  return DTO_OK;
+}
+
+// per-instance scalar of the tile path; false for slots the host loop does not keep
+static bool wide_scalar(const WideInst& s, int slot, double* v) {
+  switch (slot) {
+    case SC_STATUS: *v = s.status; return true;
+    case SC_ITER: *v = s.iter; return true;
+    case SC_MU: *v = s.mu; return true;
+    case SC_DELTA_W: *v = s.dw; return true;
+    case SC_ALPHA: *v = s.alpha; return true;
+    case SC_F: *v = s.f; return true;
+    case SC_THETA_INF: *v = s.thinf; return true;
+    case SC_DINF: *v = s.dinf; return true;
+    case SC_LS_FAIL: *v = s.ls_fail; return true;
+    case SC_DELTA_LAST: *v = s.dlast; return true;
+    case SC_THETA_MAX: *v = s.theta_max; return true;
+    case SC_THETA_MIN: *v = s.theta_min; return true;
+    case SC_FILTER_N: *v = s.filter_n; return true;
+    case SC_FULL_STREAK: *v = s.full_streak; return true;
+    case SC_ACC_COUNT: *v = s.acc_count; return true;
+    case SC_F_LAST: *v = s.f_last; return true;
+    default: return false;
+  }
+}
+
+// receding horizon: z, the dynamics multipliers and z_L / z_U moved forward by `knots` knots (k_wide_shift_knots into the spare
+// buffer, then the two are swapped); rows marked by dto_solver_shift_keep_rows keep their multipliers
+static int wide_shift(Problem* p, int knots, hipStream_t st) {
+  if (!p->wide || !p->wide->z || p->wide->I.empty())
+    return set_error(DTO_ERR_INVALID, "dto_solver_shift needs the device state of a previous solve");
+  if (knots == 0) return DTO_OK;
+  WideState& W = *p->wide;
+  const Layout& L = p->L;
+  const int T = L.T;
+  if (knots >= T - 1) return set_error(DTO_ERR_INVALID, "shift by fewer knots than the horizon has");
+  for (int t = 1; t < T; ++t)
+    if (L.nx[t] != L.nx[0] || (t < T - 1 && L.nu[t] != L.nu[0]))
+      return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_shift needs the same state / action dimensions at every knot");
+  const int nx = L.nx[0], nu = L.nu[0];
+  if (L.Ndyn != (int64_t)(T - 1) * nx || L.Nc != L.Ndyn || L.Nz != (int64_t)(T - 1) * (nx + nu) + nx)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_shift: unexpected variable / dynamics row count");
+  auto shift = [&](double*& buf, int64_t n, int stride, int last_len, const int* keep) -> int {
+    const int64_t total = W.B * n;
+    if (total == 0) return DTO_OK;
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffff) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_shift: batch too large");
+    hipLaunchKernelGGL(k_wide_shift_knots, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)buf, W.tmp, n, total, stride,
+                       T - 1, last_len, knots, keep);
+    HIP_TRY(hipGetLastError());
+    std::swap(buf, W.tmp);   // every buffer holds B x len doubles
+    return DTO_OK;
+  };
+  int rc;
+  if ((rc = shift(W.z, L.Nz, nx + nu, nx, nullptr))) return rc;
+  if ((rc = shift(W.lam, L.Nc, nx, 0, p->d_shift_keep))) return rc;
+  if (W.zl) {
+    if ((rc = shift(W.zl, L.Nz, nx + nu, nx, nullptr))) return rc;
+    if ((rc = shift(W.zu, L.Nz, nx + nu, nx, nullptr))) return rc;
+  }
   return DTO_OK;
 }
 
@@ -2362,6 +2608,7 @@ int dto_solver_begin(dto_problem* h, const dto_options* opt, const dto_batch* b)
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || !b || !b->x) return set_error(DTO_ERR_INVALID, "null argument");
   if (b->ldx < p->L.Nz) return set_error(DTO_ERR_INVALID, "ldx < num_variables");
+  if (p->vt->launch_wide) return dto::wide_begin(p, opt, b, false, 0.0);   // tile path: cold start, as dto_solve_batch
   int rc = p->ensure_device();
   if (rc) return rc;
   // no batch is begun until this call has succeeded: a failed set-up must not leave the previous batch (of either engine)
@@ -2444,6 +2691,10 @@ int dto_solver_begin(dto_problem* h, const dto_options* opt, const dto_batch* b)
 int dto_solver_iterate(dto_problem* h, int n, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (p && p->im_active && p->im && p->im->begun) return dto::im_iterate(p, n, (hipStream_t)stream);
+  if (p && p->vt->launch_wide) {
+    if (!p->wide || !p->wide->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin has not been called");
+    return dto::wide_iterate(p, std::max(0, n), (hipStream_t)stream);
+  }
   if (!p || !p->solver || !p->solver->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin has not been called");
   hipStream_t st = (hipStream_t)stream;
   dto_kkt_args a;
@@ -2563,6 +2814,7 @@ int dto_solver_hessian_mode(dto_problem* h, int* mode) {
 int dto_solver_trace(dto_problem* h, int on) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  if (p->vt->launch_wide) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_trace: the tile path has no launch trace");
   if (!p->trace) p->trace = new dto::LaunchTrace();
   if (on) p->trace->clear();
   p->trace->on = on != 0;
@@ -2614,6 +2866,22 @@ int dto_solver_stats(dto_problem* h, int32_t* status, int32_t* iterations, doubl
     }
     return DTO_OK;
   }
+  if (p && p->vt->launch_wide) {
+    if (!p->wide || p->wide->I.empty()) return set_error(DTO_ERR_INVALID, "no solver state");
+    const dto::WideState& W = *p->wide;
+    for (int64_t i = 0; i < W.B; ++i) {
+      const dto::WideInst& s = W.I[(size_t)i];
+      if (status) status[i] = s.status;
+      if (iterations) iterations[i] = s.iter;
+      if (objective) objective[i] = s.f;
+      if (constr_viol) constr_viol[i] = s.thinf;
+      if (dual_inf) dual_inf[i] = s.dinf;
+      if (mu) mu[i] = s.mu;
+      if (delta_w) delta_w[i] = s.dw;
+      if (alpha) alpha[i] = s.alpha;
+    }
+    return DTO_OK;
+  }
   if (!p || !p->solver || !p->solver->z) return set_error(DTO_ERR_INVALID, "no solver state");
   SolverState& S = *p->solver;
   HIP_TRY(hipDeviceSynchronize());
@@ -2647,6 +2915,7 @@ int dto_solver_launch_op(dto_problem* h, int op, void* stream) {
     HIP_TRY(hipMemsetAsync(I.ctr + 3, 0, 2 * sizeof(int), (hipStream_t)stream));
     return dto::im_launch(p, iop, a, (hipStream_t)stream);
   }
+  if (p && p->vt->launch_wide) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_launch_op: the tile path has no per-kernel iteration ops");
   if (!p || !p->solver || !p->solver->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin has not been called");
   if (op < DTO_KKT_EVAL || op >= DTO_KKT_OP_COUNT) return set_error(DTO_ERR_INVALID, "op out of range");
   dto_kkt_args a;
@@ -2679,6 +2948,7 @@ int dto_solver_launch_op(dto_problem* h, int op, void* stream) {
 int dto_solver_set_partitions(dto_problem* h, int partitions) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || partitions < 0 || partitions > 64) return set_error(DTO_ERR_INVALID, "partitions must be in [0, 64]");
+  if (p->vt->launch_wide) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_set_partitions: the tile path factorises every instance in one workgroup");
   if (partitions > p->L.T) return set_error(DTO_ERR_INVALID, "more partitions than stages");
   if (!p->solver) p->solver = new SolverState();
   p->solver->forced_P = partitions;
@@ -2711,6 +2981,7 @@ static __global__ void k_shift_knots(const double* in, double* out, int64_t ld, 
 int dto_solver_shift(dto_problem* h, int knots, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || knots < 0) return set_error(DTO_ERR_INVALID, "bad arguments");
+  if (p->vt->launch_wide) return dto::wide_shift(p, knots, (hipStream_t)stream);
   if (p->im_active) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_shift: SoA engine only");
   if (!p->solver || !p->solver->z) return set_error(DTO_ERR_INVALID, "dto_solver_shift needs the device state of a previous solve");
   if (knots == 0) return DTO_OK;
@@ -2755,6 +3026,23 @@ int dto_solver_shift(dto_problem* h, int knots, void* stream) {
   return DTO_OK;
 }
 
+int dto_solver_shift_keep_rows(dto_problem* h, const int32_t* keep, int64_t n) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  if (!keep) {
+    if (p->d_shift_keep) (void)hipFree(p->d_shift_keep);
+    p->d_shift_keep = nullptr;
+    return DTO_OK;
+  }
+  if (n != p->L.Nc) return set_error(DTO_ERR_INVALID, "dto_solver_shift_keep_rows: one flag per constraint row");
+  if (n == 0) return DTO_OK;
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  if (!p->d_shift_keep) HIP_TRY(hipMalloc((void**)&p->d_shift_keep, (size_t)n * sizeof(int)));
+  HIP_TRY(hipMemcpy(p->d_shift_keep, keep, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  return DTO_OK;
+}
+
 int dto_solver_release(dto_problem* h) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p) return set_error(DTO_ERR_INVALID, "null argument");
@@ -2771,6 +3059,7 @@ int dto_solver_release(dto_problem* h) {
 int dto_solver_set_engine(dto_problem* h, int engine) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || engine < 0 || engine > 2) return set_error(DTO_ERR_INVALID, "engine must be 0 (automatic), 1 (SoA tiles) or 2 (instance-major)");
+  if (p->vt->launch_wide) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_set_engine: the tile path has one engine");
   if (engine == 2 && !dto::im_supported(p))
     return set_error(DTO_ERR_UNSUPPORTED, "the instance-major engine needs an exact-Hessian register-path model without GeneralConstraint");
   p->engine_req = engine;
@@ -2807,6 +3096,7 @@ int dto_solver_footprint(dto_problem* h, int64_t* rec, int64_t* fac, int64_t* ni
     if (rounds) *rounds = 1;
     return DTO_OK;
   }
+  if (p && p->vt->launch_wide) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_footprint: the tile path keeps no stage records");
   if (!p || !p->solver || !p->solver->z) return set_error(DTO_ERR_INVALID, "no solver state");
   if (rec) *rec = p->solver->rec_total;
   if (fac) *fac = p->solver->fac_total;
@@ -2829,6 +3119,16 @@ int dto_solver_scalar(dto_problem* h, int slot, double* out) {
     int rc = dto::im_fetch_scalars(p, p->stream);
     if (rc) return rc;
     for (int64_t i = 0; i < I.B; ++i) out[i] = dto::im_hscal(I, i, slot);
+    return DTO_OK;
+  }
+  if (p && out && p->vt->launch_wide) {
+    if (!p->wide || p->wide->I.empty()) return set_error(DTO_ERR_INVALID, "no solver state");
+    if (slot < 0 || slot >= SC_COUNT) return set_error(DTO_ERR_INVALID, "slot out of range");
+    const dto::WideState& W = *p->wide;
+    for (int64_t i = 0; i < W.B; ++i)
+      if (!dto::wide_scalar(W.I[(size_t)i], slot, &out[i]))
+        return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_scalar: the tile path keeps status, iter, mu, delta_w, alpha, f, theta_inf, dinf, "
+                                              "ls_fail, delta_last, theta_max, theta_min, filter_n, full_streak, acc_count and f_last");
     return DTO_OK;
   }
   if (!p || !p->solver || !p->solver->z || !out) return set_error(DTO_ERR_INVALID, "no solver state");
@@ -2855,6 +3155,23 @@ int dto_solver_peek(dto_problem* h, int which, double* out, int64_t ld, void* st
       return DTO_OK;
     }
     return dto::im_unpack(p, which, out, ld, (hipStream_t)stream);
+  }
+  if (p && out && p->vt->launch_wide) {
+    if (!p->wide || p->wide->I.empty()) return set_error(DTO_ERR_INVALID, "no solver state");
+    if (which < 0 || which > 9 || which == 4) return set_error(DTO_ERR_INVALID, "unknown vector");
+    if (which > 6) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_peek: the tile path has no slacks (which = 0, 1, 2, 3, 5, 6)");
+    const dto::WideState& W = *p->wide;
+    const int64_t n = (which == 0 || which == 2 || which == 5 || which == 6) ? p->L.Nz : p->L.Nc;
+    if (ld < n) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+    if (n == 0) return DTO_OK;
+    const double* src = which == 0 ? W.z : which == 1 ? W.lam : which == 2 ? W.dz : which == 3 ? W.dlam : which == 5 ? W.zl : W.zu;
+    if (!src) {   // no finite variable bounds: the bound multipliers are identically zero
+      HIP_TRY(hipMemset2DAsync(out, (size_t)ld * sizeof(double), 0, (size_t)n * sizeof(double), (size_t)W.B, (hipStream_t)stream));
+      return DTO_OK;
+    }
+    HIP_TRY(hipMemcpy2DAsync(out, ld * sizeof(double), src, n * sizeof(double), n * sizeof(double), W.B, hipMemcpyDeviceToDevice,
+                             (hipStream_t)stream));
+    return DTO_OK;
   }
   if (!p || !p->solver || !p->solver->z || !out) return set_error(DTO_ERR_INVALID, "no solver state");
   if (which < 0 || which > 9 || which == 4) return set_error(DTO_ERR_INVALID, "unknown vector");
@@ -2885,6 +3202,10 @@ int dto_solver_end(dto_problem* h, double* x_out, int64_t ldxo, double* mu_out, 
     }
     return DTO_OK;
   }
+  if (p && p->vt->launch_wide) {
+    if (!p->wide || p->wide->I.empty()) return set_error(DTO_ERR_INVALID, "no solver state");
+    return dto::wide_end(p, x_out, ldxo, mu_out, ldmuo, (hipStream_t)stream);
+  }
   if (!p || !p->solver || !p->solver->z) return set_error(DTO_ERR_INVALID, "no solver state");
   hipStream_t st = (hipStream_t)stream;
   dto_kkt_args a;
@@ -2905,6 +3226,10 @@ int dto_solver_run(dto_problem* h, double* x_out, int64_t ldxo, double* mu_out, 
                    int32_t* iterations, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (p && p->im_active && p->im && p->im->begun) return dto::im_run(p, x_out, ldxo, mu_out, ldmuo, status, iterations, (hipStream_t)stream);
+  if (p && p->vt->launch_wide) {
+    if (!p->wide || !p->wide->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin[_warm] has not been called");
+    return dto::wide_run(p, x_out, ldxo, mu_out, ldmuo, status, iterations, (hipStream_t)stream);
+  }
   if (!p || !p->solver || !p->solver->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin[_warm] has not been called");
   SolverState& S = *p->solver;
   hipStream_t st = (hipStream_t)stream;
@@ -2944,6 +3269,14 @@ int dto_solver_repack(dto_problem* h, int* num_running, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
   // instance-major engine: nothing to move (work lists are rebuilt every pass); only the count is reported
   if (p && p->im_active && p->im && p->im->begun) return dto::im_count(p, (hipStream_t)stream, -1, num_running, nullptr);
+  if (p && p->vt->launch_wide) {
+    // tile path: nothing to move (the host loop skips finished instances); only the count is reported
+    if (!p->wide || !p->wide->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin[_warm] has not been called");
+    int n = 0;
+    for (const dto::WideInst& s : p->wide->I) n += s.status == 0 && !p->wide->timed_out;
+    if (num_running) *num_running = n;
+    return DTO_OK;
+  }
   if (!p || !p->solver || !p->solver->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin[_warm] has not been called");
   int rc = dto::fetch_scalars(p, (hipStream_t)stream);
   if (rc) return rc;
@@ -2956,8 +3289,10 @@ int dto_solve_batch(dto_problem* h, const dto_options* opt, const dto_batch* b, 
   // (the tile and the bordered paths have no limited-memory mode: they run the exact second derivatives of the traced
   //  expressions whatever dto_options.hessian_approximation asks for, and dto_solver_hessian_mode reports it -- ADVICE r5)
   if (p && b && b->x && x_out && p->vt->launch_wide) {
-    p->hessian_mode_last = DTO_HESSIAN_EXACT;
-    return dto::wide_solve_batch(p, opt, b, x_out, ldxo, mu_out, ldmuo, status, iterations);
+    // tile path: begin + run on the state of the handle, which stays allocated for dto_solver_begin_warm / dto_solver_shift
+    int rc = dto::wide_begin(p, opt, b, false, 0.0);
+    if (rc) return rc;
+    return dto::wide_run(p, x_out, ldxo, mu_out, ldmuo, status, iterations, (hipStream_t)b->stream);
   }
   if (p && b && b->x && x_out && p->L.Ngen > 0) {
     p->hessian_mode_last = DTO_HESSIAN_EXACT;
@@ -2971,7 +3306,7 @@ int dto_solve_batch(dto_problem* h, const dto_options* opt, const dto_batch* b, 
 int dto_solver_begin_warm(dto_problem* h, const dto_options* opt, const dto_batch* b, double mu0) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || !b) return set_error(DTO_ERR_INVALID, "null argument");
-  if (p->vt->launch_wide) return set_error(DTO_ERR_UNSUPPORTED, "warm starts are not available for wide-stage models");
+  if (p->vt->launch_wide) return dto::wide_begin(p, opt, b, true, mu0);
   if (p->im_active && p->im && p->im->A) {
     if (p->im->B != b->B) return set_error(DTO_ERR_INVALID, "dto_solver_begin_warm needs the device state of a previous solve of the same batch size");
     if (b->x && b->ldx < p->L.Nz) return set_error(DTO_ERR_INVALID, "ldx < num_variables");

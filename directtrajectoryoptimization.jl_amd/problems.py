@@ -545,3 +545,27 @@ def build_mpc_pendulum(T=30, x1=(0.0, 0.0), goal=PI):
                 constraints=[con1] + [Constraint() for _ in range(T - 2)] + [conT],
                 bounds=[Bound(n, m)] * (T - 1) + [Bound(n, 0)], parameters=[w.copy() for _ in range(T)],
                 T=T, n=n, m=m, nw=nw, evaluate_hessian=True)
+
+
+def build_mpc_acrobot_padded(T=30, n=24, x1=None, target=PI, u_max=None):
+    """Receding-horizon (MPC) instance family on the tile path, modelled on build_mpc_pendulum: the acrobot embedded in n states
+    (acrobot_padded_midpoint, 17 <= n <= 32) whose initial state is a PARAMETER, w_t = x1 (n values at every knot), pinned by the
+    first-knot rows x - w[0:n].  Those rows ride n auxiliary states of the 64-state embedding (solver.py: pad_to_wide; n + n <= 64),
+    so an instance of a batch takes its measured state through dto_batch.params.  The four physical states of the last knot are
+    fixed at (target, 0, 0, 0) by equal bounds (rows of the last knot may not read parameters); u_max: action bounds."""
+    m, nw = 1, n
+    x1 = np.zeros(n) if x1 is None else np.asarray(x1, dtype=float)
+    xT = np.zeros(n)
+    xT[0] = target
+    dt = Dynamics(acrobot_padded_midpoint(n, m=m), n, n, m, num_parameter=nw, evaluate_hessian=True)
+    ct = Cost(lambda x, u, w: 0.1 * dot(x[2:n], x[2:n]) + padded_action_cost(x, u), n, m, num_parameter=nw, evaluate_hessian=True)
+    cT = Cost(lambda x, u, w: 0.1 * dot(x[2:n], x[2:n]), n, 0, num_parameter=nw, evaluate_hessian=True)
+    con1 = Constraint(lambda x, u, w: x - w[0:n], n, m, num_parameter=nw, evaluate_hessian=True)
+    ub = {} if u_max is None else dict(action_lower=-u_max * np.ones(m), action_upper=u_max * np.ones(m))
+    lo, hi = np.full(n, -np.inf), np.full(n, np.inf)
+    lo[:4] = hi[:4] = xT[:4]
+    return dict(dynamics=[dt] * (T - 1), objective=[ct] * (T - 1) + [cT],
+                constraints=[con1] + [Constraint() for _ in range(T - 1)],
+                bounds=[Bound(n, m, **ub) for _ in range(T - 1)] + [Bound(n, 0, state_lower=lo, state_upper=hi)],
+                parameters=[x1.copy() for _ in range(T)], x1=x1, xT=xT, T=T, n=n, m=m, nw=nw, evaluate_hessian=True,
+                guess=lambda rng: (linear_interpolation(x1, xT, T), [0.1 * rng.standard_normal(m) for _ in range(T - 1)]))

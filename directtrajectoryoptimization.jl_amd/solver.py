@@ -460,6 +460,7 @@ class Solver:
         n_max = max(d.num_state for d in s_dyn)
         wide_embedded = False
         self._pins = None
+        self._stage_rows = None   # solver rows that carry stage constraints of the embedding (their multipliers stay in shift_batch)
         if gen is None and s_eh:
             padded = pad_to_wide(s_dyn, s_obj, s_con, s_bounds, s_eh)
             if padded is None and _WMIN <= n_max < _WST and any(c.num_constraint for c in s_con):
@@ -485,6 +486,7 @@ class Solver:
                         padded = padded[:5] + (full_m, full_s)
             if padded is not None:
                 s_dyn, s_obj, s_con, s_bounds, zmap, mumap, musign = padded
+                self._stage_rows = np.asarray(mumap)[np.asarray(musign) < 0]
                 if self._pad is not None:
                     za, ma, sa = self._pad
                     zmap, mumap, musign = zmap[za], mumap[ma], musign[ma] * sa
@@ -653,8 +655,16 @@ class Solver:
         self._B = B
 
     def shift_batch(self, knots: int = 1, stream=0):
-        """dto_solver_shift: move the device-resident iterate `knots` knots forward (receding-horizon warm start)."""
-        capi.check(self._solve_nlp._lib.dto_solver_shift(self._solve_nlp._h, int(knots), stream or None))
+        """dto_solver_shift: move the device-resident iterate `knots` knots forward (receding-horizon warm start).  A problem
+        embedded in the 64 states of the tile kernels carries its stage rows as dynamics rows of the embedding: they are marked
+        (dto_solver_shift_keep_rows) so that their multipliers stay with their knots, as stage-row multipliers do on the
+        lane-per-instance path."""
+        n = self._solve_nlp
+        if self._stage_rows is not None and len(self._stage_rows):
+            keep = np.zeros(max(1, n.num_constraint), dtype=np.int32)
+            keep[self._stage_rows] = 1
+            capi.check(n._lib.dto_solver_shift_keep_rows(n._h, keep.ctypes.data_as(capi.c_int32_p), n.num_constraint))
+        capi.check(n._lib.dto_solver_shift(n._h, int(knots), stream or None))
 
     def repack_batch(self, stream=0) -> int:
         """dto_solver_repack: close the gaps finished instances leave in the tiles; returns the number still running."""

@@ -251,7 +251,8 @@ int dto_kkt_solve(dto_problem* p, const double* rhs_x, int64_t ldrx, const doubl
  * status/iterations: HOST [B] (0 running, 6 cut off by max_cpu_time, 1 converged, 2 max_iter, 3 failed: non-finite iterate,
  * 4 converged to the acceptable level, 5 diverging iterates).
  * Paths by model: lane-per-instance tiles (states <= 16; bounds, inequality rows, per-instance parameters); the tile (MFMA)
- * kernels for 64-state models (variables free, fixed or bounded; no stage constraints, one to four actions, shared or per-instance parameters); a
+ * kernels for 64-state models (variables free, fixed or bounded; no stage constraints, one to four actions, shared or per-instance parameters;
+ * 17..63-state models through their 64-state embedding; stepwise, warm-started and shifted solves through the entry points below); a
  * GeneralConstraint whose rows couple several knots is solved through a border (general rows equalities or inequalities,
  * dynamics / stage rows equalities, variables free or fixed):
  * one factorisation and n_g + 1 sweeps per step, the border algebra on the device since round 4 (DTO_BORDER_HOST=1: on the
@@ -259,20 +260,35 @@ int dto_kkt_solve(dto_problem* p, const double* rhs_x, int64_t ldrx, const doubl
 int dto_solve_batch(dto_problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                     double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 
-/* The same solve split in three so a caller (bench.py) can time exactly K iterations. */
+/* The same solve split in three so a caller (bench.py) can time exactly K iterations.  On the tile path (64-state models and the
+ * 17..63-state embedding) the state of these entry points is the host-driven loop's: begin = the cold start of dto_solve_batch
+ * (which is itself begin + run there, bit for bit), iterate(n) = n outer iterations of the instances still running, resumable;
+ * the state stays allocated after the solve until dto_solver_release or a begin with another batch size; max_cpu_time counts
+ * from the begin.  There dto_solver_peek has which = 0, 1, 2, 3, 5, 6, dto_solver_scalar the slots the host loop keeps
+ * (status, iter, mu, delta_w, alpha, f, theta_inf, dinf and the filter / ladder counters), dto_solver_repack only counts, and
+ * dto_solver_launch_op, _trace, _set_partitions, _footprint and _set_engine return DTO_ERR_UNSUPPORTED. */
 int dto_solver_begin(dto_problem* p, const dto_options* opt, const dto_batch* b);
 /* Warm start for receding-horizon (MPC) re-solves -- what repeated initialize_states!/initialize_controls! + solve! calls
  * (src/solver.jl:23-47) amount to, without re-initialising the interior-point state: the multipliers, bound multipliers, slacks
  * and the barrier parameter of the previous solve of this handle stay on the device.  b->x (DEVICE, may be NULL = keep the
  * final iterate) replaces the primal iterate (e.g. the shifted trajectory), b->params the parameters (e.g. the newly
- * measured state); b->B must equal the previous batch size.  mu0 > 0 resets the barrier parameter, mu0 <= 0 keeps it. */
+ * measured state); b->B must equal the previous batch size.  mu0 > 0 resets the barrier parameter, mu0 <= 0 keeps it.
+ * Variables with lo == hi go to their bound, the others are pushed into the interior as at a cold start; positive bound
+ * multipliers are kept, non-positive ones re-initialised to mu / gap; the filter, the inertia-ladder memory and the iteration
+ * counters restart.  Both paths, the tile path included (there: the k_wide_init_warm kernel, per-instance host records reset). */
 int dto_solver_begin_warm(dto_problem* p, const dto_options* opt, const dto_batch* b, double mu0);
 /* Receding horizon: shift the device-resident iterate of the previous solve forward by `knots` knots -- x_t <- x_{t+k},
  * u_t <- u_{t+k}, dynamics multipliers and bound multipliers with them; the knots that enter at the end of the horizon hold the
  * final state and repeat the last action (the usual MPC warm start).  Stage-constraint multipliers stay with their knots.
  * Follow with dto_solver_begin_warm(x = NULL, params = the newly measured state) and dto_solver_run.  Needs the same state /
- * action dimensions at every knot. */
+ * action dimensions at every knot and knots < horizon - 1.  Tile path: one launch per array (z, multipliers, z_L, z_U), no host
+ * round trip; the rows marked by dto_solver_shift_keep_rows keep their multipliers. */
 int dto_solver_shift(dto_problem* p, int knots, void* stream);
+/* Tile path: keep[i] != 0 (HOST [n], n = num_constraint) marks constraint row i as one whose multiplier stays with its knot in
+ * dto_solver_shift -- the stage rows that a 17..63-state problem carries as dynamics rows of its 64-state embedding (the Python
+ * Solver sets them from its embedding before every shift).  keep = NULL clears the marks.  The lane-per-instance path keeps its
+ * stage rows by itself and ignores the marks. */
+int dto_solver_shift_keep_rows(dto_problem* p, const int32_t* keep, int64_t n);
 /* Move the instances that are still running to the leading tiles of the batch so that the following iterations only cover
  * tiles with work (a batch otherwise pays for every tile until its last lane has terminated); results keep coming back in
  * the caller's instance order.  dto_solver_run / dto_solve_batch do this by themselves; a caller that drives
