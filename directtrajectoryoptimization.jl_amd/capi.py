@@ -147,6 +147,7 @@ def lib() -> C.CDLL:
         "dto_solver_release": [vp],
         "dto_solver_shift": [vp, C.c_int, vp],
         "dto_solver_shift_keep_rows": [vp, c_int32_p, C.c_int64],
+        "dto_solver_set_bounds": [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp],
         "dto_solve": [vp, C.POINTER(COptions), c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p],
         "dto_device_alloc": [C.POINTER(vp), C.c_int64],
         "dto_device_free": [vp],

@@ -13,7 +13,7 @@
 
 #include <stdint.h>
 
-#define DTO_PLUGIN_ABI 5
+#define DTO_PLUGIN_ABI 6
 
 #ifdef __cplusplus
 extern "C" {

@@ -61,6 +61,8 @@ struct Problem {
   ImState* im = nullptr;
   WideState* wide = nullptr;   // tile path: iterate, multipliers and host records of the batch begun last
   int* d_shift_keep = nullptr; // dto_solver_shift_keep_rows: [Nc] 1 = the multiplier of this row stays with its knot (NULL: none)
+  double* d_bnd = nullptr;     // dto_solver_set_bounds (tile path): per-instance bounds [2][bnd_B][Nz], lower then upper (NULL: shared)
+  int64_t bnd_B = 0;
   LaunchTrace* trace = nullptr;   // dto_solver_trace
   int hessian_mode_last = -1;     // dto_solver_hessian_mode: what the last solve / begun batch used
   int engine_req = 0;      // dto_solver_set_engine: 0 automatic, 1 SoA tiles, 2 instance-major

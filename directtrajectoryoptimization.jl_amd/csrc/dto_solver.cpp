@@ -263,7 +263,7 @@ static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t l
   a.delta_w = delta_w; a.delta_c = delta_c; a.piv_tol = 1e-9;
   a.dz = dx; a.lddz = lddx; a.dmu = dmu; a.lddmu = lddmu;
   a.fac = p->wide_fac; a.flags = p->wide_flags; a.Nc = L.Nc;
-  a.fixed_lo = a.fixed_hi = nullptr; a.dw_inst = nullptr; a.gam_inst = nullptr; a.active = nullptr; a.stats = nullptr; a.merit = nullptr;
+  a.fixed_lo = a.fixed_hi = nullptr; a.ldb = 0; a.dw_inst = nullptr; a.gam_inst = nullptr; a.active = nullptr; a.stats = nullptr; a.merit = nullptr;
   a.zl = a.zu = nullptr; a.mu_inst = nullptr; a.tau_min = 0.99;
   a.prof = nullptr;
   if (const char* e = getenv("DTO_WIDE_PROF")) a.prof = (long long*)(uintptr_t)strtoull(e, nullptr, 0);  // debug: device pointer
@@ -293,14 +293,15 @@ static __global__ void k_rows_axpy(double* y, const double* x, const double* alp
 }
 
 // ---- finite variable bounds on the wide path (round 4): the barrier bookkeeping around k_wide_step, instance-major ----------
+// (lo / hi of instance b at lo[b * ldb]: ldb = 0 for the problem's shared bounds, Nz for those of dto_solver_set_bounds)
 // push the guess into the bounds and put the bound multipliers on the central path of mu (Waechter & Biegler 2006, section 3.6;
 // the same rule as k_init of the lane-per-instance path)
-static __global__ void k_wide_init_bounds(double* z, double* zl, double* zu, const double* lo, const double* hi, double mu,
+static __global__ void k_wide_init_bounds(double* z, double* zl, double* zu, const double* lo, const double* hi, int64_t ldb, double mu,
                                           double bound_push, double bound_frac, int64_t n) {
   const int64_t b = blockIdx.x / AXPY_BLOCKS_PER_ROW, blk = blockIdx.x % AXPY_BLOCKS_PER_ROW;
   for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x) {
     double v = z[b * n + i], l = 0.0, u = 0.0;
-    const double a = lo[i], c = hi[i];
+    const double a = lo[b * ldb + i], c = hi[b * ldb + i];
     if (a == c) v = a;
     else {
       const bool fl = a > -1e300, fh = c < 1e300;
@@ -319,13 +320,13 @@ static __global__ void k_wide_init_bounds(double* z, double* zl, double* zu, con
 // bound multipliers after a step: z_L + alpha_d dz_L with dz_L = mu/(x-lo) - z_L - z_L/(x-lo) dx at the OLD point, kept within
 // [mu / (kappa gap'), kappa mu / gap'] of the NEW gap (Ipopt's kappa_Sigma = 1e10 safeguard); runs before z is updated
 static __global__ void k_wide_update_bounds(const double* z, const double* dz, double* zl, double* zu, const double* lo, const double* hi,
-                                            const double* alpha_p, const double* alpha_d, const double* mu, int64_t n) {
+                                            int64_t ldb, const double* alpha_p, const double* alpha_d, const double* mu, int64_t n) {
   const int64_t b = blockIdx.x / AXPY_BLOCKS_PER_ROW, blk = blockIdx.x % AXPY_BLOCKS_PER_ROW;
   const double ap = alpha_p[b], ad = alpha_d[b], m = mu[b];
   if (ap == 0.0 && ad == 0.0) return;
   constexpr double KSIG = 1e10;
   for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x) {
-    const double a = lo[i], c = hi[i];
+    const double a = lo[b * ldb + i], c = hi[b * ldb + i];
     if (a == c) continue;
     const double x = z[b * n + i], dx = dz[b * n + i], xn = x + ap * dx;
     if (a > -1e300) {
@@ -343,13 +344,13 @@ static __global__ void k_wide_update_bounds(const double* z, const double* dz, d
 // bound (whether or not the problem has other finite bounds), the others are pushed into the interior as at a cold start, positive
 // bound multipliers of the previous solve are kept and non-positive ones re-initialised to mu / gap with the instance's new mu.
 // zl / zu / mu are NULL when the problem has no finite bounds (no barrier).  The dynamics multipliers are not touched.
-static __global__ void k_wide_init_warm(double* z, double* zl, double* zu, const double* lo, const double* hi, const double* mu,
+static __global__ void k_wide_init_warm(double* z, double* zl, double* zu, const double* lo, const double* hi, int64_t ldb, const double* mu,
                                         double bound_push, double bound_frac, int64_t n) {
   const int64_t b = blockIdx.x / AXPY_BLOCKS_PER_ROW, blk = blockIdx.x % AXPY_BLOCKS_PER_ROW;
   const double m = mu ? mu[b] : 0.0;
   for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x) {
     double v = z[b * n + i], l = 0.0, u = 0.0;
-    const double a = lo[i], c = hi[i];
+    const double a = lo[b * ldb + i], c = hi[b * ldb + i];
     if (a == c) v = a;
     else {
       const bool fl = a > -1e300, fh = c < 1e300;
@@ -390,6 +391,23 @@ static __global__ void k_wide_shift_knots(const double* in, double* out, int64_t
   out[b * n + j] = in[b * n + src];
 }
 
+// dto_solver_set_bounds: per-instance bounds lo / hi [B][n] against the problem's own slo / shi [n] -- the same pattern (fixed where
+// the problem's are, finite lower / upper bounds where the problem's are, lo < hi elsewhere, no NaN).  out[0] counts the entries
+// that break it, out[1] is the smallest flat index among them.  One thread per entry.
+static __global__ void k_wide_check_bounds(const double* lo, const double* hi, const double* slo, const double* shi, int64_t n,
+                                           int64_t total, unsigned long long* out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t j = idx % n;
+  const double l = lo[idx], h = hi[idx], sl = slo[j], sh = shi[j];
+  const bool fixed = sl == sh;
+  const bool ok = l == l && h == h && (l == h) == fixed && isfinite(l) == isfinite(sl) && isfinite(h) == isfinite(sh) && (fixed || l < h);
+  if (!ok) {
+    atomicAdd(&out[0], 1ull);
+    atomicMin(&out[1], (unsigned long long)idx);
+  }
+}
+
 // ---- the tile-path solver state (dto_solver_begin / iterate / run / end / begin_warm / shift on a wide plugin) ----------------
 // Host record of one instance: filter ring, inertia-ladder memory, barrier parameter, and the measures of the current iterate
 struct WideInst {
@@ -403,6 +421,7 @@ struct WideInst {
 
 struct WideState {
   int64_t B = 0, len = 0, n_bnd = 0;  // len: doubles per instance of z / lam / zl / zu / tmp (max(Nz, Nc): the shift swaps them)
+  int64_t ldb = 0, lo_len = 0;        // lo / hi: [Nz] shared (ldb = 0) or [B][Nz] per instance (ldb = Nz); lo_len doubles allocated
   bool barrier = false, begun = false, any_running = false, timed_out = false;
   double *z = nullptr, *lam = nullptr, *dz = nullptr, *dlam = nullptr, *lo = nullptr, *hi = nullptr, *dw = nullptr,
          *stats = nullptr, *merit = nullptr, *alpha = nullptr, *gam = nullptr, *zl = nullptr, *zu = nullptr, *mu = nullptr,
@@ -424,7 +443,7 @@ struct WideState {
       if (q) (void)hipFree(q);
     z = lam = dz = dlam = lo = hi = dw = stats = merit = alpha = gam = zl = zu = mu = alphad = params = tmp = nullptr;
     flags = active = nullptr;
-    B = len = 0; begun = any_running = timed_out = own_params = false;
+    B = len = ldb = lo_len = 0; begun = any_running = timed_out = own_params = false;
     I.clear();
   }
 };
@@ -446,13 +465,13 @@ static int wide_alloc(Problem* p, int64_t B, bool barrier) {
 #define WALLOC(ptr, count) do { hipError_t e_ = hipMalloc((void**)&(ptr), (size_t)(count) * sizeof(*(ptr))); if (e_ != hipSuccess) return fail(e_, "hipMalloc " #ptr); } while (0)
   WALLOC(W.z, n); WALLOC(W.lam, n); WALLOC(W.tmp, n);
   WALLOC(W.dz, (size_t)B * L.Nz); WALLOC(W.dlam, (size_t)B * std::max<int64_t>(1, L.Nc));
-  WALLOC(W.lo, L.Nz); WALLOC(W.hi, L.Nz);
+  WALLOC(W.lo, L.Nz); WALLOC(W.hi, L.Nz);   // (grown to [B][Nz] by wide_begin when per-instance bounds are set)
   WALLOC(W.dw, B); WALLOC(W.stats, (size_t)B * DTO_WIDE_NSTAT); WALLOC(W.merit, (size_t)B * 2 * DTO_WIDE_TRIALS);
   WALLOC(W.alpha, B); WALLOC(W.gam, B); WALLOC(W.flags, B); WALLOC(W.active, B);
   if (barrier) { WALLOC(W.zl, n); WALLOC(W.zu, n); WALLOC(W.mu, B); WALLOC(W.alphad, B); }
   if (L.Nw > 0) WALLOC(W.params, (size_t)B * L.Nw);
 #undef WALLOC
-  W.B = B; W.len = len;
+  W.B = B; W.len = len; W.lo_len = L.Nz;
   return DTO_OK;
 }
 
@@ -466,7 +485,7 @@ static void wide_fill_args(Problem* p, dto_wide_args& a) {
   a.delta_w = 0.0; a.delta_c = W.opt.delta_c; a.piv_tol = W.opt.piv_tol;
   a.dz = W.dz; a.lddz = L.Nz; a.dmu = W.dlam; a.lddmu = L.Nc;
   a.fac = p->wide_fac; a.flags = W.flags; a.Nc = L.Nc; a.prof = nullptr;
-  a.fixed_lo = W.lo; a.fixed_hi = W.hi; a.dw_inst = W.dw; a.gam_inst = W.gam; a.active = W.active; a.stats = W.stats; a.merit = W.merit;
+  a.fixed_lo = W.lo; a.fixed_hi = W.hi; a.ldb = W.ldb; a.dw_inst = W.dw; a.gam_inst = W.gam; a.active = W.active; a.stats = W.stats; a.merit = W.merit;
   a.zl = W.zl; a.zu = W.zu; a.mu_inst = W.mu; a.tau_min = W.opt.tau_min;
 }
 
@@ -497,10 +516,17 @@ static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bo
     return set_error(DTO_ERR_INVALID, "null argument");
   }
   if (b->x && b->ldx < L.Nz) return set_error(DTO_ERR_INVALID, "ldx < num_variables");
-  // finite bounds (lo < hi, one side finite): primal-dual barrier, round 4; n_bnd = number of bound multipliers
+  if (p->d_bnd && p->bnd_B != b->B)
+    return set_error(DTO_ERR_INVALID, "dto_solver_set_bounds set bounds for " + std::to_string(p->bnd_B) + " instances, the batch has " +
+                                          std::to_string(b->B));
+  // finite bounds (lo < hi, one side finite): primal-dual barrier, round 4; n_bnd = number of bound multipliers.  Per-instance
+  // bounds (dto_solver_set_bounds) have the problem's pattern, so everything decided here holds for them too
   int64_t n_bnd = 0;
-  for (int64_t i = 0; i < L.Nz; ++i)
+  bool any_fixed = false;
+  for (int64_t i = 0; i < L.Nz; ++i) {
     if (L.var_lo[i] != L.var_hi[i]) n_bnd += (std::isfinite(L.var_lo[i]) ? 1 : 0) + (std::isfinite(L.var_hi[i]) ? 1 : 0);
+    else any_fixed = true;
+  }
   const bool barrier = n_bnd > 0;
   dto_wide_info info;
   p->vt->wide_info(&info);
@@ -520,16 +546,39 @@ static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bo
   default_opts(W.opt, W.user);
   if ((rc = wide_set_params(p, b, st))) return rc;
   const dto_solver_opts& o = W.opt;
-  if (!warm) {
+  // the bounds this batch runs with: the handle's per-instance ones (copied, so that a later dto_solver_set_bounds leaves the
+  // begun state alone) or the problem's shared ones
+  W.ldb = p->d_bnd ? Nz : 0;
+  const int64_t lo_len = p->d_bnd ? B * Nz : Nz;
+  if (W.lo_len != lo_len) {
+    (void)hipFree(W.lo); (void)hipFree(W.hi);
+    W.lo = W.hi = nullptr; W.lo_len = 0;
+    HIP_TRY(hipMalloc((void**)&W.lo, (size_t)lo_len * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&W.hi, (size_t)lo_len * sizeof(double)));
+    W.lo_len = lo_len;
+  }
+  if (p->d_bnd) {
+    HIP_TRY(hipMemcpyAsync(W.lo, p->d_bnd, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.hi, p->d_bnd + (size_t)B * Nz, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToDevice, st));
+  } else {
     HIP_TRY(hipMemcpyAsync(W.lo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(W.hi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  if (!warm) {
     HIP_TRY(hipMemcpy2DAsync(W.z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemsetAsync(W.lam, 0, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(W.dz, 0, (size_t)B * Nz * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(W.dlam, 0, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double), st));
     if (barrier) {
       hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, W.z, W.zl, W.zu, (const double*)W.lo,
-                         (const double*)W.hi, o.mu_init, o.bound_push, o.bound_frac, Nz);
+                         (const double*)W.hi, W.ldb, o.mu_init, o.bound_push, o.bound_frac, Nz);
+      HIP_TRY(hipGetLastError());
+    } else if (any_fixed) {
+      // no finite bounds besides the fixed variables: put those on their values (the guess may miss them -- a measured state
+      // pinned by bounds).  k_wide_init_warm without multipliers does exactly that: the other variables are free on both sides
+      hipLaunchKernelGGL(k_wide_init_warm, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, W.z, (double*)nullptr,
+                         (double*)nullptr, (const double*)W.lo, (const double*)W.hi, W.ldb, (const double*)nullptr, o.bound_push,
+                         o.bound_frac, Nz);
       HIP_TRY(hipGetLastError());
     }
     W.I.assign((size_t)B, WideInst());
@@ -553,7 +602,7 @@ static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bo
     }
     if (barrier) HIP_TRY(hipMemcpyAsync(W.mu, W.h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_wide_init_warm, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, W.z, W.zl, W.zu, (const double*)W.lo,
-                       (const double*)W.hi, (const double*)W.mu, o.bound_push, o.bound_frac, Nz);
+                       (const double*)W.hi, W.ldb, (const double*)W.mu, o.bound_push, o.bound_frac, Nz);
     HIP_TRY(hipGetLastError());
   }
   if (barrier && !warm) HIP_TRY(hipMemcpyAsync(W.mu, W.h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
@@ -790,7 +839,7 @@ static int wide_outer(Problem* p, hipStream_t st) {
       for (int64_t i = 0; i < B; ++i) if (h_alpha[(size_t)i] == 0.0) h_alphad[(size_t)i] = 0.0;
       HIP_TRY(hipMemcpyAsync(d_alphad, h_alphad.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_wide_update_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (const double*)z, (const double*)dz,
-                         d_zl, d_zu, (const double*)d_lo, (const double*)d_hi, (const double*)d_alpha, (const double*)d_alphad,
+                         d_zl, d_zu, (const double*)d_lo, (const double*)d_hi, W.ldb, (const double*)d_alpha, (const double*)d_alphad,
                          (const double*)d_mu, Nz);
     }
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)d_alpha, Nz, Nz, Nz);
@@ -3040,6 +3089,83 @@ int dto_solver_shift_keep_rows(dto_problem* h, const int32_t* keep, int64_t n) {
   if (rc) return rc;
   if (!p->d_shift_keep) HIP_TRY(hipMalloc((void**)&p->d_shift_keep, (size_t)n * sizeof(int)));
   HIP_TRY(hipMemcpy(p->d_shift_keep, keep, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  return DTO_OK;
+}
+
+int dto_solver_set_bounds(dto_problem* h, int64_t B, const double* lower, int64_t ldl, const double* upper, int64_t ldu,
+                          void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  if (!p->vt->launch_wide)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_set_bounds: per-instance variable bounds are a tile-path (17..64-state) feature; on "
+                                          "the lane-per-instance path per-instance values enter through parameters in stage rows");
+  if (!lower && !upper) {
+    if (p->d_bnd) (void)hipFree(p->d_bnd);
+    p->d_bnd = nullptr; p->bnd_B = 0;
+    return DTO_OK;
+  }
+  const dto::Layout& L = p->L;
+  const int64_t Nz = L.Nz;
+  if (!lower || !upper) return set_error(DTO_ERR_INVALID, "dto_solver_set_bounds: lower and upper are both NULL or both set");
+  if (B < 1 || Nz < 1) return set_error(DTO_ERR_INVALID, "dto_solver_set_bounds: B >= 1 instances of num_variables >= 1 entries");
+  if (ldl < Nz || ldu < Nz) return set_error(DTO_ERR_INVALID, "dto_solver_set_bounds: ldl / ldu < num_variables");
+  const int64_t total = B * Nz, blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffff) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_set_bounds: batch too large");
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the new bounds go to a buffer of their own: a violation leaves the previous setting in force
+  double *buf = nullptr, *shared = nullptr;
+  unsigned long long* res = nullptr;
+  auto cleanup = [&]() {
+    if (buf) (void)hipFree(buf);
+    if (shared) (void)hipFree(shared);
+    if (res) (void)hipFree(res);
+  };
+  hipError_t e = hipMalloc((void**)&buf, (size_t)2 * total * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&shared, (size_t)2 * Nz * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&res, 2 * sizeof(unsigned long long));
+  const unsigned long long init[2] = {0ull, ~0ull};
+  unsigned long long out[2] = {0ull, 0ull};
+  if (e == hipSuccess) e = hipMemcpy2DAsync(buf, Nz * sizeof(double), lower, ldl * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(buf + total, Nz * sizeof(double), upper, ldu * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(shared, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(shared + Nz, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(res, init, sizeof(init), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(dto::k_wide_check_bounds, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)buf, (const double*)(buf + total),
+                       (const double*)shared, (const double*)(shared + Nz), Nz, total, res);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, res, sizeof(out), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  double lh[2] = {0.0, 0.0};
+  if (e == hipSuccess && out[0] > 0) {
+    e = hipMemcpy(&lh[0], buf + out[1], sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&lh[1], buf + total + out[1], sizeof(double), hipMemcpyDeviceToHost);
+  }
+  if (e != hipSuccess) { cleanup(); return dto::hip_fail(e, "dto_solver_set_bounds"); }
+  (void)hipFree(shared); shared = nullptr;
+  (void)hipFree(res); res = nullptr;
+  if (out[0] > 0) {
+    const int64_t b = (int64_t)(out[1] / (unsigned long long)Nz), j = (int64_t)(out[1] % (unsigned long long)Nz);
+    const double l = lh[0], u = lh[1], sl = L.var_lo[(size_t)j], su = L.var_hi[(size_t)j];
+    const char* why = (l != l || u != u) ? "NaN"
+                      : (sl == su && l != u) ? "not fixed (lower != upper) where the problem's variable is fixed"
+                      : (sl != su && l == u) ? "fixed (lower == upper) where the problem's variable is not"
+                      : (std::isfinite(l) != std::isfinite(sl)) ? (std::isfinite(l) ? "finite lower bound where the problem's is infinite"
+                                                                                     : "infinite lower bound where the problem's is finite")
+                      : (std::isfinite(u) != std::isfinite(su)) ? (std::isfinite(u) ? "finite upper bound where the problem's is infinite"
+                                                                                     : "infinite upper bound where the problem's is finite")
+                      : "lower >= upper";
+    char msg[384];
+    snprintf(msg, sizeof(msg), "dto_solver_set_bounds: instance %lld, variable %lld: %s (lower %.17g, upper %.17g; the problem's %.17g, %.17g); "
+             "%llu entries break the problem's bound pattern", (long long)b, (long long)j, why, l, u, sl, su, out[0]);
+    cleanup();
+    return set_error(DTO_ERR_INVALID, msg);
+  }
+  if (p->d_bnd) (void)hipFree(p->d_bnd);
+  p->d_bnd = buf; p->bnd_B = B;
   return DTO_OK;
 }
 

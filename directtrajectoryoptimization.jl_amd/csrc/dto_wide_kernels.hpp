@@ -50,7 +50,8 @@ struct dto_wide_args {
   int64_t Nc;
   long long* prof;  // optional [32] cycle counters of workgroup 0 (tools/wide_profile.py), else NULL
   // ---- solver use (dto_solve_batch on wide models); all NULL / 0 for the plain dto_kkt_step_batch
-  const double* fixed_lo; const double* fixed_hi;  // [Nz] variable bounds: components with lo == hi get identity rows
+  const double* fixed_lo; const double* fixed_hi;  // variable bounds at fixed_lo[b * ldb + i]: components with lo == hi get identity rows
+  int64_t ldb;                                     // ldb = 0: one set [Nz] shared by all instances; Nz: per instance [B][Nz]
   const double* dw_inst;   // [B] per-instance delta_w (overrides delta_w)
   const double* gam_inst;  // [B] 1: exact Hessian of the Lagrangian, 0: Gauss-Newton (constraint curvature lam' d'' dropped)
   const int* active;       // [B] 0 = skip this instance
@@ -1000,6 +1001,9 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
   const double mub = (barrier && a.mu_inst) ? a.mu_inst[b] : 0.0;
   const double* zlb = barrier ? a.zl + b * a.ldz : nullptr;
   const double* zub = barrier ? a.zu + b * a.ldz : nullptr;
+  // this instance's variable bounds (ldb = 0: the shared set)
+  const double* lo_b = a.fixed_lo ? a.fixed_lo + b * a.ldb : nullptr;
+  const double* hi_b = a.fixed_hi ? a.fixed_hi + b * a.ldb : nullptr;
   const double taub = fmax(a.tau_min, 1.0 - mub);
 
   long long tick_ = clock64();
@@ -1032,7 +1036,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
             xv[tid] = z[a.zoff[t] + tid];
             yv[tid] = z[a.zoff[t + 1] + tid];
             lamv[tid] = mu[a.cdoff[t] + tid];
-            fxm[tid] = (a.fixed_lo && a.fixed_lo[a.zoff[t] + tid] == a.fixed_hi[a.zoff[t] + tid]) ? 1.0 : 0.0;
+            fxm[tid] = (lo_b && lo_b[a.zoff[t] + tid] == hi_b[a.zoff[t] + tid]) ? 1.0 : 0.0;
             const unsigned long long anyf = __ballot(fxm[tid] != 0.0);   // (tid < N is exactly wavefront 0)
             if (tid == 0) cnt[6] = anyf != 0ull;
           }
@@ -1044,7 +1048,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           if (BAR) brx[tid] = 0.0;
           if (barrier) {
             const int gi = a.zoff[t] + tid;
-            const WideBar wb = wide_bar(xv[tid], a.fixed_lo[gi], a.fixed_hi[gi], zlb[gi], zub[gi], mub);
+            const WideBar wb = wide_bar(xv[tid], lo_b[gi], hi_b[gi], zlb[gi], zub[gi], mub);
             sig = wb.sig; brx[tid] = wb.br;
             if (a.stats) {   // tid < N is exactly wavefront 0: complementarity / barrier statistics of this knot's states
               const double m1 = wave_max(wb.sz_max), m2 = wave_max(wb.isz_max), s1 = wave_sum(wb.sum_z), s2 = wave_sum(wb.logb);
@@ -1063,7 +1067,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           WideBar wb{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
           if (barrier) {
             const int gi = a.zoff[t] + N + (tid - 64);
-            wb = wide_bar(z[gi], a.fixed_lo[gi], a.fixed_hi[gi], zlb[gi], zub[gi], mub);
+            wb = wide_bar(z[gi], lo_b[gi], hi_b[gi], zlb[gi], zub[gi], mub);
           }
           ubar[0] = wb.br; ubar[1] = wb.sig; ubar[2] = wb.zdiff; ubar[3] = wb.sz_max; ubar[4] = wb.isz_max; ubar[5] = wb.sum_z; ubar[6] = wb.logb;
         }
@@ -1218,7 +1222,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           double zd = 0.0;
           if (barrier) {
             const int gi = a.zoff[t] + l;
-            const double lo = a.fixed_lo[gi], hi = a.fixed_hi[gi];
+            const double lo = lo_b[gi], hi = hi_b[gi];
             if (lo != hi) zd = (hi < 1e300 ? zub[gi] : 0.0) - (lo > -1e300 ? zlb[gi] : 0.0);
           }
           // bx = -grad L + byc + brx
@@ -1231,7 +1235,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         // (the pass itself is skipped when no state of this knot is fixed -- it costs ~3 k cycles a stage -- but its two barriers
         //  stay: they also separate the statistics above, which read bx / buv on wavefront 3, from phase 5, where wavefront 0
         //  changes them)
-        if (a.fixed_lo) {
+        if (lo_b) {
           lds_barrier();
           if (cnt[6]) {
             for (int i = tid; i < N * N; i += WG) {
@@ -1373,7 +1377,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           nx_ = z[a.zoff[t + 1] + tid];
           ny_ = z[a.zoff[t + 2] + tid];
           nl_ = mu[a.cdoff[t + 1] + tid];
-          nf_ = (a.fixed_lo && a.fixed_lo[a.zoff[t + 1] + tid] == a.fixed_hi[a.zoff[t + 1] + tid]) ? 1.0 : 0.0;
+          nf_ = (lo_b && lo_b[a.zoff[t + 1] + tid] == hi_b[a.zoff[t + 1] + tid]) ? 1.0 : 0.0;
           if (tid < NU) nu_ = z[a.zoff[t + 1] + N + tid];
         }
         if (DTO_WIDE_PACK_L) store_ltiles<N>(fac + D::F_LA, MA); else store_fac<MAT>(fac + D::F_LA, MA);
@@ -1527,7 +1531,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         const double* wp = a.params + b * a.ldw + a.woff[t];
         if (tid < N) {
           xv[tid] = z[a.zoff[t] + tid];
-          fxm[tid] = (a.fixed_lo && a.fixed_lo[a.zoff[t] + tid] == a.fixed_hi[a.zoff[t] + tid]) ? 1.0 : 0.0;
+          fxm[tid] = (lo_b && lo_b[a.zoff[t] + tid] == hi_b[a.zoff[t] + tid]) ? 1.0 : 0.0;
         }
         __syncthreads();
         if (w == 0) {
@@ -1549,7 +1553,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           double zd = 0.0;
           if (barrier) {
             const int gi = a.zoff[t] + tid;
-            const WideBar wb = wide_bar(xv[tid], a.fixed_lo[gi], a.fixed_hi[gi], zlb[gi], zub[gi], mub);
+            const WideBar wb = wide_bar(xv[tid], lo_b[gi], hi_b[gi], zlb[gi], zub[gi], mub);
             sig = wb.sig; brx[tid] = wb.br; zd = wb.zdiff;
             if (a.stats) {
               const double m1 = wave_max(wb.sz_max), m2 = wave_max(wb.isz_max), s1 = wave_sum(wb.sum_z), s2 = wave_sum(wb.logb);
@@ -1568,7 +1572,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           }
         }
         __syncthreads();
-        if (a.fixed_lo) {
+        if (lo_b) {
           for (int i = tid; i < N * N; i += WG) {
             const int r = i >> 6, c = i & 63;
             if (fxm[r] != 0.0 || fxm[c] != 0.0) MA[r * LD + c] = (r == c) ? 1.0 : 0.0;
@@ -1592,7 +1596,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
             if (barrier) {
               const int gi = a.zoff[t] + l;
               double ap = 1.0, ad = 1.0;
-              wide_bar_step(xv[l], bx[l], a.fixed_lo[gi], a.fixed_hi[gi], zlb[gi], zub[gi], mub, taub, ap, ad);
+              wide_bar_step(xv[l], bx[l], lo_b[gi], hi_b[gi], zlb[gi], zub[gi], mub, taub, ap, ad);
               ap = wave_min(ap); ad = wave_min(ad);
               if (l == 0) { stat[DTO_WIDE_APMAX] = fmin(stat[DTO_WIDE_APMAX], ap); stat[DTO_WIDE_ADMAX] = fmin(stat[DTO_WIDE_ADMAX], ad); }
             }
@@ -1675,12 +1679,12 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         double brl = 0.0, ap = 1.0, ad = 1.0;
         if (barrier) {
           const int gi = a.zoff[t] + l;
-          const double xo = z[gi], lo = a.fixed_lo[gi], hi = a.fixed_hi[gi];
+          const double xo = z[gi], lo = lo_b[gi], hi = hi_b[gi];
           brl = wide_bar(xo, lo, hi, zlb[gi], zub[gi], mub).br;
           wide_bar_step(xo, xv[l], lo, hi, zlb[gi], zub[gi], mub, taub, ap, ad);
           if (l < NU) {
             const int gu = a.zoff[t] + N + l;
-            const double uo = z[gu], ulo = a.fixed_lo[gu], uhi = a.fixed_hi[gu];
+            const double uo = z[gu], ulo = lo_b[gu], uhi = hi_b[gu];
             wide_bar_step(uo, du, ulo, uhi, zlb[gu], zub[gu], mub, taub, ap, ad);
           }
           ap = wave_min(ap); ad = wave_min(ad);
@@ -1690,7 +1694,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           double bru = 0.0;
           if (barrier) {
             const int gu = a.zoff[t] + N + l;
-            bru = wide_bar(z[gu], a.fixed_lo[gu], a.fixed_hi[gu], zlb[gu], zub[gu], mub).br;
+            bru = wide_bar(z[gu], lo_b[gu], hi_b[gu], zlb[gu], zub[gu], mub).br;
           }
           gl += (fv[D::V_GC + N + l] - bru) * du;
         }
@@ -1755,6 +1759,9 @@ __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
   const double mub = (barrier && a.mu_inst) ? a.mu_inst[b] : 0.0;
   const double* zlb = barrier ? a.zl + b * a.ldz : nullptr;
   const double* zub = barrier ? a.zu + b * a.ldz : nullptr;
+  // this instance's variable bounds (ldb = 0: the shared set)
+  const double* lo_b = a.fixed_lo ? a.fixed_lo + b * a.ldb : nullptr;
+  const double* hi_b = a.fixed_hi ? a.fixed_hi + b * a.ldb : nullptr;
   const double taub = fmax(a.tau_min, 1.0 - mub);
   long long tick_ = clock64();
   if (tid < N) yv[tid] = a.dz[b * a.lddz + a.zoff[a.T - 1] + tid];
@@ -1883,12 +1890,12 @@ __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
         double brl = 0.0, ap = 1.0, ad = 1.0;
         if (barrier) {
           const int gi = a.zoff[t] + l;
-          const double xo = z[gi], lo = a.fixed_lo[gi], hi = a.fixed_hi[gi];
+          const double xo = z[gi], lo = lo_b[gi], hi = hi_b[gi];
           brl = wide_bar(xo, lo, hi, zlb[gi], zub[gi], mub).br;
           wide_bar_step(xo, xv[l], lo, hi, zlb[gi], zub[gi], mub, taub, ap, ad);
           if (l < NU) {
             const int gu = a.zoff[t] + N + l;
-            const double uo = z[gu], ulo = a.fixed_lo[gu], uhi = a.fixed_hi[gu];
+            const double uo = z[gu], ulo = lo_b[gu], uhi = hi_b[gu];
             wide_bar_step(uo, du, ulo, uhi, zlb[gu], zub[gu], mub, taub, ap, ad);
           }
           ap = wave_min(ap); ad = wave_min(ad);
@@ -1898,7 +1905,7 @@ __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
           double bru = 0.0;
           if (barrier) {
             const int gu = a.zoff[t] + N + l;
-            bru = wide_bar(z[gu], a.fixed_lo[gu], a.fixed_hi[gu], zlb[gu], zub[gu], mub).br;
+            bru = wide_bar(z[gu], lo_b[gu], hi_b[gu], zlb[gu], zub[gu], mub).br;
           }
           gl += (gcv[N + l] - bru) * du;
         }
@@ -2221,6 +2228,9 @@ __global__ __launch_bounds__(WG) void k_wide_merit(dto_wide_args a) {
   double* pk = dy + N; double* yk = pk + N + NU + 1; double* nl = yk + N;
   const double* z = a.z + b * a.ldz;
   const double* dz = a.dz + b * a.lddz;
+  // this instance's variable bounds (ldb = 0: the shared set)
+  const double* lo_b = a.fixed_lo ? a.fixed_lo + b * a.ldb : nullptr;
+  const double* hi_b = a.fixed_hi ? a.fixed_hi + b * a.ldb : nullptr;
   double facc[DTO_WIDE_TRIALS], tacc[DTO_WIDE_TRIALS];
 #pragma unroll
   for (int k = 0; k < DTO_WIDE_TRIALS; ++k) facc[k] = tacc[k] = 0.0;
@@ -2260,8 +2270,8 @@ __global__ __launch_bounds__(WG) void k_wide_merit(dto_wide_args a) {
       double alpha = barrier ? a.stats[b * DTO_WIDE_NSTAT + DTO_WIDE_APMAX] : 1.0;
       double lo_l = 0.0, hi_l = 0.0, lo_u = 0.0, hi_u = 0.0;
       if (barrier) {
-        lo_l = a.fixed_lo[a.zoff[t] + l]; hi_l = a.fixed_hi[a.zoff[t] + l];
-        if (l < NUK) { lo_u = a.fixed_lo[a.zoff[t] + N + l]; hi_u = a.fixed_hi[a.zoff[t] + N + l]; }
+        lo_l = lo_b[a.zoff[t] + l]; hi_l = hi_b[a.zoff[t] + l];
+        if (l < NUK) { lo_u = lo_b[a.zoff[t] + N + l]; hi_u = hi_b[a.zoff[t] + N + l]; }
       }
 #pragma unroll 1
       for (int k = 0; k < DTO_WIDE_TRIALS; ++k) {

@@ -666,6 +666,72 @@ class Solver:
             capi.check(n._lib.dto_solver_shift_keep_rows(n._h, keep.ctypes.data_as(capi.c_int32_p), n.num_constraint))
         capi.check(n._lib.dto_solver_shift(n._h, int(knots), stream or None))
 
+    def set_bounds_batch(self, lower, upper, stream=0):
+        """dto_solver_set_bounds: per-instance variable bounds for the following solve_batch / begin_batch / begin_warm_batch of a
+        tile-path (17..64-state) problem, e.g. a measured initial state pinned by lower == upper or per-scenario action limits.
+        lower / upper: [B][num_variables] in the problem's layout, torch CUDA tensors or numpy arrays; None, None = back to the
+        shared bounds.  Every instance keeps the problem's bound pattern (fixed where the problem's variable is fixed, finite
+        lower / upper bounds where the problem's are, lower < upper elsewhere, no NaN): numpy input is checked here, the device
+        checks it again in the solver's layout.  A problem embedded in the 64 states keeps the solver's bounds of its padding and
+        auxiliary states and the pins that pins_to_bounds made of stage rows (there the problem itself has (-inf, inf), and so must
+        the input).  shift_batch does not move bounds: set those of the new horizon before begin_warm_batch."""
+        import torch
+        n = self._solve_nlp
+        if not n.structure.wide:
+            raise ValueError("set_bounds_batch: per-instance variable bounds are a tile-path (17..64-state) feature; on the "
+                             "lane-per-instance path give per-instance values through parameters in stage rows (as "
+                             "problems.build_mpc_pendulum does for its initial state)")
+        if self.solve_unsupported:
+            raise ValueError(self.solve_unsupported)
+        if lower is None and upper is None:
+            capi.check(n._lib.dto_solver_set_bounds(n._h, 0, None, 0, None, 0, stream or None))
+            return
+        if lower is None or upper is None:
+            raise ValueError("set_bounds_batch: lower and upper are both None or both given")
+        nv = self.nlp.num_variables
+        host = not (isinstance(lower, torch.Tensor) or isinstance(upper, torch.Tensor))
+        if host:
+            lower, upper = np.asarray(lower, dtype=float), np.asarray(upper, dtype=float)
+        if lower.ndim != 2 or tuple(lower.shape) != tuple(upper.shape) or lower.shape[1] != nv or lower.shape[0] < 1:
+            raise ValueError(f"set_bounds_batch: lower and upper are [B][{nv}] (num_variables of the problem); got "
+                             f"{tuple(lower.shape)} and {tuple(upper.shape)}")
+        if host:
+            check_bounds_pattern(lower, upper, *self.nlp.variable_bounds)
+            lower, upper = (torch.tensor(a, device="cuda", dtype=torch.float64) for a in self.bounds_to_solver_layout(lower, upper))
+        else:
+            lower = lower.to(device="cuda", dtype=torch.float64).contiguous()
+            upper = upper.to(device="cuda", dtype=torch.float64).contiguous()
+            lower, upper = self.bounds_to_solver_layout(lower, upper)
+        torch.cuda.synchronize()
+        nz = n.num_variables
+        capi.check(n._lib.dto_solver_set_bounds(n._h, int(lower.shape[0]), lower.data_ptr(), nz, upper.data_ptr(), nz, stream or None))
+
+    def bounds_to_solver_layout(self, lower, upper):
+        """Per-instance bounds [B][num_variables] in the problem's layout -> the solver's (set_bounds_batch), numpy or torch as
+        given.  Identity unless the problem is embedded in the 64 states: then the solver's shared bounds with the problem's
+        variables overwritten -- padding and auxiliary states and the pins of pins_to_bounds keep the solver's values."""
+        if self._pad is None:
+            return lower, upper
+        zmap = np.asarray(self._pad[0], dtype=np.int64)
+        keep = np.array([p for p, _ in (self._pins or [])], dtype=np.int64)
+        out = []
+        for a, s in zip((lower, upper), self._solve_nlp.variable_bounds):
+            if isinstance(a, np.ndarray):
+                f = np.tile(s, (a.shape[0], 1))
+                f[:, zmap] = a
+                f[:, keep] = s[keep]
+            else:
+                import torch
+                s_ = torch.tensor(s, device=a.device, dtype=torch.float64)
+                f = s_.repeat(a.shape[0], 1)
+                f[:, torch.as_tensor(zmap, device=a.device)] = a
+                if len(keep):
+                    k = torch.as_tensor(keep, device=a.device)
+                    f[:, k] = s_[k]
+                f = f.contiguous()
+            out.append(f)
+        return out[0], out[1]
+
     def repack_batch(self, stream=0) -> int:
         """dto_solver_repack: close the gaps finished instances leave in the tiles; returns the number still running."""
         n = C.c_int(0)
@@ -806,6 +872,33 @@ class Solver:
 
     def end_batch(self, x_out_ptr, ldxo, mu_out_ptr=0, ldmuo=0, stream=0):
         capi.check(self._solve_nlp._lib.dto_solver_end(self._solve_nlp._h, x_out_ptr, ldxo, mu_out_ptr or None, ldmuo, stream or None))
+
+
+def check_bounds_pattern(lower, upper, lo, hi):
+    """Per-instance bounds lower / upper [B][n] against the problem's own lo / hi [n] (Solver.set_bounds_batch, include/dto.h:
+    dto_solver_set_bounds): fixed (lower == upper) exactly where the problem's variable is, finite lower / upper bounds exactly
+    where the problem's are, lower < upper elsewhere, no NaN.  Raises ValueError naming the first offending instance and variable."""
+    lower, upper = np.asarray(lower, dtype=float), np.asarray(upper, dtype=float)
+    fixed = lo == hi
+    with np.errstate(invalid="ignore"):
+        checks = [("NaN", np.isnan(lower) | np.isnan(upper)),
+                  ("not fixed (lower != upper) where the problem's variable is fixed", fixed & (lower != upper)),
+                  ("fixed (lower == upper) where the problem's variable is not", ~fixed & (lower == upper)),
+                  ("finite lower bound where the problem's is infinite", np.isfinite(lower) & ~np.isfinite(lo)),
+                  ("infinite lower bound where the problem's is finite", ~np.isfinite(lower) & np.isfinite(lo)),
+                  ("finite upper bound where the problem's is infinite", np.isfinite(upper) & ~np.isfinite(hi)),
+                  ("infinite upper bound where the problem's is finite", ~np.isfinite(upper) & np.isfinite(hi)),
+                  ("lower >= upper", ~fixed & ~(lower < upper))]
+    first = None
+    for why, bad in checks:
+        if bad.any():
+            b, j = np.argwhere(bad)[0]
+            if first is None or (b, j) < first[:2]:
+                first = (b, j, why)
+    if first is not None:
+        b, j, why = first
+        raise ValueError(f"set_bounds_batch: instance {b}, variable {j}: {why} (lower {lower[b, j]!r}, upper {upper[b, j]!r}; "
+                         f"the problem's {lo[j]!r}, {hi[j]!r})")
 
 
 def _with_exact_hessians(dynamics, objective, constraints):

@@ -282,8 +282,24 @@ int dto_solver_begin_warm(dto_problem* p, const dto_options* opt, const dto_batc
  * final state and repeat the last action (the usual MPC warm start).  Stage-constraint multipliers stay with their knots.
  * Follow with dto_solver_begin_warm(x = NULL, params = the newly measured state) and dto_solver_run.  Needs the same state /
  * action dimensions at every knot and knots < horizon - 1.  Tile path: one launch per array (z, multipliers, z_L, z_U), no host
- * round trip; the rows marked by dto_solver_shift_keep_rows keep their multipliers. */
+ * round trip; the rows marked by dto_solver_shift_keep_rows keep their multipliers.  Variable bounds do not move: with
+ * per-instance bounds (dto_solver_set_bounds) the caller sets those of the new horizon (e.g. the measured first-knot state)
+ * before dto_solver_begin_warm. */
 int dto_solver_shift(dto_problem* p, int knots, void* stream);
+/* Per-instance variable bounds for the batched solver entry points of a tile-path (17..64-state) plugin.
+ * lower / upper: DEVICE [B][ldl] / [B][ldu], solver layout (num_variables entries per instance).  Copied on `stream` into
+ * storage owned by the handle and checked before the call returns.  They apply to every later dto_solve_batch /
+ * dto_solver_begin / dto_solver_begin_warm whose batch has B instances.  A begun state keeps the bounds it was begun with.
+ * lower = upper = NULL: back to the problem's shared bounds.
+ * Every instance's bounds have the pattern of the problem's own (dto_variable_bounds): a variable is fixed (lo == hi) exactly
+ * where the problem's is (its value may differ), a lower / upper bound is finite exactly where the problem's is, lo < hi where
+ * the variable is not fixed, no NaN.  So the barrier, the bound multipliers and the identity rows of fixed variables are the
+ * problem's; only the values are per instance (e.g. a measured initial state pinned by lo == hi, per-scenario actuator
+ * limits).  A violation returns DTO_ERR_INVALID naming the first offending instance and variable and leaves the previous
+ * setting in force; a begin whose B differs from the B set here returns DTO_ERR_INVALID.  The lane-per-instance path returns
+ * DTO_ERR_UNSUPPORTED (per-instance values enter there through parameters in stage rows). */
+int dto_solver_set_bounds(dto_problem* p, int64_t B, const double* lower, int64_t ldl, const double* upper, int64_t ldu,
+                          void* stream);
 /* Tile path: keep[i] != 0 (HOST [n], n = num_constraint) marks constraint row i as one whose multiplier stays with its knot in
  * dto_solver_shift -- the stage rows that a 17..63-state problem carries as dynamics rows of its 64-state embedding (the Python
  * Solver sets them from its embedding before every shift).  keep = NULL clears the marks.  The lane-per-instance path keeps its

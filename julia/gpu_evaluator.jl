@@ -245,6 +245,36 @@ function solve_batch(ev::GPUEvaluator, X0::Matrix{Float64}; options = Options(),
 end
 
 """
+    set_bounds_batch!(ev, lower, upper)
+    set_bounds_batch!(ev, nothing, nothing)
+
+Per-instance variable bounds (`dto_solver_set_bounds`, tile path: 17..64-state models) for the following `solve_batch` /
+`resolve_warm!` calls on `ev` with B = size(lower, 2) instances: `lower` / `upper` are num_variables × B in the solver's layout,
+with the pattern of the problem's own bounds (fixed, finite lower / upper exactly where the problem's are; the values may
+differ) -- e.g. each instance's measured initial state pinned by lower == upper.  `nothing, nothing` goes back to the shared
+bounds.  The library keeps its own copy, so the device arrays are freed here.
+"""
+function set_bounds_batch!(ev::GPUEvaluator, lower::Union{Matrix{Float64}, Nothing}, upper::Union{Matrix{Float64}, Nothing})
+    if lower === nothing && upper === nothing
+        dto_check(ccall((:dto_solver_set_bounds, libdto), Cint,
+                        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                        ev.handle, 0, C_NULL, 0, C_NULL, 0, C_NULL))
+        return nothing
+    end
+    (lower === nothing || upper === nothing) && error("lower and upper are both nothing or both given")
+    nz, B = size(lower)
+    nz == ev.num_variables || error("lower must have num_variables rows")
+    size(upper) == size(lower) || error("upper must have the size of lower")
+    dlo = dto_device_array(lower)                                 # column-major nz × B == instance-major [B][nz]
+    dhi = dto_device_array(upper)
+    rc = ccall((:dto_solver_set_bounds, libdto), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+               ev.handle, B, dlo, nz, dhi, nz, C_NULL)
+    dto_device_free(dlo); dto_device_free(dhi)
+    dto_check(rc)
+    return nothing
+end
+
+"""
     resolve_warm!(ev, B, parameters; options = Options(), mu0 = 0.0)
 
 Receding-horizon re-solve of the batch solved last on `ev` (same B): the multipliers, bound multipliers, slacks and the
