@@ -13,7 +13,7 @@
 
 #include <stdint.h>
 
-#define DTO_PLUGIN_ABI 6
+#define DTO_PLUGIN_ABI 7
 
 #ifdef __cplusplus
 extern "C" {

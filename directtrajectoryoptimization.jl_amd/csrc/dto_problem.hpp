@@ -17,6 +17,7 @@ int hip_fail(hipError_t e, const char* what);
 struct SolverState;  // dto_solver.cpp
 struct ImState;      // dto_solver.cpp: instance-major engine
 struct WideState;    // dto_solver.cpp: solver state of the tile (MFMA) path
+struct WideKkt;      // dto_solver.cpp: tile path, the linear solver alone (dto_kkt_assemble / factor / solve)
 
 // dto_solver_trace: a HIP event pair around every kernel launch of the solver entry points, on the stream the kernel is launched
 // on (the caller's, or the low-priority one of the early back substitutions) -- so that a caller can report what each kernel
@@ -60,6 +61,7 @@ struct Problem {
   SolverState* solver = nullptr;
   ImState* im = nullptr;
   WideState* wide = nullptr;   // tile path: iterate, multipliers and host records of the batch begun last
+  WideKkt* wide_kkt = nullptr; // tile path: the system assembled last by dto_kkt_assemble; its factor lives in wide_fac
   int* d_shift_keep = nullptr; // dto_solver_shift_keep_rows: [Nc] 1 = the multiplier of this row stays with its knot (NULL: none)
   double* d_bnd = nullptr;     // dto_solver_set_bounds (tile path): per-instance bounds [2][bnd_B][Nz], lower then upper (NULL: shared)
   int64_t bnd_B = 0;
@@ -67,7 +69,8 @@ struct Problem {
   int hessian_mode_last = -1;     // dto_solver_hessian_mode: what the last solve / begun batch used
   int engine_req = 0;      // dto_solver_set_engine: 0 automatic, 1 SoA tiles, 2 instance-major
   bool im_active = false;  // which engine holds the batch that was begun last
-  // factor storage and inertia flags of the wide-stage KKT kernels
+  // factor storage and inertia flags of the wide-stage KKT kernels (wide_fac is shared by dto_kkt_step_batch, the solver and
+  // dto_kkt_factor: whoever writes it last owns it, WideKkt::factored says whether that is dto_kkt_factor)
   double* wide_fac = nullptr;
   size_t wide_fac_len = 0;
   int* wide_flags = nullptr;

@@ -146,9 +146,11 @@ struct ImState {
 };
 
 static void release_wide(Problem* p);
+static void release_wide_kkt(Problem* p);
 
 void Problem::free_solver() {
   release_wide(this);
+  release_wide_kkt(this);
   if (solver) {
     solver->release();
     delete solver;
@@ -232,6 +234,36 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
 static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                                double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 
+// ---- wide-stage models, the linear solver alone: device copies of what dto_kkt_assemble was given.  The factor itself is in
+//      p->wide_fac, which dto_kkt_step_batch and the solver write too: each of them clears `factored`
+struct WideKkt {
+  int64_t B = 0;
+  bool assembled = false, factored = false, own_params = false, use_sigx = false, use_sigc = false;
+  double delta_w = 0.0, delta_c = 0.0;
+  double *z = nullptr, *mu = nullptr, *params = nullptr, *sigx = nullptr, *sigc = nullptr;
+  size_t cap_z = 0, cap_mu = 0, cap_params = 0, cap_sigx = 0, cap_sigc = 0;   // doubles allocated
+  int* flags = nullptr;   // [2][B]: inertia flags, negative-pivot counts
+  size_t cap_flags = 0;
+  void release() {
+    for (void* q : {(void*)z, (void*)mu, (void*)params, (void*)sigx, (void*)sigc, (void*)flags})
+      if (q) (void)hipFree(q);
+    z = mu = params = sigx = sigc = nullptr; flags = nullptr;
+    cap_z = cap_mu = cap_params = cap_sigx = cap_sigc = cap_flags = 0;
+    B = 0; assembled = factored = false;
+  }
+};
+static void release_wide_kkt(Problem* p) {
+  if (p->wide_kkt) { p->wide_kkt->release(); delete p->wide_kkt; p->wide_kkt = nullptr; }
+}
+// every other writer of p->wide_fac calls this before it launches
+static inline void wide_fac_taken(Problem* p) {
+  if (p->wide_kkt) p->wide_kkt->factored = false;
+}
+static inline void wide_args_no_linear(dto_wide_args& a) {
+  a.sigma_x = a.sigma_c = nullptr; a.ldsx = a.ldsc = 0; a.nneg = nullptr;
+  a.rhs_x = a.rhs_c = nullptr; a.ldrx = a.ldrc = 0;
+}
+
 // ---- wide-stage models (dto_wide_kernels.hpp): one workgroup per instance, AoS buffers used as they are
 static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, double delta_w, double delta_c,
                      double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* inertia_ok) {
@@ -242,6 +274,7 @@ static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t l
   const Layout& L = p->L;
   if (L.Nstage != 0 || L.Ngen != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows and bounds only");
   hipStream_t st = (hipStream_t)b->stream;
+  wide_fac_taken(p);
   const size_t need = (size_t)b->B * (size_t)L.T * (size_t)info.fac_stage;
   if (p->wide_fac_len < need) {
     if (p->wide_fac) (void)hipFree(p->wide_fac);
@@ -265,6 +298,7 @@ static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t l
   a.fac = p->wide_fac; a.flags = p->wide_flags; a.Nc = L.Nc;
   a.fixed_lo = a.fixed_hi = nullptr; a.ldb = 0; a.dw_inst = nullptr; a.gam_inst = nullptr; a.active = nullptr; a.stats = nullptr; a.merit = nullptr;
   a.zl = a.zu = nullptr; a.mu_inst = nullptr; a.tau_min = 0.99;
+  wide_args_no_linear(a);
   a.prof = nullptr;
   if (const char* e = getenv("DTO_WIDE_PROF")) a.prof = (long long*)(uintptr_t)strtoull(e, nullptr, 0);  // debug: device pointer
   const int lrc = p->vt->launch_wide(DTO_WIDE_STEP, &a, (void*)st);
@@ -279,6 +313,126 @@ static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t l
   return DTO_OK;
 }
 
+
+// ---- wide-stage models, the linear solver alone (dto_kkt_assemble / dto_kkt_factor / dto_kkt_solve): factor once into
+//      p->wide_fac (k_wide_step in its linear-solver mode, terminal block included), then every solve is substitution only
+//      (k_wide_fsub + k_wide_bwd).  Bounds are ignored, as on the lane path.
+static int wide_kkt_grow(double** ptr, size_t* cap, size_t need, const char* what) {
+  if (*cap >= need) return DTO_OK;
+  if (*ptr) (void)hipFree(*ptr);
+  *ptr = nullptr; *cap = 0;
+  hipError_t e = hipMalloc((void**)ptr, need * sizeof(double));
+  if (e != hipSuccess) return hip_fail(e, what);
+  *cap = need;
+  return DTO_OK;
+}
+static void wide_kkt_args(Problem* p, dto_wide_args& a) {
+  const Layout& L = p->L;
+  const WideKkt& K = *p->wide_kkt;
+  a.T = L.T; a.B = K.B;
+  a.kind = p->d_kind; a.zoff = p->d_zoff; a.woff = p->d_woff; a.cdoff = p->d_cdoff;
+  a.params = K.own_params ? K.params : p->d_params; a.ldw = K.own_params ? L.Nw : 0;
+  a.z = K.z; a.ldz = L.Nz; a.mu = K.mu; a.ldmu = L.Nc;
+  a.delta_w = K.delta_w; a.delta_c = K.delta_c; a.piv_tol = 1e-9;
+  a.dz = nullptr; a.lddz = 0; a.dmu = nullptr; a.lddmu = 0;
+  a.fac = p->wide_fac; a.flags = K.flags; a.Nc = L.Nc; a.prof = nullptr;
+  a.fixed_lo = a.fixed_hi = nullptr; a.ldb = 0; a.dw_inst = nullptr; a.gam_inst = nullptr; a.active = nullptr; a.stats = nullptr; a.merit = nullptr;
+  a.zl = a.zu = nullptr; a.mu_inst = nullptr; a.tau_min = 0.99;
+  wide_args_no_linear(a);
+}
+static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_system* sys) {
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  const Layout& L = p->L;
+  if (L.Nstage != 0 || L.Ngen != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows and bounds only");
+  if (b->B < 1) return set_error(DTO_ERR_INVALID, "empty batch");
+  if (b->params && L.Nw > 0 && b->ldp < L.Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
+  if (!p->wide_kkt) p->wide_kkt = new WideKkt();
+  WideKkt& K = *p->wide_kkt;
+  K.assembled = K.factored = false;
+  dto_wide_info info;
+  p->vt->wide_info(&info);
+  const size_t B = (size_t)b->B, Nz = (size_t)L.Nz, Nc = (size_t)std::max<int64_t>(1, L.Nc), Nw = (size_t)L.Nw;
+  // the factor records: T per instance, the last one for the terminal block
+  const size_t need_fac = B * (size_t)L.T * (size_t)info.fac_stage;
+  if (p->wide_fac_len < need_fac) {
+    if (p->wide_fac) (void)hipFree(p->wide_fac);
+    p->wide_fac = nullptr; p->wide_fac_len = 0;
+    hipError_t e = hipMalloc((void**)&p->wide_fac, need_fac * sizeof(double));
+    if (e != hipSuccess)
+      return hip_fail(e, ("dto_kkt_assemble: hipMalloc of the factor records (" + std::to_string(need_fac * sizeof(double)) + " bytes: " +
+                          std::to_string(b->B) + " instances x " + std::to_string(L.T) + " knots x " +
+                          std::to_string(info.fac_stage * (int64_t)sizeof(double)) + " bytes)").c_str());
+    p->wide_fac_len = need_fac;
+  }
+  if ((rc = wide_kkt_grow(&K.z, &K.cap_z, B * Nz, "dto_kkt_assemble: hipMalloc of the point"))) return rc;
+  if ((rc = wide_kkt_grow(&K.mu, &K.cap_mu, B * Nc, "dto_kkt_assemble: hipMalloc of the multipliers"))) return rc;
+  K.own_params = b->params != nullptr && Nw > 0;
+  if (K.own_params && (rc = wide_kkt_grow(&K.params, &K.cap_params, B * Nw, "dto_kkt_assemble: hipMalloc of the parameters"))) return rc;
+  K.use_sigx = sys->sigma_x != nullptr;
+  K.use_sigc = sys->sigma_c != nullptr && L.Nc > 0;
+  if (K.use_sigx && (rc = wide_kkt_grow(&K.sigx, &K.cap_sigx, B * Nz, "dto_kkt_assemble: hipMalloc of sigma_x"))) return rc;
+  if (K.use_sigc && (rc = wide_kkt_grow(&K.sigc, &K.cap_sigc, B * Nc, "dto_kkt_assemble: hipMalloc of sigma_c"))) return rc;
+  if (K.cap_flags < 2 * B) {
+    if (K.flags) (void)hipFree(K.flags);
+    K.flags = nullptr; K.cap_flags = 0;
+    HIP_TRY(hipMalloc((void**)&K.flags, 2 * B * sizeof(int)));
+    K.cap_flags = 2 * B;
+  }
+  hipStream_t st = (hipStream_t)b->stream;
+  auto copy = [&](double* dst, size_t n, const double* src, int64_t ld) {
+    return hipMemcpy2DAsync(dst, n * sizeof(double), src, (size_t)ld * sizeof(double), n * sizeof(double), B, hipMemcpyDeviceToDevice, st);
+  };
+  HIP_TRY(copy(K.z, Nz, b->x, b->ldx));
+  if (L.Nc > 0) HIP_TRY(copy(K.mu, (size_t)L.Nc, sys->mu, sys->ldmu));
+  if (K.own_params) HIP_TRY(copy(K.params, Nw, b->params, b->ldp));
+  if (K.use_sigx) HIP_TRY(copy(K.sigx, Nz, sys->sigma_x, sys->ldsx));
+  if (K.use_sigc) HIP_TRY(copy(K.sigc, (size_t)L.Nc, sys->sigma_c, sys->ldsc));
+  // (dto_kkt_factor takes a stream of its own: the copies are complete when this returns)
+  HIP_TRY(hipStreamSynchronize(st));
+  K.B = b->B; K.delta_w = sys->delta_w; K.delta_c = sys->delta_c;
+  K.assembled = true;
+  return DTO_OK;
+}
+static int wide_kkt_factor(Problem* p, int32_t* inertia_ok, int32_t* num_negative, hipStream_t st) {
+  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  WideKkt& K = *p->wide_kkt;
+  K.factored = false;
+  dto_wide_info info;
+  p->vt->wide_info(&info);
+  if (p->wide_fac_len < (size_t)K.B * (size_t)p->L.T * (size_t)info.fac_stage) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  dto_wide_args a;
+  wide_kkt_args(p, a);
+  a.sigma_x = K.use_sigx ? K.sigx : nullptr; a.ldsx = p->L.Nz;
+  a.sigma_c = K.use_sigc ? K.sigc : nullptr; a.ldsc = std::max<int64_t>(1, p->L.Nc);
+  a.nneg = K.flags + K.B;
+  const int lrc = p->vt->launch_wide(DTO_WIDE_FACTOR, &a, (void*)st);
+  if (lrc != 0) return hip_fail((hipError_t)lrc, "wide factor launch");
+  K.factored = true;
+  if (inertia_ok || num_negative) {
+    std::vector<int> fl(2 * (size_t)K.B);
+    HIP_TRY(hipMemcpyAsync(fl.data(), K.flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < K.B; ++i) {
+      if (inertia_ok) inertia_ok[i] = fl[(size_t)i] ? 1 : 0;
+      if (num_negative) num_negative[i] = fl[(size_t)(K.B + i)];
+    }
+  }
+  return DTO_OK;
+}
+static int wide_kkt_solve(Problem* p, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, double* sol_x, int64_t ldsx,
+                          double* sol_c, int64_t ldsc, hipStream_t st) {
+  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (!p->wide_kkt->factored)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_factor has not been called (or dto_kkt_step_batch / the solver has used the factor storage since)");
+  dto_wide_args a;
+  wide_kkt_args(p, a);
+  a.rhs_x = rhs_x; a.ldrx = ldrx; a.rhs_c = rhs_c; a.ldrc = ldrc;
+  a.dz = sol_x; a.lddz = ldsx; a.dmu = sol_c; a.lddmu = ldsc;
+  const int lrc = p->vt->launch_wide(DTO_WIDE_SOLVE, &a, (void*)st);
+  if (lrc != 0) return hip_fail((hipError_t)lrc, "wide solve launch");
+  return DTO_OK;
+}
 
 // ---- wide-stage models: helpers of the host-driven solver below (wide_outer)
 constexpr int AXPY_BLOCKS_PER_ROW = 64;
@@ -487,6 +641,7 @@ static void wide_fill_args(Problem* p, dto_wide_args& a) {
   a.fac = p->wide_fac; a.flags = W.flags; a.Nc = L.Nc; a.prof = nullptr;
   a.fixed_lo = W.lo; a.fixed_hi = W.hi; a.ldb = W.ldb; a.dw_inst = W.dw; a.gam_inst = W.gam; a.active = W.active; a.stats = W.stats; a.merit = W.merit;
   a.zl = W.zl; a.zu = W.zu; a.mu_inst = W.mu; a.tau_min = W.opt.tau_min;
+  wide_args_no_linear(a);
 }
 
 // the batch's parameters: b->params (DEVICE [B][ldp]) copied into the state, NULL = the problem's shared ones
@@ -509,6 +664,7 @@ static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bo
   const Layout& L = p->L;
   if (L.Nstage != 0 || L.Ngen != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows and bounds only");
   if (p->wide) p->wide->begun = false;
+  wide_fac_taken(p);
   if (warm) {
     if (!p->wide || !p->wide->z || p->wide->B != b->B)
       return set_error(DTO_ERR_INVALID, "dto_solver_begin_warm needs the device state of a previous solve of the same batch size");
@@ -637,6 +793,7 @@ static int wide_outer(Problem* p, hipStream_t st) {
   dto_wide_args a;
   wide_fill_args(p, a);
   auto launch = [&](int op) -> int {
+    if (op == DTO_WIDE_STEP) wide_fac_taken(p);
     const int lrc = p->vt->launch_wide(op, &a, (void*)st);
     return lrc;
   };
@@ -3472,9 +3629,9 @@ int dto_solver_begin_warm(dto_problem* h, const dto_options* opt, const dto_batc
 int dto_kkt_assemble(dto_problem* h, const dto_batch* b, const dto_kkt_system* sys) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || !b || !b->x || !sys || !sys->mu) return set_error(DTO_ERR_INVALID, "null argument");
-  if (p->vt->launch_wide) return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_assemble/factor/solve: use dto_kkt_step_batch for wide-stage models");
   if (b->ldx < p->L.Nz || sys->ldmu < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if ((sys->sigma_x && sys->ldsx < p->L.Nz) || (sys->sigma_c && sys->ldsc < p->L.Nc)) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (p->vt->launch_wide) return dto::wide_kkt_assemble(p, b, sys);   // tile path: the factor is stored, a solve is substitution only
   // models with GeneralConstraint rows: this is the STAGE part of K (dynamics + stage rows); the border is the caller's
   int rc = dto::ensure_state(p, b->B, true);
   if (rc) return rc;
@@ -3510,6 +3667,7 @@ int dto_kkt_assemble(dto_problem* h, const dto_batch* b, const dto_kkt_system* s
 
 int dto_kkt_factor(dto_problem* h, int32_t* inertia_ok, int32_t* num_negative, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
+  if (p && p->vt->launch_wide) return dto::wide_kkt_factor(p, inertia_ok, num_negative, (hipStream_t)stream);
   if (!p || !p->solver || !p->solver->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
   SolverState& S = *p->solver;
   hipStream_t st = (hipStream_t)stream;
@@ -3532,9 +3690,12 @@ int dto_kkt_factor(dto_problem* h, int32_t* inertia_ok, int32_t* num_negative, v
 int dto_kkt_solve(dto_problem* h, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, double* sol_x,
                   int64_t ldsx, double* sol_c, int64_t ldsc, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
-  if (!p || !p->solver || !p->solver->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  const bool wide = p && p->vt->launch_wide;
+  if (!p || (wide ? !p->wide_kkt || !p->wide_kkt->assembled : !p->solver || !p->solver->assembled))
+    return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
   if (!rhs_x || !sol_x || (p->L.Nc > 0 && (!rhs_c || !sol_c))) return set_error(DTO_ERR_INVALID, "null argument");
   if (ldrx < p->L.Nz || ldsx < p->L.Nz || ldrc < p->L.Nc || ldsc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (wide) return dto::wide_kkt_solve(p, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, (hipStream_t)stream);
   hipStream_t st = (hipStream_t)stream;
   dto_kkt_args a;
   dto::fill_kkt_args(p, a);

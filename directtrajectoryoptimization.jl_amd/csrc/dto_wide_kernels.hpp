@@ -23,7 +23,9 @@
 #include "dto_math.hpp"
 #include "dto_model_plugin.h"
 
-enum dto_wide_op { DTO_WIDE_STEP = 0, DTO_WIDE_MERIT = 1 };
+// DTO_WIDE_FACTOR / DTO_WIDE_SOLVE: the linear solver alone (dto_kkt_factor / dto_kkt_solve): factor once, then any number of
+// substitution-only solves against the stored records
+enum dto_wide_op { DTO_WIDE_STEP = 0, DTO_WIDE_MERIT = 1, DTO_WIDE_FACTOR = 2, DTO_WIDE_SOLVE = 3 };
 
 struct dto_wide_info {
   int supported;
@@ -63,6 +65,12 @@ struct dto_wide_args {
   const double* zl; const double* zu;   // [B][Nz] bound multipliers
   const double* mu_inst;                // [B] barrier parameter
   double tau_min;                       // fraction-to-the-boundary parameter floor (0.99)
+  // ---- the linear solver alone (DTO_WIDE_FACTOR / DTO_WIDE_SOLVE); all NULL / 0 everywhere else
+  const double* sigma_x; int64_t ldsx;  // [B][ldsx] >= 0 added to the diagonal of H, actions and last knot included (NULL: none)
+  const double* sigma_c; int64_t ldsc;  // [B][ldsc] >= 0 subtracted from the diagonal of the constraint block (NULL: none)
+  int* nneg;                            // [B] number of negative pivots (DTO_WIDE_FACTOR)
+  const double* rhs_x; int64_t ldrx;    // [B][ldrx] right-hand side of the variables, problem layout (DTO_WIDE_SOLVE)
+  const double* rhs_c; int64_t ldrc;    // [B][ldrc] right-hand side of the constraint rows
 };
 // stats: 0 f (barrier terms excluded), 1 theta_1, 2 theta_inf, 3 dual infeasibility, 4 grad phi' dz, 5 sum |lam|, 6/7 scratch,
 // 8 alpha_pmax, 9 alpha_dmax, 10 max s z, 11 max 1 / (s z), 12 sum z, 13 sum log s  (8..13 only with bounds)
@@ -939,7 +947,11 @@ struct WK {
 // ---------------------------------------------------------------------------------------------------
 // BAR: instantiation with the barrier terms of finite variable bounds (launch_wide picks it when the caller passes bound
 // multipliers); the plain KKT step carries none of that code
-template <class M, bool BAR>
+// LIN: the factorisation of the linear solver alone (DTO_WIDE_FACTOR): sigma_x / sigma_c on the diagonals, the terminal factor
+// stored in record T-1 (packed L_A and D_A^-1: k_wide_fsub solves the last block with it), the negative-pivot count reported per
+// instance, no step written (the right-hand sides of the records are replaced by every k_wide_fsub).  A compile-time mode: the
+// two other instantiations carry none of it
+template <class M, bool BAR, bool LIN = false>
 __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
   constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
   static_assert(N == 64, "wide path is built for 64 states (one wavefront of rows, 4 x 4 tiles)");
@@ -1058,6 +1070,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
               }
             }
           }
+          if constexpr (LIN) { if (a.sigma_x) sig = a.sigma_x[b * a.ldsx + a.zoff[t] + tid]; }
           MA[tid * LD + tid] += dw + sig;
         }
         if (t == 0 && tid < NU) sc[tid] = z[a.zoff[t] + N + tid];
@@ -1207,6 +1220,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
               const double* ubar = brx + N + 8 * j;
               buv[j] = -(gc[N + j] + part) + (BAR ? ubar[0] : 0.0);
               auu[j * NU + j] += dw + (BAR ? ubar[1] : 0.0);
+              if constexpr (LIN) { if (a.sigma_x) auu[j * NU + j] += a.sigma_x[b * a.ldsx + a.zoff[t] + N + j]; }
               if (barrier && a.stats) {
                 stat[DTO_WIDE_SZMAX] = fmax(stat[DTO_WIDE_SZMAX], ubar[3]); stat[DTO_WIDE_ISZMAX] = fmax(stat[DTO_WIDE_ISZMAX], ubar[4]);
                 stat[DTO_WIDE_SUMZ] += ubar[5]; stat[DTO_WIDE_LOGBAR] += ubar[6];
@@ -1394,7 +1408,9 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
             double fuu = 0.0;
 #pragma unroll
             for (int ju = 0; ju < NU; ++ju) fuu += fu[ju * N + row] * fu[ju * N + col] * ip[ju];
-            macc[jb][j] = (row == col ? dc : 0.0) + fuu;
+            double dcr = dc;
+            if constexpr (LIN) { if (a.sigma_c && row == col) dcr += a.sigma_c[b * a.ldsc + a.cdoff[t] + row]; }
+            macc[jb][j] = (row == col ? dcr : 0.0) + fuu;
           }
         }
         mm_row4<0, N>(macc, MF, w * TB, MF, dAi, 1.0);
@@ -1563,6 +1579,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
               }
             }
           }
+          if constexpr (LIN) { if (a.sigma_x) sig = a.sigma_x[b * a.ldsx + a.zoff[t] + tid]; }
           MA[tid * LD + tid] += dw + sig;
           bx[tid] = -(gc[tid] + gyp[tid]) + byc[tid] + (BAR ? brx[tid] : 0.0);
           if (a.stats) {
@@ -1582,13 +1599,20 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         }
         if (DTO_WIDE_LDL_RANK1) ldl_rank1<N>((lds_double*)MA, (lds_double*)dA, (lds_double*)dAi, (lds_double*)LI, (lds_double*)colb, (lds_double*)dg0, a.piv_tol, (lds_int*)cnt);
         else ldl_blocked<N>(MA, dA, dAi, LI, a.piv_tol, cnt);
+        if constexpr (LIN) {
+          // the terminal factor, record T-1 (allocated with the others, unused by the step: its solve is the code below)
+          static_assert(!LIN || (DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD), "k_wide_fsub reads packed triangular factors");
+          double* facT = facb + (int64_t)t * D::FAC;
+          store_ltiles<N>(facT + D::F_LA, MA);
+          if (tid < N) facT[D::F_VEC + D::V_DA + tid] = dAi[tid];
+        }
         if (w == 0) {
           trsv_lower<N>(MA, bx);
           if (l < N) bx[l] *= dAi[l];
           trsv_lower_t<N>(MA, bx);
           if (l < N) {
             yv[l] = bx[l];
-            a.dz[b * a.lddz + a.zoff[t] + l] = bx[l];
+            if constexpr (!LIN) a.dz[b * a.lddz + a.zoff[t] + l] = bx[l];
           }
           if (a.stats) {
             const double part = wave_sum((gc[l] - (BAR ? brx[l] : 0.0)) * bx[l]);     // gradient of the barrier objective along the step
@@ -1608,6 +1632,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
   }
   DTO_WIDE_TICK(13);
   if (tid == 0) a.flags[b] = (cnt[0] == (int)a.Nc && cnt[1] == 0) ? 1 : 0;
+  if constexpr (LIN) { if (tid == 0 && a.nneg) a.nneg[b] = cnt[0]; }
 #if DTO_WIDE_SPLIT_BWD
   // the backward sweep is k_wide_bwd (next launch on the same stream): it picks up the statistics from here
   if (a.stats && tid < DTO_WIDE_NSTAT) a.stats[b * DTO_WIDE_NSTAT + tid] = stat[tid];
@@ -1922,6 +1947,194 @@ __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
   }
   __syncthreads();
   if (a.stats && tid < DTO_WIDE_NSTAT) a.stats[b * DTO_WIDE_NSTAT + tid] = stat[tid];
+}
+
+// ---------------------------------------------------------------------------------------------------
+// forward substitution with a NEW right-hand side against the stored records (DTO_WIDE_SOLVE; the records come from
+// k_wide_step<M, false, true>): the transposed mirror of k_wide_bwd, stage by stage what k_wide_step does to its own
+// right-hand side while it factorises --
+//     bu^ = L_u^-1 ru,   bx = rx + by - A_xu' (bu^ / piv),   bd = rc - F_u' (bu^ / piv),   byn = -V_u' (bu^ / piv)
+//     bx~ = L_A^-1 bx,   bd^ = L_M^-1 (bd - F~ D_A^-1 bx~),   by <- byn - V~' D_A^-1 bx~ + E~' D_M^-1 bd^
+// and the terminal block x_T = L_A^-T D_A^-1 L_A^-1 (rx_T + by) from record T-1.  bu^, bx~ and bd^ go to the right-hand-side
+// slots of the records, x_T to dz: k_wide_bwd<M, false> then runs unchanged.  The matrices of the records are only read.
+// No O(n^3) work: per stage five matrix loads, two triangular solves by one wavefront and three workgroup-wide products.
+// PRE: the record of stage t+1 travels into registers while stage t is worked on (as in k_wide_bwd); 0: loaded at the top of
+// its own stage (kept for A/B runs, -DDTO_WIDE_FSUB_PREFETCH=0).  grid = B, block = 256, LDS as k_wide_bwd.
+// ---------------------------------------------------------------------------------------------------
+#ifndef DTO_WIDE_FSUB_PREFETCH
+#define DTO_WIDE_FSUB_PREFETCH 1
+#endif
+template <class M, bool PRE>
+__global__ __launch_bounds__(WG) void k_wide_fsub(dto_wide_args a) {
+  constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
+  static_assert(N == 64, "wide path is built for 64 states");
+  static_assert(DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD, "reads packed triangular factors");
+  using D = Dims<N, NU>;
+  constexpr int LD = D::LD, MAT = D::MAT;
+  constexpr int NP = (MAT / 2 + WG - 1) / WG;            // 16-byte pieces of one matrix per thread
+  constexpr int NPL = D::LTILES * TB * TB / 2 / WG;      // pieces of a triangular factor
+  constexpr int NSC = (NU * (NU + 2) + 7) & ~7;          // scalars of the action block in the record
+  static_assert(NSC <= 32 && NU <= 32, "scalars of the action block: one lane each");
+  extern __shared__ double sm[];
+  double* MA = sm;
+  double* MF = MA + MAT;
+  double* MV = MF + MAT;
+  double* ME = MV + MAT;
+  double* au = ME + MAT;
+  double* fu = au + NU * N;
+  double* vu = fu + NU * N;
+  double* bx = vu + NU * N;
+  double* bd = bx + N;
+  double* byc = bd + N;        // carried right-hand side into the next stage
+  double* byn = byc + N;       // its action part
+  double* dAi = byn + N;
+  double* dMi = dAi + N;
+  double* scv = dMi + N;       // [32] scalars of the action block: 1 / pivot [NU], (reduced right-hand side [NU]), L_u [NU][NU]
+  double* ruv = scv + 32;      // [8] right-hand side of the actions (NU <= 4)
+  static_assert(4 * MAT + (6 + 3 * NU) * N + 32 + 8 <= BwdLds<M>::DOUBLES, "within the LDS image of k_wide_bwd");
+  const int tid = threadIdx.x, w = wave_id(), l = lane_id();
+  const int64_t b = blockIdx.x;
+  if (a.active && !a.active[b]) return;
+  double* facb = a.fac + b * (int64_t)a.T * D::FAC;
+  const double* rx = a.rhs_x + b * a.ldrx;
+  const double* rc = a.rhs_c + b * a.ldrc;
+
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  v2d pa[NPL], pf[NP], pv[NP], pe[NP], pm[NPL];
+  double pvec[4 + 3 * NU], psc = 0.0;
+  auto load_mat = [&](v2d (&r)[NP], const double* src) {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < MAT / 2) r[k] = s2[i];
+    }
+  };
+  auto store_mat = [&](double* dst, const v2d (&r)[NP]) {
+    v2d* d2 = reinterpret_cast<v2d*>(dst);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < MAT / 2) d2[i] = r[k];
+    }
+  };
+  auto load_l = [&](v2d (&r)[NPL], const double* src) {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) r[k] = s2[tid + k * WG];
+  };
+  auto store_l = [&](double* dst, const v2d (&r)[NPL]) {
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) { const int e = ltile_elem<N>(tid + k * WG); dst[e] = r[k].x; dst[e + 1] = r[k].y; }
+  };
+  auto issue = [&](int t) {
+    const double* fac = facb + (int64_t)t * D::FAC;
+    const double* fv = fac + D::F_VEC;
+    load_l(pa, fac + D::F_LA);
+    load_mat(pf, fac + D::F_FT);
+    load_mat(pv, fac + D::F_VT);
+    load_mat(pe, fac + D::F_ET);
+    if (tid < N) {
+      pvec[0] = fv[D::V_DA + tid]; pvec[1] = fv[D::V_DM + tid];
+      pvec[2] = rx[a.zoff[t] + tid]; pvec[3] = rc[a.cdoff[t] + tid];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        pvec[4 + 3 * j] = fv[D::V_AU + j * N + tid]; pvec[5 + 3 * j] = fv[D::V_FU + j * N + tid]; pvec[6 + 3 * j] = fv[D::V_VU + j * N + tid];
+      }
+    } else if (tid < N + 32) {
+      const int q = tid - N;
+      psc = q < NSC ? fv[D::V_SC + q] : 0.0;
+    } else if (tid < N + 32 + NU) {
+      psc = rx[a.zoff[t] + N + (tid - N - 32)];
+    }
+  };
+  // the upper tiles of MA are zeroed once and never written (the triangular factors arrive as their lower tiles)
+  for (int i = tid; i < MAT; i += WG) MA[i] = 0.0;
+  if (tid < N) byc[tid] = 0.0;
+  if (PRE && a.T > 1) { issue(0); load_l(pm, facb + D::F_LM); }
+  for (int t = 0; t < a.T - 1; ++t) {
+    double* fac = facb + (int64_t)t * D::FAC;
+    if (!PRE) { issue(t); load_l(pm, fac + D::F_LM); }
+    __syncthreads();
+    store_l(MA, pa);
+    store_mat(MF, pf);
+    store_mat(MV, pv);
+    store_mat(ME, pe);
+    if (tid < N) {
+      dAi[tid] = pvec[0]; dMi[tid] = pvec[1]; bx[tid] = pvec[2] + byc[tid]; bd[tid] = pvec[3];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) { au[j * N + tid] = pvec[4 + 3 * j]; fu[j * N + tid] = pvec[5 + 3 * j]; vu[j * N + tid] = pvec[6 + 3 * j]; }
+    } else if (tid < N + 32) {
+      scv[tid - N] = psc;
+    } else if (tid < N + 32 + NU) {
+      ruv[tid - N - 32] = psc;
+    }
+    __syncthreads();
+    if (PRE && t + 1 < a.T - 1) issue(t + 1);
+    // ---- eliminate u: bu^ = L_u^-1 ru (every lane of wavefront 0 for itself, NU <= 4), its terms in bx, bd and by; bx~ = L_A^-1 bx
+    if (w == 0) {
+      double bu[NU];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) bu[j] = ruv[j];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+#pragma unroll
+        for (int k = j + 1; k < NU; ++k) bu[k] -= scv[2 * NU + k * NU + j] * bu[j];
+      }
+      double sx = 0.0, sd = 0.0, sy = 0.0, mine = bu[0];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        const double bj = bu[j] * scv[j];
+        sx += au[j * N + l] * bj; sd += fu[j * N + l] * bj; sy += vu[j * N + l] * bj;
+        mine = (l == j) ? bu[j] : mine;
+      }
+      if (l < NU) fac[D::F_VEC + D::V_SC + NU + l] = mine;
+      bx[l] -= sx;
+      bd[l] -= sd;
+      byn[l] = -sy;
+      trsv_lower<N>(MA, bx);
+      fac[D::F_VEC + D::V_BX + l] = bx[l];
+    }
+    __syncthreads();
+    // ---- bd~ = bd - F~ D_A^-1 bx~
+    {
+      const double part = quad_sum(dotq_rs<N>(MF, LD, bx, dAi));
+      if ((tid & 3) == 0) bd[tid >> 2] -= part;
+    }
+    store_l(MA, pm);   // L_A is done with (the trsv above ended at the last barrier)
+    if (PRE && t + 1 < a.T - 1) load_l(pm, facb + (int64_t)(t + 1) * D::FAC + D::F_LM);
+    __syncthreads();
+    // ---- bd^ = L_M^-1 bd~
+    if (w == 0) {
+      trsv_lower<N>(MA, bd);
+      fac[D::F_VEC + D::V_BD + l] = bd[l];
+    }
+    __syncthreads();
+    // ---- carried right-hand side: by = byn - V~' D_A^-1 bx~ + E~' D_M^-1 bd^
+    {
+      const double part = quad_sum(dotq_cs<N>(ME, LD, bd, dMi) - dotq_cs<N>(MV, LD, bx, dAi));
+      if ((tid & 3) == 0) byc[tid >> 2] = byn[tid >> 2] + part;
+    }
+  }
+  // ---- terminal block: x_T = L_A^-T D_A^-1 L_A^-1 (rx_T + by), where k_wide_bwd picks it up
+  {
+    const int t = a.T - 1;
+    const double* facT = facb + (int64_t)t * D::FAC;
+    __syncthreads();
+    load_l(pa, facT + D::F_LA);
+    store_l(MA, pa);
+    if (tid < N) {
+      dAi[tid] = facT[D::F_VEC + D::V_DA + tid];
+      bx[tid] = rx[a.zoff[t] + tid] + byc[tid];
+    }
+    __syncthreads();
+    if (w == 0) {
+      trsv_lower<N>(MA, bx);
+      bx[l] *= dAi[l];
+      trsv_lower_t<N>(MA, bx);
+      a.dz[b * a.lddz + a.zoff[t] + l] = bx[l];
+    }
+  }
 }
 
 // one wavefront per instance: out[b] = sum_t rows[b][t] in a fixed order (lane-strided partials, then a tree)
@@ -2344,9 +2557,29 @@ int launch_wide(int op, const dto_wide_args* a, void* stream) {
     hipLaunchKernelGGL(k_wide_merit<M>, dim3((unsigned)a->B), dim3(WG), lds, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
   }
-  if (op != DTO_WIDE_STEP) return (int)hipErrorInvalidValue;
   dto_wide_info info;
   wide_info<M>(&info);
+#if DTO_WIDE_SPLIT_BWD && DTO_WIDE_PACK_L
+  if (op == DTO_WIDE_FACTOR) {
+    // the linear solver alone: one sweep, factors (terminal block included) to the records, nothing solved
+    hipError_t ef = hipFuncSetAttribute((const void*)k_wide_step<M, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, info.lds_bytes);
+    if (ef != hipSuccess) return (int)ef;
+    hipLaunchKernelGGL((k_wide_step<M, false, true>), dim3((unsigned)a->B), dim3(WG), info.lds_bytes, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+  }
+  if (op == DTO_WIDE_SOLVE) {
+    // substitution only: forward over the stored records with the caller's right-hand side, then the backward sweep of the step
+    constexpr bool PRE = DTO_WIDE_FSUB_PREFETCH != 0;
+    hipError_t es = hipFuncSetAttribute((const void*)k_wide_fsub<M, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<M>::BYTES);
+    if (es != hipSuccess) return (int)es;
+    hipLaunchKernelGGL((k_wide_fsub<M, PRE>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
+    es = hipFuncSetAttribute((const void*)k_wide_bwd<M, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<M>::BYTES);
+    if (es != hipSuccess) return (int)es;
+    hipLaunchKernelGGL((k_wide_bwd<M, false>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
+    return (int)hipGetLastError();
+  }
+#endif
+  if (op != DTO_WIDE_STEP) return (int)hipErrorInvalidValue;
   if (a->zl) {
     hipError_t eb = hipFuncSetAttribute((const void*)k_wide_step<M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, info.lds_bytes);
     if (eb != hipSuccess) return (int)eb;

@@ -750,6 +750,12 @@ class Solver:
     # ---- the linear solver alone (include/dto.h: dto_kkt_assemble / dto_kkt_factor / dto_kkt_solve)
     def kkt_assemble(self, x_ptr, B, ldx, mu_ptr, ldmu, delta_w, delta_c, sigma_x_ptr=0, ldsx=0, sigma_c_ptr=0, ldsc=0, stream=0,
                      params_ptr=0, ldp=0):
+        """The linear solver alone (include/dto.h: dto_kkt_assemble): the system at (x, mu) with sigma_x / sigma_c and delta_w /
+        delta_c on the diagonals.  Device pointers in the SOLVER's layout: a 17 .. 63-state problem that was embedded in the 64
+        states of the tile kernels passes pad_batch(...) arrays of _solve_nlp.num_variables / num_constraint entries (sigma_x of
+        the padding states: anything >= 0) and maps solutions back with unpad_batch.  On the tile path the factor is stored by
+        kkt_factor and kkt_solve is substitution only; kkt_step_batch or a solve on the same Solver invalidates the stored
+        factor (kkt_solve then raises until kkt_factor is called again)."""
         b = self._solve_nlp._batch(x_ptr, B, ldx, stream, params_ptr, ldp)
         sysd = capi.KktSystem()
         sysd.mu, sysd.ldmu = mu_ptr, ldmu
@@ -767,6 +773,7 @@ class Solver:
         return ok, neg
 
     def kkt_solve(self, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, sol_x_ptr, ldsx, sol_c_ptr, ldsc, stream=0):
+        """K^-1 [rhs_x; rhs_c] for the system factorised last, one right-hand side per call (solver layout, see kkt_assemble)."""
         capi.check(self._solve_nlp._lib.dto_kkt_solve(self._solve_nlp._h, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, sol_x_ptr, ldsx,
                                                       sol_c_ptr, ldsc, stream or None))
 

@@ -231,8 +231,19 @@ int dto_kkt_step_batch(dto_problem* p, const dto_batch* b, const double* mu, int
  *  terms enter through sigma_x / sigma_c.  DEVICE pointers, instance-major.  dto_kkt_assemble packs the point and the
  *  diagonals; dto_kkt_factor runs the block-tridiagonal LDL^T once and reports the inertia (HOST arrays [B], may be NULL:
  *  inertia_ok[i] = the matrix has exactly num_constraint negative and no tiny pivots; num_negative[i] = negative pivots);
- *  dto_kkt_solve solves for one right-hand side.  The factors are not stored between calls (the sweeps recompute each
- *  stage's LDL^T -- cheaper than the HBM traffic on this hardware), so every dto_kkt_solve costs a forward + backward sweep. */
+ *  dto_kkt_solve solves for one right-hand side, any number of times per factorisation.  What a solve costs depends on the path:
+ *  - lane-per-instance path (states <= 16): the factors are NOT stored between calls -- the sweeps recompute each stage's
+ *    LDL^T, which is cheaper than the HBM traffic on this hardware -- so every dto_kkt_solve costs a forward + backward sweep;
+ *  - tile (MFMA) path (64-state models, and 17 .. 63-state problems in their 64-state embedding): dto_kkt_factor STORES the
+ *    factor, about 170 KB per stage and instance (B x T x 145 024 bytes with one action; dto_kkt_assemble allocates it and
+ *    reports the size if that fails), and dto_kkt_solve is substitution only: one forward and one backward pass over the
+ *    stored records, no O(n^3) work.  The storage is shared with dto_kkt_step_batch and the solver entry points of the same
+ *    handle: any of them invalidates the stored factor, and dto_kkt_solve then fails with DTO_ERR_INVALID until
+ *    dto_kkt_factor is called again (the assembled system is kept).  dto_kkt_assemble copies the point, the multipliers, the
+ *    diagonals and the batch's parameters, so the caller's arrays may change after it returns.
+ *  Order: assemble, factor, solve; dto_kkt_factor before dto_kkt_assemble and dto_kkt_solve before dto_kkt_factor fail with
+ *  DTO_ERR_INVALID.  The single factorisation attempt is swept to the end whatever its inertia: dto_kkt_solve returns
+ *  K^-1 rhs (unpivoted) also when inertia_ok is 0. */
 typedef struct dto_kkt_system {
   const double* mu;      int64_t ldmu;   /* [B][ldmu] multipliers inside W */
   const double* sigma_x; int64_t ldsx;   /* [B][ldsx] >= 0, or NULL */

@@ -3,6 +3,8 @@ register use and spills, and optionally the whole text -- to check that an edit 
 kernels' code generation alone (what decides k_kkt_fwd_seq's speed is where its spills land).
 
     python tools/isa_of_plugin.py acrobot [out.s]      # summary on stdout
+    python tools/isa_of_plugin.py acrobot_padded       # a tile-path plugin (csrc/dto_wide_kernels.hpp): its flags, one line per
+                                                       # instantiation (k_wide_step<M, BAR, LIN>: ...Lb0ELb0E, Lb1ELb0E, Lb0ELb1E)
 """
 import os
 import re
@@ -23,7 +25,9 @@ def kernel_stats(isa):
             cur = m.group(1)
             out[cur] = dict(instructions=0, scratch=0, readlane=0, hash=0)
             continue
-        if cur and ln.startswith("\t") and not ln.startswith("\t.") and not ln.startswith("\t;"):
+        # (instructions only: assembler directives -- .amdhsa_kernarg_size moves when a field is appended to the argument struct --
+        #  and comments stay out of the count and of the checksum)
+        if cur and ln.startswith("\t") and not ln.lstrip().startswith((".", ";")):
             out[cur]["instructions"] += 1
             # (labels are numbered per function index in the file: normalised, so that the checksum only moves with the code)
             out[cur]["hash"] = zlib.crc32(re.sub(r"\.LBB\d+_", ".LBB_", ln.strip()).encode(), out[cur]["hash"])
@@ -50,7 +54,7 @@ def main():
     path = os.path.join(PL.PLUGIN_DIR, f"_isa_{model}.hip")
     with open(path, "w") as f:
         f.write(src)
-    isa = C.compile_to_isa(path, PL.BASE_CXXFLAGS + PL._extra_flags())
+    isa = C.compile_to_isa(path, PL.BASE_CXXFLAGS + (PL.WIDE_CXXFLAGS if st.wide else []) + PL._extra_flags())
     os.remove(path)
     if len(sys.argv) > 2:
         with open(sys.argv[2], "w") as f:
@@ -63,7 +67,8 @@ def main():
     for k in sorted(ks):
         if ks[k]["instructions"] < 50:
             continue
-        short = re.sub(r"^_ZN?3dto\d*|I\d+.*$", "", k)[:40]
+        # (tile-path kernels are templates over the anonymous Model class: keep the flags behind it, they tell the instantiations apart)
+        short = re.sub(r"^_ZN?3dto\d*|I\d+.*$|v\d+dto_\w+_args$", "", k.replace("N12_GLOBAL__N_15ModelE", "M"))[:40]
         print(f"{short:40s} instr {ks[k]['instructions']:6d} scratch {ks[k]['scratch']:4d} lane-ops {ks[k]['readlane']:5d} hash {ks[k]['hash']:08x} {meta.get(k, '')}")
 
 
