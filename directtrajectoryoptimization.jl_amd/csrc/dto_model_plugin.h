@@ -13,7 +13,7 @@
 
 #include <stdint.h>
 
-#define DTO_PLUGIN_ABI 7
+#define DTO_PLUGIN_ABI 8
 
 #ifdef __cplusplus
 extern "C" {

@@ -244,11 +244,13 @@ struct WideKkt {
   size_t cap_z = 0, cap_mu = 0, cap_params = 0, cap_sigx = 0, cap_sigc = 0;   // doubles allocated
   int* flags = nullptr;   // [2][B]: inertia flags, negative-pivot counts
   size_t cap_flags = 0;
+  double* ws = nullptr;   // [B][T][multi_ws_stage]: intermediates of one block of right-hand sides (dto_kkt_solve_multi), allocated by
+  size_t cap_ws = 0;      // the first multi-solve
   void release() {
-    for (void* q : {(void*)z, (void*)mu, (void*)params, (void*)sigx, (void*)sigc, (void*)flags})
+    for (void* q : {(void*)z, (void*)mu, (void*)params, (void*)sigx, (void*)sigc, (void*)flags, (void*)ws})
       if (q) (void)hipFree(q);
-    z = mu = params = sigx = sigc = nullptr; flags = nullptr;
-    cap_z = cap_mu = cap_params = cap_sigx = cap_sigc = cap_flags = 0;
+    z = mu = params = sigx = sigc = ws = nullptr; flags = nullptr;
+    cap_z = cap_mu = cap_params = cap_sigx = cap_sigc = cap_flags = cap_ws = 0;
     B = 0; assembled = factored = false;
   }
 };
@@ -262,6 +264,7 @@ static inline void wide_fac_taken(Problem* p) {
 static inline void wide_args_no_linear(dto_wide_args& a) {
   a.sigma_x = a.sigma_c = nullptr; a.ldsx = a.ldsc = 0; a.nneg = nullptr;
   a.rhs_x = a.rhs_c = nullptr; a.ldrx = a.ldrc = 0;
+  a.nrhs = a.rhs0 = 0; a.ws = nullptr;
 }
 
 // ---- wide-stage models (dto_wide_kernels.hpp): one workgroup per instance, AoS buffers used as they are
@@ -431,6 +434,41 @@ static int wide_kkt_solve(Problem* p, const double* rhs_x, int64_t ldrx, const d
   a.dz = sol_x; a.lddz = ldsx; a.dmu = sol_c; a.lddmu = ldsc;
   const int lrc = p->vt->launch_wide(DTO_WIDE_SOLVE, &a, (void*)st);
   if (lrc != 0) return hip_fail((hipError_t)lrc, "wide solve launch");
+  return DTO_OK;
+}
+// nrhs right-hand sides per instance (row b * nrhs + r of every array) in blocks of multi_r columns on the stream: a block reads
+// every record once on the way forward and once on the way back.  The records are only read, the intermediates of a block live
+// in K.ws, so single and multi solves may follow one another on one factorisation.
+static int wide_kkt_solve_multi(Problem* p, int64_t nrhs, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
+                                double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, hipStream_t st) {
+  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  WideKkt& K = *p->wide_kkt;
+  if (!K.factored)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_factor has not been called (or dto_kkt_step_batch / the solver has used the factor storage since)");
+  dto_wide_info info;
+  p->vt->wide_info(&info);
+  if (info.multi_r < 1) return set_error(DTO_ERR_UNSUPPORTED, "this plugin was built without the panel substitution kernels");
+  const size_t need = (size_t)K.B * (size_t)p->L.T * (size_t)info.multi_ws_stage;
+  if (K.cap_ws < need) {
+    if (K.ws) (void)hipFree(K.ws);
+    K.ws = nullptr; K.cap_ws = 0;
+    hipError_t e = hipMalloc((void**)&K.ws, need * sizeof(double));
+    if (e != hipSuccess)
+      return hip_fail(e, ("dto_kkt_solve_multi: hipMalloc of the workspace (" + std::to_string(need * sizeof(double)) + " bytes: " +
+                          std::to_string(K.B) + " instances x " + std::to_string(p->L.T) + " knots x " +
+                          std::to_string(info.multi_ws_stage * (int64_t)sizeof(double)) + " bytes)").c_str());
+    K.cap_ws = need;
+  }
+  dto_wide_args a;
+  wide_kkt_args(p, a);
+  a.rhs_x = rhs_x; a.ldrx = ldrx; a.rhs_c = rhs_c; a.ldrc = ldrc;
+  a.dz = sol_x; a.lddz = ldsx; a.dmu = sol_c; a.lddmu = ldsc;
+  a.nrhs = nrhs; a.ws = K.ws;
+  for (int64_t r0 = 0; r0 < nrhs; r0 += info.multi_r) {
+    a.rhs0 = r0;
+    const int lrc = p->vt->launch_wide(DTO_WIDE_SOLVE_MULTI, &a, (void*)st);
+    if (lrc != 0) return hip_fail((hipError_t)lrc, "wide multi-solve launch");
+  }
   return DTO_OK;
 }
 
@@ -3710,6 +3748,29 @@ int dto_kkt_solve(dto_problem* h, const double* rhs_x, int64_t ldrx, const doubl
   if ((rc = dto::kkt_launch(p, DTO_KKT_BWD, a, st))) return rc;
   if ((rc = dto::unpack(p, a, 2, sol_x, ldsx, st))) return rc;
   if (p->L.Nc > 0 && (rc = dto::unpack(p, a, 3, sol_c, ldsc, st))) return rc;
+  return DTO_OK;
+}
+
+int dto_kkt_solve_multi(dto_problem* h, int64_t nrhs, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
+                        double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();   // (allocates the tables of the handle once, launches nothing)
+  if (rc) return rc;
+  const bool wide = p->vt->launch_wide != nullptr;
+  if (wide ? !p->wide_kkt || !p->wide_kkt->assembled : !p->solver || !p->solver->assembled)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (nrhs < 1) return set_error(DTO_ERR_INVALID, "nrhs < 1");
+  if (!rhs_x || !sol_x || (p->L.Nc > 0 && (!rhs_c || !sol_c))) return set_error(DTO_ERR_INVALID, "null argument");
+  if (ldrx < p->L.Nz || ldsx < p->L.Nz || ldrc < p->L.Nc || ldsc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (wide) return dto::wide_kkt_solve_multi(p, nrhs, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, (hipStream_t)stream);
+  // lane-per-instance path: no stored factor, so nrhs passes of the single solve -- right-hand side r of every instance is a
+  // batch of its own with the rows nrhs apart
+  for (int64_t r = 0; r < nrhs; ++r) {
+    rc = dto_kkt_solve(h, rhs_x + r * ldrx, nrhs * ldrx, rhs_c ? rhs_c + r * ldrc : nullptr, nrhs * ldrc, sol_x + r * ldsx, nrhs * ldsx,
+                       sol_c ? sol_c + r * ldsc : nullptr, nrhs * ldsc, stream);
+    if (rc) return rc;
+  }
   return DTO_OK;
 }
 

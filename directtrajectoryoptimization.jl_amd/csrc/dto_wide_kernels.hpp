@@ -24,14 +24,17 @@
 #include "dto_model_plugin.h"
 
 // DTO_WIDE_FACTOR / DTO_WIDE_SOLVE: the linear solver alone (dto_kkt_factor / dto_kkt_solve): factor once, then any number of
-// substitution-only solves against the stored records
-enum dto_wide_op { DTO_WIDE_STEP = 0, DTO_WIDE_MERIT = 1, DTO_WIDE_FACTOR = 2, DTO_WIDE_SOLVE = 3 };
+// substitution-only solves against the stored records.  DTO_WIDE_SOLVE_MULTI (dto_kkt_solve_multi): one block of up to
+// dto_wide_info::multi_r right-hand sides per launch, carried as 64 x R panels through the same records, which are only read
+enum dto_wide_op { DTO_WIDE_STEP = 0, DTO_WIDE_MERIT = 1, DTO_WIDE_FACTOR = 2, DTO_WIDE_SOLVE = 3, DTO_WIDE_SOLVE_MULTI = 4 };
 
 struct dto_wide_info {
   int supported;
   int n, nu;
   int64_t fac_stage;  // doubles of factor storage per stage and instance
   int lds_bytes;
+  int multi_r;             // right-hand sides per launch of DTO_WIDE_SOLVE_MULTI (0: not built)
+  int64_t multi_ws_stage;  // doubles of workspace per stage and instance for one such block
 };
 
 struct dto_wide_args {
@@ -71,6 +74,10 @@ struct dto_wide_args {
   int* nneg;                            // [B] number of negative pivots (DTO_WIDE_FACTOR)
   const double* rhs_x; int64_t ldrx;    // [B][ldrx] right-hand side of the variables, problem layout (DTO_WIDE_SOLVE)
   const double* rhs_c; int64_t ldrc;    // [B][ldrc] right-hand side of the constraint rows
+  // ---- a block of right-hand sides against the stored records (DTO_WIDE_SOLVE_MULTI); NULL / 0 everywhere else.  Right-hand
+  //      side r of instance b is row b * nrhs + r of rhs_x / rhs_c / dz / dmu; this launch takes r = rhs0 .. rhs0 + multi_r - 1
+  int64_t nrhs, rhs0;
+  double* ws;                           // [B][T][multi_ws_stage] intermediates of one block (bx~, bd^, bu^ panels)
 };
 // stats: 0 f (barrier terms excluded), 1 theta_1, 2 theta_inf, 3 dual infeasibility, 4 grad phi' dz, 5 sum |lam|, 6/7 scratch,
 // 8 alpha_pmax, 9 alpha_dmax, 10 max s z, 11 max 1 / (s z), 12 sum z, 13 sum log s  (8..13 only with bounds)
@@ -2137,6 +2144,534 @@ __global__ __launch_bounds__(WG) void k_wide_fsub(dto_wide_args a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// A block of R right-hand sides against the stored records (DTO_WIDE_SOLVE_MULTI, dto_kkt_solve_multi): the algebra of
+// k_wide_fsub and of the loop of k_wide_bwd<M, false> with the vectors replaced by 64 x R panels in LDS, so that a record is
+// read once per block instead of once per right-hand side.  Products with F~, V~, E~ and their transposes are MFMA tile
+// products with the panel as the B operand (wavefront w owns rows 16 w .. 16 w + 15 of the result); L_A^-1, L_M^-1 and their
+// transposes are blocked substitutions over the ten packed lower tiles, which stay tile-major in LDS as they are in the record
+// (20 KB; three full matrices and three panels then fit beside them): off-diagonal tiles through MFMA, the four unit-lower
+// diagonal tiles substituted in-wave with one lane per column.  The action block stays scalar per column.
+// The records are ONLY READ: bx~, bd^ and bu^ of the block go to a workspace [B][T][R (2 N + NU)] instead of the records' own
+// slots, so dto_kkt_solve and dto_kkt_solve_multi may be mixed on one factorisation.  Columns past nrhs in the last block are
+// zero on the way in and never written out.  Needs the zeros that ldl_rank1 leaves on and above the diagonals of the
+// diagonal tiles.  grid = B, block = 256; the record of the next stage travels into registers as in the single-vector kernels.
+// ---------------------------------------------------------------------------------------------------
+#ifndef DTO_WIDE_MULTI_R
+#define DTO_WIDE_MULTI_R 16
+#endif
+template <class M, int R>
+struct MultiLds {
+  static constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
+  static_assert(R == TB, "a panel is one MFMA tile of columns (R = 8 would leave half of every tile product idle)");
+  static constexpr int PLD = R + 1;                        // row stride of a panel (odd: row and column walks both spread over the banks)
+  static constexpr int PAN = N * PLD;
+  static constexpr int LT = Dims<N>::LTILES * TB * TB;     // a triangular factor as its packed lower tiles
+  static constexpr int DOUBLES = LT + 3 * Dims<N>::MAT + 3 * PAN + (3 * NU + 2) * N + 32 + NU * R;
+  static constexpr int BYTES = DOUBLES * (int)sizeof(double);
+  static constexpr int WS = R * (2 * N + NU);              // workspace doubles per stage and instance
+  static_assert(BYTES <= 160 * 1024, "wide path: the panels of a multi-solve do not fit the 160 KB of LDS of one workgroup");
+};
+
+// X <- L^-1 X for the 16 rows at X against the unit-lower diagonal tile Lt (zeros on and above its diagonal), one wavefront:
+// lane c < 16 holds column c in registers, the tile's entries are broadcast reads
+template <int PLD>
+__device__ __forceinline__ void panel_diag_lower(const double* Lt, double* X) {
+  const int c = lane_id();
+  if (c < TB) {
+    double x[TB];
+#pragma unroll
+    for (int i = 0; i < TB; ++i) x[i] = X[i * PLD + c];
+#pragma unroll
+    for (int j = 0; j < TB - 1; ++j) {
+#pragma unroll
+      for (int i = j + 1; i < TB; ++i) x[i] = __builtin_fma(-Lt[i * TB + j], x[j], x[i]);
+    }
+#pragma unroll
+    for (int i = 1; i < TB; ++i) X[i * PLD + c] = x[i];
+  }
+}
+// X <- L^-T X, the same way
+template <int PLD>
+__device__ __forceinline__ void panel_diag_upper(const double* Lt, double* X) {
+  const int c = lane_id();
+  if (c < TB) {
+    double x[TB];
+#pragma unroll
+    for (int i = 0; i < TB; ++i) x[i] = X[i * PLD + c];
+#pragma unroll
+    for (int j = TB - 1; j >= 1; --j) {
+#pragma unroll
+      for (int i = 0; i < j; ++i) x[i] = __builtin_fma(-Lt[j * TB + i], x[j], x[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < TB - 1; ++i) X[i * PLD + c] = x[i];
+  }
+}
+// X <- L^-1 X for a 64 x 16 panel, L as packed lower tiles (tile (ib, jb) at LT + (ib (ib + 1) / 2 + jb) 256), one wavefront
+template <int N, int PLD>
+__device__ __forceinline__ void panel_trsm_lower(const double* LT, double* X) {
+  static_assert(N == 64, "four tiles per edge");
+  const int r = lane_id() & 15, q = lane_id() >> 4;
+  auto blk = [&](auto ibc) {
+    constexpr int ib = decltype(ibc)::value;
+    constexpr int row0 = ib * (ib + 1) / 2;                // first tile of tile-row ib: its off-diagonal tiles follow one another
+    if constexpr (ib > 0) {
+      d4 c = tile_load(X, PLD, ib * TB, 0);
+      const double* lr = LT + row0 * TB * TB + r * TB + q;   // A operand: L[ib rows][k], k-step st in tile st >> 2
+      const double* xc = X + q * PLD + r;                    // B operand: X[k][columns]
+      c = mm_steps<4 * ib>(c, [&](int st) { return -lr[(st >> 2) * TB * TB + 4 * (st & 3)]; }, [&](int st) { return xc[4 * st * PLD]; });
+      tile_store(X, PLD, ib * TB, 0, c);
+      wave_lds_fence();
+    }
+    panel_diag_lower<PLD>(LT + (row0 + ib) * TB * TB, X + ib * TB * PLD);
+    wave_lds_fence();
+  };
+  blk(std::integral_constant<int, 0>{});
+  blk(std::integral_constant<int, 1>{});
+  blk(std::integral_constant<int, 2>{});
+  blk(std::integral_constant<int, 3>{});
+}
+// X <- L^-T X
+template <int N, int PLD>
+__device__ __forceinline__ void panel_trsm_upper(const double* LT, double* X) {
+  static_assert(N == 64, "four tiles per edge");
+  const int r = lane_id() & 15, q = lane_id() >> 4;
+  auto blk = [&](auto ibc) {
+    constexpr int ib = decltype(ibc)::value;
+    if constexpr (ib < 3) {
+      d4 c = tile_load(X, PLD, ib * TB, 0);
+      // A operand: (L[jb rows][ib columns])' for jb = ib + 1 .. 3, k-step st in tile jb = ib + 1 + (st >> 2)
+      const double* lc = LT + q * TB + r;
+      const double* xc = X + ((ib + 1) * TB + q) * PLD + r;
+      c = mm_steps<4 * (3 - ib)>(c,
+                                 [&](int st) { const int jb = ib + 1 + (st >> 2); return -lc[(jb * (jb + 1) / 2 + ib) * TB * TB + 4 * (st & 3) * TB]; },
+                                 [&](int st) { return xc[4 * st * PLD]; });
+      tile_store(X, PLD, ib * TB, 0, c);
+      wave_lds_fence();
+    }
+    panel_diag_upper<PLD>(LT + (ib * (ib + 1) / 2 + ib) * TB * TB, X + ib * TB * PLD);
+    wave_lds_fence();
+  };
+  blk(std::integral_constant<int, 3>{});
+  blk(std::integral_constant<int, 2>{});
+  blk(std::integral_constant<int, 1>{});
+  blk(std::integral_constant<int, 0>{});
+}
+
+// forward panel substitution: per stage what k_wide_fsub does, R columns at a time
+template <class M, int R>
+__global__ __launch_bounds__(WG) void k_wide_fsub_multi(dto_wide_args a) {
+  constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
+  static_assert(N == 64, "wide path is built for 64 states");
+  static_assert(NU >= 1 && NU <= 4, "wide path: one to four actions per stage");
+  static_assert(DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD && DTO_WIDE_LDL_RANK1, "reads packed triangular factors with clean diagonal tiles");
+  using D = Dims<N, NU>;
+  using ML = MultiLds<M, R>;
+  constexpr int LD = D::LD, MAT = D::MAT, PLD = ML::PLD, PAN = ML::PAN;
+  constexpr int NP = (MAT / 2 + WG - 1) / WG;            // 16-byte pieces of one matrix per thread
+  constexpr int NPL = ML::LT / 2 / WG;                   // pieces of a triangular factor
+  constexpr int NSC = (NU * (NU + 2) + 7) & ~7;          // scalars of the action block in the record
+  constexpr int CPT = R / 4;                             // panel entries per thread
+  static_assert(NSC <= 32 && NU * R <= N && NPL * WG * 2 == ML::LT, "thread maps of the small pieces");
+  extern __shared__ double sm[];
+  double* LT = sm;             // L_A, then L_M: packed lower tiles
+  double* MF = LT + ML::LT;
+  double* MV = MF + MAT;
+  double* ME = MV + MAT;
+  double* BX = ME + MAT;       // panels [N][PLD]
+  double* BD = BX + PAN;
+  double* BY = BD + PAN;       // carried right-hand side into the next stage
+  double* au = BY + PAN;
+  double* fu = au + NU * N;
+  double* vu = fu + NU * N;
+  double* dAi = vu + NU * N;
+  double* dMi = dAi + N;
+  double* scv = dMi + N;       // [32] scalars of the action block: 1 / pivot [NU], (unused [NU]), L_u [NU][NU]
+  double* ruv = scv + 32;      // [NU][R] right-hand sides of the actions
+  const int tid = threadIdx.x, w = wave_id(), l = lane_id();
+  const int r = l & 15, q = l >> 4;
+  const int64_t b = blockIdx.x;
+  if (a.active && !a.active[b]) return;
+  const double* facb = a.fac + b * (int64_t)a.T * D::FAC;
+  double* wsb = a.ws + b * (int64_t)a.T * ML::WS;
+  const int ncol = (int)((a.nrhs - a.rhs0 < R) ? a.nrhs - a.rhs0 : R);
+  const int64_t row0 = b * a.nrhs + a.rhs0;              // row of column 0 in the caller's arrays
+  const int grow = tid & 63, gc = tid >> 6;              // caller's arrays <-> panels: lanes along a row of the caller (coalesced), columns gc + 4 k
+  const int pc = tid & 15, pr = tid >> 4;                // panels <-> workspace: entry (pr + 16 k, pc) = linear index tid + 256 k
+
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  v2d pa[NPL], pf[NP], pv[NP], pe[NP], pm[NPL];
+  double pvec[2 + 3 * NU], psc = 0.0, prx[CPT], prc[CPT], pru = 0.0;
+  auto load_mat = [&](v2d (&rg)[NP], const double* src) {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < MAT / 2) rg[k] = s2[i];
+    }
+  };
+  auto store_mat = [&](double* dst, const v2d (&rg)[NP]) {
+    v2d* d2 = reinterpret_cast<v2d*>(dst);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < MAT / 2) d2[i] = rg[k];
+    }
+  };
+  auto load_l = [&](v2d (&rg)[NPL], const double* src) {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) rg[k] = s2[tid + k * WG];
+  };
+  auto store_l = [&](const v2d (&rg)[NPL]) {
+    v2d* d2 = reinterpret_cast<v2d*>(LT);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) d2[tid + k * WG] = rg[k];
+  };
+  auto issue = [&](int t) {
+    const double* fac = facb + (int64_t)t * D::FAC;
+    const double* fv = fac + D::F_VEC;
+    load_l(pa, fac + D::F_LA);
+    load_mat(pf, fac + D::F_FT);
+    load_mat(pv, fac + D::F_VT);
+    load_mat(pe, fac + D::F_ET);
+    const int zo = a.zoff[t], co = a.cdoff[t];
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+      const int c = gc + 4 * k;
+      prx[k] = c < ncol ? a.rhs_x[(row0 + c) * a.ldrx + zo + grow] : 0.0;
+      prc[k] = c < ncol ? a.rhs_c[(row0 + c) * a.ldrc + co + grow] : 0.0;
+    }
+    if (tid < NU * R) { const int c = tid % R; pru = c < ncol ? a.rhs_x[(row0 + c) * a.ldrx + zo + N + tid / R] : 0.0; }
+    if (tid < N) {
+      pvec[0] = fv[D::V_DA + tid]; pvec[1] = fv[D::V_DM + tid];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        pvec[2 + 3 * j] = fv[D::V_AU + j * N + tid]; pvec[3 + 3 * j] = fv[D::V_FU + j * N + tid]; pvec[4 + 3 * j] = fv[D::V_VU + j * N + tid];
+      }
+    } else if (tid < N + 32) {
+      const int s = tid - N;
+      psc = s < NSC ? fv[D::V_SC + s] : 0.0;
+    }
+  };
+  for (int i = tid; i < PAN; i += WG) BY[i] = 0.0;
+  if (a.T > 1) { issue(0); load_l(pm, facb + D::F_LM); }
+  for (int t = 0; t < a.T - 1; ++t) {
+    double* wst = wsb + (int64_t)t * ML::WS;
+    __syncthreads();
+    store_l(pa);
+    store_mat(MF, pf);
+    store_mat(MV, pv);
+    store_mat(ME, pe);
+    if (tid < N) {
+      dAi[tid] = pvec[0]; dMi[tid] = pvec[1];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) { au[j * N + tid] = pvec[2 + 3 * j]; fu[j * N + tid] = pvec[3 + 3 * j]; vu[j * N + tid] = pvec[4 + 3 * j]; }
+    } else if (tid < N + 32) {
+      scv[tid - N] = psc;
+    }
+    if (tid < NU * R) ruv[tid] = pru;
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+      const int e = grow * PLD + gc + 4 * k;
+      BX[e] = prx[k] + BY[e];
+      BD[e] = prc[k];
+    }
+    __syncthreads();
+    if (t + 1 < a.T - 1) issue(t + 1);
+    // ---- eliminate u, column pc: bu^ = L_u^-1 ru, its terms in bx and bd (those in by: the start of its tile product below)
+    double bs[NU];
+    {
+      double bu[NU];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) bu[j] = ruv[j * R + pc];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+#pragma unroll
+        for (int k = j + 1; k < NU; ++k) bu[k] -= scv[2 * NU + k * NU + j] * bu[j];
+      }
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        if (pr == 0) wst[2 * N * R + j * R + pc] = bu[j];
+        bs[j] = bu[j] * scv[j];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+      const int row = pr + 16 * k;
+      double sx = 0.0, sd = 0.0;
+#pragma unroll
+      for (int j = 0; j < NU; ++j) { sx += au[j * N + row] * bs[j]; sd += fu[j * N + row] * bs[j]; }
+      BX[row * PLD + pc] -= sx;
+      BD[row * PLD + pc] -= sd;
+    }
+    __syncthreads();
+    // ---- bx~ = L_A^-1 bx
+    if (w == 0) panel_trsm_lower<N, PLD>(LT, BX);
+    __syncthreads();
+    // ---- bd~ = bd - F~ D_A^-1 bx~
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) wst[(pr + 16 * k) * R + pc] = BX[(pr + 16 * k) * PLD + pc];
+    {
+      d4 c = tile_load(BD, PLD, w * TB, 0);
+      const double* fr = MF + (w * TB + r) * LD + q;
+      c = mm_steps<N / 4>(c, [&](int st) { return -(fr[4 * st] * dAi[4 * st + q]); }, [&](int st) { return BX[(4 * st + q) * PLD + r]; });
+      tile_store(BD, PLD, w * TB, 0, c);
+    }
+    store_l(pm);   // L_A is done with (the substitution above ended at the last barrier)
+    if (t + 1 < a.T - 1) load_l(pm, facb + (int64_t)(t + 1) * D::FAC + D::F_LM);
+    __syncthreads();
+    // ---- bd^ = L_M^-1 bd~
+    if (w == 0) panel_trsm_lower<N, PLD>(LT, BD);
+    __syncthreads();
+    // ---- carried right-hand side: by = -V_u' (bu^ / piv) - V~' D_A^-1 bx~ + E~' D_M^-1 bd^
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) wst[N * R + (pr + 16 * k) * R + pc] = BD[(pr + 16 * k) * PLD + pc];
+    {
+      d4 c;
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < NU; ++j) s += vu[j * N + w * TB + q + 4 * jj] * bs[j];   // (pc == r: this lane's column)
+        c[jj] = -s;
+      }
+      const double* vc = MV + q * LD + w * TB + r;
+      const double* ec = ME + q * LD + w * TB + r;
+      c = mm_steps<N / 4>(c, [&](int st) { return -(vc[4 * st * LD] * dAi[4 * st + q]); }, [&](int st) { return BX[(4 * st + q) * PLD + r]; });
+      c = mm_steps<N / 4>(c, [&](int st) { return ec[4 * st * LD] * dMi[4 * st + q]; }, [&](int st) { return BD[(4 * st + q) * PLD + r]; });
+      tile_store(BY, PLD, w * TB, 0, c);
+    }
+  }
+  // ---- terminal block: x_T = L_A^-T D_A^-1 L_A^-1 (rx_T + by), to the caller's array where k_wide_bwd_multi picks it up
+  {
+    const int t = a.T - 1;
+    const double* facT = facb + (int64_t)t * D::FAC;
+    const int zo = a.zoff[t];
+    __syncthreads();
+    load_l(pa, facT + D::F_LA);
+    store_l(pa);
+    if (tid < N) dAi[tid] = facT[D::F_VEC + D::V_DA + tid];
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+      const int c = gc + 4 * k, e = grow * PLD + c;
+      BX[e] = (c < ncol ? a.rhs_x[(row0 + c) * a.ldrx + zo + grow] : 0.0) + BY[e];
+    }
+    __syncthreads();
+    if (w == 0) {
+      panel_trsm_lower<N, PLD>(LT, BX);
+      const double di = dAi[l];
+#pragma unroll
+      for (int c = 0; c < R; ++c) BX[l * PLD + c] *= di;
+      wave_lds_fence();
+      panel_trsm_upper<N, PLD>(LT, BX);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+      const int c = gc + 4 * k;
+      if (c < ncol) a.dz[(row0 + c) * a.lddz + zo + grow] = BX[grow * PLD + c];
+    }
+  }
+}
+
+// backward panel substitution: per stage what the loop of k_wide_bwd<M, false> does, R columns at a time
+template <class M, int R>
+__global__ __launch_bounds__(WG) void k_wide_bwd_multi(dto_wide_args a) {
+  constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
+  static_assert(N == 64, "wide path is built for 64 states");
+  static_assert(NU >= 1 && NU <= 4, "wide path: one to four actions per stage");
+  static_assert(DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD && DTO_WIDE_LDL_RANK1, "reads packed triangular factors with clean diagonal tiles");
+  using D = Dims<N, NU>;
+  using ML = MultiLds<M, R>;
+  constexpr int LD = D::LD, MAT = D::MAT, PLD = ML::PLD, PAN = ML::PAN;
+  constexpr int NP = (MAT / 2 + WG - 1) / WG;
+  constexpr int NPL = ML::LT / 2 / WG;
+  constexpr int NSC = (NU * (NU + 2) + 7) & ~7;
+  constexpr int CPT = R / 4;
+  static_assert(NSC <= 32 && NU * R <= N && NPL * WG * 2 == ML::LT, "thread maps of the small pieces");
+  extern __shared__ double sm[];
+  double* LT = sm;             // L_M, then L_A: packed lower tiles
+  double* MF = LT + ML::LT;
+  double* MV = MF + MAT;
+  double* ME = MV + MAT;
+  double* XP = ME + MAT;       // panels [N][PLD]: x_t, lam_t, y = x_{t+1}
+  double* LP = XP + PAN;
+  double* YP = LP + PAN;
+  double* au = YP + PAN;
+  double* fu = au + NU * N;
+  double* vu = fu + NU * N;
+  double* dAi = vu + NU * N;
+  double* dMi = dAi + N;
+  double* scv = dMi + N;       // [32]
+  double* buv = scv + 32;      // [NU][R] bu^ of the block
+  const int tid = threadIdx.x, w = wave_id(), l = lane_id();
+  const int r = l & 15, q = l >> 4;
+  const int64_t b = blockIdx.x;
+  if (a.active && !a.active[b]) return;
+  const double* facb = a.fac + b * (int64_t)a.T * D::FAC;
+  const double* wsb = a.ws + b * (int64_t)a.T * ML::WS;
+  const int ncol = (int)((a.nrhs - a.rhs0 < R) ? a.nrhs - a.rhs0 : R);
+  const int64_t row0 = b * a.nrhs + a.rhs0;
+  const int grow = tid & 63, gc = tid >> 6;
+  const int pc = tid & 15, pr = tid >> 4;
+
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  v2d pe[NP], pm[NPL], pf[NP], pv[NP], pa[NPL];
+  double pvec[2 + 3 * NU], psc = 0.0, pbx[4], pbd[4], pbu = 0.0;
+  auto load_mat = [&](v2d (&rg)[NP], const double* src) {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < MAT / 2) rg[k] = s2[i];
+    }
+  };
+  auto store_mat = [&](double* dst, const v2d (&rg)[NP]) {
+    v2d* d2 = reinterpret_cast<v2d*>(dst);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < MAT / 2) d2[i] = rg[k];
+    }
+  };
+  auto load_l = [&](v2d (&rg)[NPL], const double* src) {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) rg[k] = s2[tid + k * WG];
+  };
+  auto store_l = [&](const v2d (&rg)[NPL]) {
+    v2d* d2 = reinterpret_cast<v2d*>(LT);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) d2[tid + k * WG] = rg[k];
+  };
+  auto issue = [&](int t) {
+    const double* fac = facb + (int64_t)t * D::FAC;
+    const double* fv = fac + D::F_VEC;
+    const double* wst = wsb + (int64_t)t * ML::WS;
+    load_mat(pe, fac + D::F_ET);
+    load_l(pm, fac + D::F_LM);
+    load_mat(pf, fac + D::F_FT);
+    load_mat(pv, fac + D::F_VT);
+    // bx~ and bd^ of the block as this lane's accumulator entries of tile-row w
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      pbx[jj] = wst[(w * TB + q + 4 * jj) * R + r];
+      pbd[jj] = wst[N * R + (w * TB + q + 4 * jj) * R + r];
+    }
+    if (tid < NU * R) pbu = wst[2 * N * R + tid];
+    if (tid < N) {
+      pvec[0] = fv[D::V_DA + tid]; pvec[1] = fv[D::V_DM + tid];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        pvec[2 + 3 * j] = fv[D::V_AU + j * N + tid]; pvec[3 + 3 * j] = fv[D::V_FU + j * N + tid]; pvec[4 + 3 * j] = fv[D::V_VU + j * N + tid];
+      }
+    } else if (tid < N + 32) {
+      const int s = tid - N;
+      psc = s < NSC ? fv[D::V_SC + s] : 0.0;
+    }
+  };
+  {
+    const int zo = a.zoff[a.T - 1];
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+      const int c = gc + 4 * k;
+      YP[grow * PLD + c] = c < ncol ? a.dz[(row0 + c) * a.lddz + zo + grow] : 0.0;
+    }
+  }
+  if (a.T > 1) { issue(a.T - 2); load_l(pa, facb + (int64_t)(a.T - 2) * D::FAC + D::F_LA); }
+  for (int t = a.T - 2; t >= 0; --t) {
+    __syncthreads();
+    store_mat(ME, pe);
+    store_l(pm);
+    store_mat(MF, pf);
+    store_mat(MV, pv);
+    if (tid < N) {
+      dAi[tid] = pvec[0]; dMi[tid] = pvec[1];
+#pragma unroll
+      for (int j = 0; j < NU; ++j) { au[j * N + tid] = pvec[2 + 3 * j]; fu[j * N + tid] = pvec[3 + 3 * j]; vu[j * N + tid] = pvec[4 + 3 * j]; }
+    } else if (tid < N + 32) {
+      scv[tid - N] = psc;
+    }
+    if (tid < NU * R) buv[tid] = pbu;
+    d4 cx, cl;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) { cx[jj] = pbx[jj]; cl[jj] = -pbd[jj]; }
+    __syncthreads();
+    if (t > 0) issue(t - 1);
+    // ---- lam = L_M^-T D_M^-1 (E~ y - bd^)
+    {
+      const double* er = ME + (w * TB + r) * LD + q;
+      cl = mm_steps<N / 4>(cl, [&](int st) { return er[4 * st]; }, [&](int st) { return YP[(4 * st + q) * PLD + r]; });
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) cl[jj] *= dMi[w * TB + q + 4 * jj];
+      tile_store(LP, PLD, w * TB, 0, cl);
+    }
+    __syncthreads();
+    if (w == 0) panel_trsm_upper<N, PLD>(LT, LP);
+    __syncthreads();
+    // ---- x = L_A^-T D_A^-1 (bx~ - F~' lam - V~ y)
+    {
+      const double* fc = MF + q * LD + w * TB + r;
+      const double* vr = MV + (w * TB + r) * LD + q;
+      cx = mm_steps<N / 4>(cx, [&](int st) { return -fc[4 * st * LD]; }, [&](int st) { return LP[(4 * st + q) * PLD + r]; });
+      cx = mm_steps<N / 4>(cx, [&](int st) { return -vr[4 * st]; }, [&](int st) { return YP[(4 * st + q) * PLD + r]; });
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) cx[jj] *= dAi[w * TB + q + 4 * jj];
+      tile_store(XP, PLD, w * TB, 0, cx);
+    }
+    store_l(pa);   // L_M is done with (the substitution above ended at the last barrier)
+    if (t > 0) load_l(pa, facb + (int64_t)(t - 1) * D::FAC + D::F_LA);
+    __syncthreads();
+    if (w == 0) panel_trsm_upper<N, PLD>(LT, XP);
+    __syncthreads();
+    {
+      const int zo = a.zoff[t], co = a.cdoff[t];
+#pragma unroll
+      for (int k = 0; k < CPT; ++k) {
+        const int c = gc + 4 * k;
+        if (c < ncol) {
+          a.dz[(row0 + c) * a.lddz + zo + grow] = XP[grow * PLD + c];
+          a.dmu[(row0 + c) * a.lddmu + co + grow] = LP[grow * PLD + c];
+        }
+      }
+      if (w == 1) {
+        // u_j = (bu^_j - au_j'x - fu_j'lam - vu_j'y) / piv_j - sum_{k > j} L_u[k][j] u_k per column, last action first: lane (r, q)
+        // sums rows 16 q .. 16 q + 15 of column r, the four quarters meet by two exchanges
+        double part[NU];
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+          double s = 0.0;
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int row = q * 16 + i;
+            s += au[j * N + row] * XP[row * PLD + r] + fu[j * N + row] * LP[row * PLD + r] + vu[j * N + row] * YP[row * PLD + r];
+          }
+          s += __shfl_xor(s, 16);
+          s += __shfl_xor(s, 32);
+          part[j] = s;
+        }
+        double duv[NU];
+#pragma unroll
+        for (int j = NU - 1; j >= 0; --j) {
+          double uj = (buv[j * R + r] - part[j]) * scv[j];
+#pragma unroll
+          for (int k = j + 1; k < NU; ++k) uj -= scv[2 * NU + k * NU + j] * duv[k];
+          duv[j] = uj;
+        }
+        if (q == 0 && r < ncol) {
+#pragma unroll
+          for (int j = 0; j < NU; ++j) a.dz[(row0 + r) * a.lddz + zo + N + j] = duv[j];
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) YP[(pr + 16 * k) * PLD + pc] = XP[(pr + 16 * k) * PLD + pc];
+  }
+}
+
 // one wavefront per instance: out[b] = sum_t rows[b][t] in a fixed order (lane-strided partials, then a tree)
 static __global__ __launch_bounds__(64) void k_wide_sum_rows(const double* rows, int64_t ld, int n, double* out) {
   const int64_t b = blockIdx.x;
@@ -2544,8 +3079,19 @@ int wide_info(dto_wide_info* out) {
   out->nu = M::WIDE_NU;
   out->fac_stage = D::FAC;
   out->lds_bytes = StepLds<M>::BYTES;
+#if DTO_WIDE_SPLIT_BWD && DTO_WIDE_PACK_L && DTO_WIDE_LDL_RANK1
+  out->multi_r = DTO_WIDE_MULTI_R;
+  out->multi_ws_stage = MultiLds<M, DTO_WIDE_MULTI_R>::WS;
+#else
+  out->multi_r = 0;
+  out->multi_ws_stage = 0;
+#endif
   return 0;
 }
+
+// (defined behind launch_wide: the panel kernels are instantiated after every other kernel of the plugin)
+template <class M>
+int launch_wide_multi(const dto_wide_args* a, void* stream);
 
 template <class M>
 int launch_wide(int op, const dto_wide_args* a, void* stream) {
@@ -2578,6 +3124,9 @@ int launch_wide(int op, const dto_wide_args* a, void* stream) {
     hipLaunchKernelGGL((k_wide_bwd<M, false>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
     return (int)hipGetLastError();
   }
+#if DTO_WIDE_LDL_RANK1
+  if (op == DTO_WIDE_SOLVE_MULTI) return launch_wide_multi<M>(a, stream);
+#endif
 #endif
   if (op != DTO_WIDE_STEP) return (int)hipErrorInvalidValue;
   if (a->zl) {
@@ -2600,6 +3149,24 @@ int launch_wide(int op, const dto_wide_args* a, void* stream) {
   hipLaunchKernelGGL((k_wide_bwd<M, false>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
 #endif
   return (int)hipGetLastError();
+}
+
+// one block of right-hand sides: forward and backward panel substitution over the stored records, which are only read
+template <class M>
+int launch_wide_multi(const dto_wide_args* a, void* stream) {
+#if DTO_WIDE_SPLIT_BWD && DTO_WIDE_PACK_L && DTO_WIDE_LDL_RANK1
+  constexpr int R = DTO_WIDE_MULTI_R;
+  constexpr int lds = MultiLds<M, R>::BYTES;
+  hipError_t e = hipFuncSetAttribute((const void*)k_wide_fsub_multi<M, R>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL((k_wide_fsub_multi<M, R>), dim3((unsigned)a->B), dim3(WG), lds, (hipStream_t)stream, *a);
+  e = hipFuncSetAttribute((const void*)k_wide_bwd_multi<M, R>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL((k_wide_bwd_multi<M, R>), dim3((unsigned)a->B), dim3(WG), lds, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
+#else
+  return (int)hipErrorInvalidValue;
+#endif
 }
 
 }  // namespace wide

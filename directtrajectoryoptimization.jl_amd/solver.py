@@ -777,6 +777,16 @@ class Solver:
         capi.check(self._solve_nlp._lib.dto_kkt_solve(self._solve_nlp._h, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, sol_x_ptr, ldsx,
                                                       sol_c_ptr, ldsc, stream or None))
 
+    def kkt_solve_multi(self, nrhs, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, sol_x_ptr, ldsx, sol_c_ptr, ldsc, stream=0):
+        """K^-1 [rhs_x; rhs_c] for nrhs right-hand sides per instance against the system factorised last (include/dto.h:
+        dto_kkt_solve_multi).  Row rule: right-hand side r of instance b is row b * nrhs + r of every array, so rhs_x is
+        [B * nrhs][ldrx] and the solutions follow the same rule -- with B = 2 and nrhs = 3, right-hand side 1 of instance 1
+        is row 4.  nrhs = 1 is the layout of kkt_solve.  The solutions must not overlap the right-hand sides.  On the tile path
+        the stored factor is read once per block of 16 right-hand sides and is not written: kkt_solve and kkt_solve_multi may
+        be mixed on one factorisation; on the lane path this is nrhs passes of kkt_solve."""
+        capi.check(self._solve_nlp._lib.dto_kkt_solve_multi(self._solve_nlp._h, int(nrhs), rhs_x_ptr, ldrx, rhs_c_ptr, ldrc,
+                                                            sol_x_ptr, ldsx, sol_c_ptr, ldsc, stream or None))
+
     def iterate_batch(self, n, stream=0):
         capi.check(self._solve_nlp._lib.dto_solver_iterate(self._solve_nlp._h, int(n), stream or None))
 

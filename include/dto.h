@@ -243,7 +243,18 @@ int dto_kkt_step_batch(dto_problem* p, const dto_batch* b, const double* mu, int
  *    diagonals and the batch's parameters, so the caller's arrays may change after it returns.
  *  Order: assemble, factor, solve; dto_kkt_factor before dto_kkt_assemble and dto_kkt_solve before dto_kkt_factor fail with
  *  DTO_ERR_INVALID.  The single factorisation attempt is swept to the end whatever its inertia: dto_kkt_solve returns
- *  K^-1 rhs (unpivoted) also when inertia_ok is 0. */
+ *  K^-1 rhs (unpivoted) also when inertia_ok is 0.
+ *  dto_kkt_solve_multi solves for nrhs right-hand sides per instance against the same factorisation: right-hand side r of
+ *  instance b is row b * nrhs + r of rhs_x ([B * nrhs][ldrx]) and of rhs_c, and its solution is the same row of sol_x / sol_c;
+ *  nrhs = 1 is the layout of dto_kkt_solve.  The solutions must not overlap the right-hand sides.  Same state and same errors
+ *  as dto_kkt_solve, DTO_ERR_INVALID also for nrhs < 1; an indefinite matrix gives the unpivoted K^-1 rhs.  Cost per path:
+ *  - lane-per-instance path: nrhs passes of dto_kkt_solve (there is no stored factor to share), results bit-identical to them;
+ *  - tile path: the right-hand sides travel as 64 x 16 panels, so the stored records are read once forward and once backward
+ *    per block of 16 right-hand sides instead of once per right-hand side, and the triangular solves and matrix products of
+ *    a stage run on the matrix cores.  The records are only read (the intermediates of a block go to a workspace of
+ *    B x T x 16 x (128 + actions) doubles, allocated by the first call; the size is reported if that fails), so
+ *    dto_kkt_solve and dto_kkt_solve_multi may be mixed in any order on one factorisation.  With a single right-hand side
+ *    dto_kkt_solve is the cheaper call. */
 typedef struct dto_kkt_system {
   const double* mu;      int64_t ldmu;   /* [B][ldmu] multipliers inside W */
   const double* sigma_x; int64_t ldsx;   /* [B][ldsx] >= 0, or NULL */
@@ -254,6 +265,8 @@ int dto_kkt_assemble(dto_problem* p, const dto_batch* b, const dto_kkt_system* s
 int dto_kkt_factor(dto_problem* p, int32_t* inertia_ok, int32_t* num_negative, void* stream);
 int dto_kkt_solve(dto_problem* p, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, double* sol_x,
                   int64_t ldsx, double* sol_c, int64_t ldsc, void* stream);
+int dto_kkt_solve_multi(dto_problem* p, int64_t nrhs, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
+                        double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, void* stream);
 
 /* Batched interior-point solve, one independent NLP per instance, same structure, different guesses.
  * x0: DEVICE [B][ldx] initial guesses (what initialize_states!/initialize_controls! set,
