@@ -246,11 +246,13 @@ struct WideKkt {
   size_t cap_flags = 0;
   double* ws = nullptr;   // [B][T][multi_ws_stage]: intermediates of one block of right-hand sides (dto_kkt_solve_multi), allocated by
   size_t cap_ws = 0;      // the first multi-solve
+  double *ref_r = nullptr, *ref_d = nullptr;   // [B][Nz + Nc] each: residual and correction (or K sol) of dto_kkt_solve_refined,
+  size_t cap_ref_r = 0, cap_ref_d = 0;         // allocated by its first call with passes > 0 or a residual norm to report
   void release() {
-    for (void* q : {(void*)z, (void*)mu, (void*)params, (void*)sigx, (void*)sigc, (void*)flags, (void*)ws})
+    for (void* q : {(void*)z, (void*)mu, (void*)params, (void*)sigx, (void*)sigc, (void*)flags, (void*)ws, (void*)ref_r, (void*)ref_d})
       if (q) (void)hipFree(q);
-    z = mu = params = sigx = sigc = ws = nullptr; flags = nullptr;
-    cap_z = cap_mu = cap_params = cap_sigx = cap_sigc = cap_flags = cap_ws = 0;
+    z = mu = params = sigx = sigc = ws = ref_r = ref_d = nullptr; flags = nullptr;
+    cap_z = cap_mu = cap_params = cap_sigx = cap_sigc = cap_flags = cap_ws = cap_ref_r = cap_ref_d = 0;
     B = 0; assembled = factored = false;
   }
 };
@@ -265,6 +267,7 @@ static inline void wide_args_no_linear(dto_wide_args& a) {
   a.sigma_x = a.sigma_c = nullptr; a.ldsx = a.ldsc = 0; a.nneg = nullptr;
   a.rhs_x = a.rhs_c = nullptr; a.ldrx = a.ldrc = 0;
   a.nrhs = a.rhs0 = 0; a.ws = nullptr;
+  a.kmul_s = 0;
 }
 
 // ---- wide-stage models (dto_wide_kernels.hpp): one workgroup per instance, AoS buffers used as they are
@@ -482,6 +485,90 @@ static __global__ void k_rows_axpy(double* y, const double* x, const double* alp
   if (al == 0.0) return;
   for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x)
     y[b * ldy + i] += al * x[b * ldx + i];
+}
+
+// ---- wide-stage models: y = K v on the assembled system (k_wide_kmul) and the refined solve built on it.  The product reads what
+//      dto_kkt_assemble copied (point, multipliers, parameters, sigmas) and never the factor records, so it needs no
+//      factorisation and leaves one alone.
+static __global__ void k_rows_residual(double* r, const double* rhs, const double* kx, int64_t n, int64_t ldr, int64_t ldrhs, int64_t ldk) {
+  // r = rhs - K x, row by row (grid.x = B * AXPY_BLOCKS_PER_ROW, as k_rows_axpy)
+  const int64_t b = blockIdx.x / AXPY_BLOCKS_PER_ROW, blk = blockIdx.x % AXPY_BLOCKS_PER_ROW;
+  for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x)
+    r[b * ldr + i] = rhs[b * ldrhs + i] - kx[b * ldk + i];
+}
+static __global__ void k_rows_add(double* y, const double* d, int64_t n, int64_t ldy, int64_t ldd) {
+  const int64_t b = blockIdx.x / AXPY_BLOCKS_PER_ROW, blk = blockIdx.x % AXPY_BLOCKS_PER_ROW;
+  for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x)
+    y[b * ldy + i] += d[b * ldd + i];
+}
+// out[b] = max |r[b][0 .. n)|: one workgroup of 256 per instance; the maximum does not depend on the order it is taken in
+static __global__ __launch_bounds__(256) void k_rows_maxabs(const double* r, int64_t n, int64_t ldr, double* out) {
+  __shared__ double part[256];
+  const int64_t b = blockIdx.x;
+  double m = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) m = fmax(m, fabs(r[b * ldr + i]));
+  part[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if ((int)threadIdx.x < s) part[threadIdx.x] = fmax(part[threadIdx.x], part[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[b] = part[0];
+}
+static int wide_kkt_multiply(Problem* p, const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc, double* out_x, int64_t ldox,
+                             double* out_c, int64_t ldoc, hipStream_t st) {
+  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  const WideKkt& K = *p->wide_kkt;
+  dto_wide_args a;
+  wide_kkt_args(p, a);
+  a.sigma_x = K.use_sigx ? K.sigx : nullptr; a.ldsx = p->L.Nz;
+  a.sigma_c = K.use_sigc ? K.sigc : nullptr; a.ldsc = std::max<int64_t>(1, p->L.Nc);
+  a.rhs_x = v_x; a.ldrx = ldvx; a.rhs_c = v_c; a.ldrc = ldvc;
+  a.dz = out_x; a.lddz = ldox; a.dmu = out_c; a.lddmu = ldoc;
+  // stages per workgroup (0: the kernel's default DTO_WIDE_KMUL_S); the variable is for tools/wide_refine_bench.py, the result does
+  // not depend on it
+  static const int chunk = [] { const char* e = getenv("DTO_WIDE_KMUL_S"); return e ? std::max(0, atoi(e)) : 0; }();
+  a.kmul_s = chunk;
+  const int lrc = p->vt->launch_wide(DTO_WIDE_KMUL, &a, (void*)st);
+  if (lrc != 0) return hip_fail((hipError_t)lrc, "wide K v launch");
+  return DTO_OK;
+}
+// dto_kkt_solve, then `passes` rounds of r = rhs - K sol, d = K^-1 r against the same records, sol += d; with `resid` one more
+// product for max |rhs - K sol| of what is returned.  Residuals are formed in working precision (fixed-precision refinement).
+static int wide_kkt_solve_refined(Problem* p, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, double* sol_x,
+                                  int64_t ldsx, double* sol_c, int64_t ldsc, double* resid, hipStream_t st) {
+  int rc = wide_kkt_solve(p, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, st);
+  if (rc || (passes == 0 && !resid)) return rc;
+  WideKkt& K = *p->wide_kkt;
+  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, ld = Nz + Nc;
+  const size_t need = (size_t)K.B * (size_t)ld;
+  const std::string what = "dto_kkt_solve_refined: hipMalloc of a workspace array (" + std::to_string(need * sizeof(double)) + " bytes: " +
+                           std::to_string(K.B) + " instances x " + std::to_string(ld) + " doubles)";
+  if ((rc = wide_kkt_grow(&K.ref_r, &K.cap_ref_r, need, what.c_str()))) return rc;
+  if ((rc = wide_kkt_grow(&K.ref_d, &K.cap_ref_d, need, what.c_str()))) return rc;
+  double *r_x = K.ref_r, *r_c = K.ref_r + Nz, *d_x = K.ref_d, *d_c = K.ref_d + Nz;
+  const dim3 grid((unsigned)(K.B * AXPY_BLOCKS_PER_ROW)), block(256);
+  auto residual = [&]() -> int {   // ref_r = rhs - K sol (K sol passes through ref_d)
+    int e = wide_kkt_multiply(p, sol_x, ldsx, sol_c, ldsc, d_x, ld, d_c, ld, st);
+    if (e) return e;
+    hipLaunchKernelGGL(k_rows_residual, grid, block, 0, st, r_x, rhs_x, (const double*)d_x, Nz, ld, ldrx, ld);
+    if (Nc > 0) hipLaunchKernelGGL(k_rows_residual, grid, block, 0, st, r_c, rhs_c, (const double*)d_c, Nc, ld, ldrc, ld);
+    HIP_TRY(hipGetLastError());
+    return DTO_OK;
+  };
+  for (int it = 0; it < passes; ++it) {
+    if ((rc = residual())) return rc;
+    if ((rc = wide_kkt_solve(p, r_x, ld, r_c, ld, d_x, ld, d_c, ld, st))) return rc;
+    hipLaunchKernelGGL(k_rows_add, grid, block, 0, st, sol_x, (const double*)d_x, Nz, ldsx, ld);
+    if (Nc > 0) hipLaunchKernelGGL(k_rows_add, grid, block, 0, st, sol_c, (const double*)d_c, Nc, ldsc, ld);
+    HIP_TRY(hipGetLastError());
+  }
+  if (resid) {
+    if ((rc = residual())) return rc;
+    hipLaunchKernelGGL(k_rows_maxabs, dim3((unsigned)K.B), dim3(256), 0, st, (const double*)K.ref_r, ld, ld, resid);
+    HIP_TRY(hipGetLastError());
+  }
+  return DTO_OK;
 }
 
 // ---- finite variable bounds on the wide path (round 4): the barrier bookkeeping around k_wide_step, instance-major ----------
@@ -3772,6 +3859,37 @@ int dto_kkt_solve_multi(dto_problem* h, int64_t nrhs, const double* rhs_x, int64
     if (rc) return rc;
   }
   return DTO_OK;
+}
+
+int dto_kkt_multiply(dto_problem* h, const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc, double* out_x, int64_t ldox,
+                     double* out_c, int64_t ldoc, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();   // (allocates the tables of the handle once, launches nothing)
+  if (rc) return rc;
+  if (!p->vt->launch_wide)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_multiply: tile path only (the lane-per-instance path keeps no assembled system: its sweeps "
+                                          "rebuild the stage blocks in registers)");
+  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (!v_x || !out_x || (p->L.Nc > 0 && (!v_c || !out_c))) return set_error(DTO_ERR_INVALID, "null argument");
+  if (ldvx < p->L.Nz || ldox < p->L.Nz || ldvc < p->L.Nc || ldoc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  return dto::wide_kkt_multiply(p, v_x, ldvx, v_c, ldvc, out_x, ldox, out_c, ldoc, (hipStream_t)stream);
+}
+
+int dto_kkt_solve_refined(dto_problem* h, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, double* sol_x,
+                          int64_t ldsx, double* sol_c, int64_t ldsc, double* resid, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  if (!p->vt->launch_wide)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_solve_refined: tile path only (the lane-per-instance path stores no factor; its solver "
+                                          "refines through dto_options.kkt_refinement)");
+  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (passes < 0 || passes > 4) return set_error(DTO_ERR_INVALID, "passes outside 0..4");
+  if (!rhs_x || !sol_x || (p->L.Nc > 0 && (!rhs_c || !sol_c))) return set_error(DTO_ERR_INVALID, "null argument");
+  if (ldrx < p->L.Nz || ldsx < p->L.Nz || ldrc < p->L.Nc || ldsc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  return dto::wide_kkt_solve_refined(p, passes, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, resid, (hipStream_t)stream);
 }
 
 int dto_shard_range(int64_t total, int rank, int world, int64_t* first, int64_t* count) {

@@ -25,8 +25,9 @@
 
 // DTO_WIDE_FACTOR / DTO_WIDE_SOLVE: the linear solver alone (dto_kkt_factor / dto_kkt_solve): factor once, then any number of
 // substitution-only solves against the stored records.  DTO_WIDE_SOLVE_MULTI (dto_kkt_solve_multi): one block of up to
-// dto_wide_info::multi_r right-hand sides per launch, carried as 64 x R panels through the same records, which are only read
-enum dto_wide_op { DTO_WIDE_STEP = 0, DTO_WIDE_MERIT = 1, DTO_WIDE_FACTOR = 2, DTO_WIDE_SOLVE = 3, DTO_WIDE_SOLVE_MULTI = 4 };
+// dto_wide_info::multi_r right-hand sides per launch, carried as 64 x R panels through the same records, which are only read.
+// DTO_WIDE_KMUL (dto_kkt_multiply): out = K v on the system of DTO_WIDE_FACTOR, from the point alone -- no record is touched
+enum dto_wide_op { DTO_WIDE_STEP = 0, DTO_WIDE_MERIT = 1, DTO_WIDE_FACTOR = 2, DTO_WIDE_SOLVE = 3, DTO_WIDE_SOLVE_MULTI = 4, DTO_WIDE_KMUL = 5 };
 
 struct dto_wide_info {
   int supported;
@@ -78,6 +79,8 @@ struct dto_wide_args {
   //      side r of instance b is row b * nrhs + r of rhs_x / rhs_c / dz / dmu; this launch takes r = rhs0 .. rhs0 + multi_r - 1
   int64_t nrhs, rhs0;
   double* ws;                           // [B][T][multi_ws_stage] intermediates of one block (bx~, bd^, bu^ panels)
+  // ---- K v (DTO_WIDE_KMUL): v travels in rhs_x / rhs_c, the product in dz / dmu, sigma_x / sigma_c as for DTO_WIDE_FACTOR
+  int kmul_s;                           // stages per workgroup (0: DTO_WIDE_KMUL_S); 0 everywhere else
 };
 // stats: 0 f (barrier terms excluded), 1 theta_1, 2 theta_inf, 3 dual infeasibility, 4 grad phi' dz, 5 sum |lam|, 6/7 scratch,
 // 8 alpha_pmax, 9 alpha_dmax, 10 max s z, 11 max 1 / (s z), 12 sum z, 13 sum log s  (8..13 only with bounds)
@@ -3089,9 +3092,11 @@ int wide_info(dto_wide_info* out) {
   return 0;
 }
 
-// (defined behind launch_wide: the panel kernels are instantiated after every other kernel of the plugin)
+// (defined behind launch_wide: the panel kernels and K v are instantiated after every other kernel of the plugin)
 template <class M>
 int launch_wide_multi(const dto_wide_args* a, void* stream);
+template <class M>
+int launch_wide_kmul(const dto_wide_args* a, void* stream);
 
 template <class M>
 int launch_wide(int op, const dto_wide_args* a, void* stream) {
@@ -3127,6 +3132,7 @@ int launch_wide(int op, const dto_wide_args* a, void* stream) {
 #if DTO_WIDE_LDL_RANK1
   if (op == DTO_WIDE_SOLVE_MULTI) return launch_wide_multi<M>(a, stream);
 #endif
+  if (op == DTO_WIDE_KMUL) return launch_wide_kmul<M>(a, stream);
 #endif
   if (op != DTO_WIDE_STEP) return (int)hipErrorInvalidValue;
   if (a->zl) {
@@ -3167,6 +3173,269 @@ int launch_wide_multi(const dto_wide_args* a, void* stream) {
 #else
   return (int)hipErrorInvalidValue;
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------------
+// out = K [v_x; v_c] on the system that k_wide_step<M, false, true> factorises (DTO_WIDE_KMUL, dto_kkt_multiply):
+//     K = [ W + diag(sigma_x) + dw I    J'                  ]
+//         [ J                           -diag(sigma_c) - dc I ]
+// in the problem layout.  The stage blocks are assembled in LDS the way phases 0-4 of the sweep assemble them -- constant
+// Jacobian table, variable entries over it, dynamics and cost Hessian entries, dw + sigma_x on the diagonals, gam = 1, no fixed
+// components, no barrier terms -- and applied with the workgroup-wide dot products:
+//     x_t rows:    A vx + sum_j au_j vu_j + V vy + F' vl + carry        (A holds the y-y Hessian of stage t-1, as the sweep's P')
+//     u_t rows:    au_j' vx + W_uu vu + vu_j' vy + fu_j' vl + (dw + sigma) vu_j
+//     lam_t rows:  F vx + sum_j fu_j vu_j + E vy - (dc + sigma_c) vl
+//     carry to the rows of x_{t+1}:  V' vx + sum_j vu_j vu_j + E' vl
+// with vx, vu, vl the pieces of v at knot t and vy = v at x_{t+1}.  There is no O(n^3) work and no MFMA.
+// grid = (B, chunks), block = 256: workgroup (b, c) writes the rows of stages c S .. c S + S - 1 (the last one also the terminal
+// knot) and walks them in order, carrying the y-row terms in LDS as byc / gyp travel in the sweep; at its left edge it evaluates
+// the stage before its chunk only for that carry (and the y-y Hessian), by the same code -- so every row is written once, by one
+// thread, from the same operations whatever S is: no atomics, results bit-identical run to run and for every S.
+// Reads the point, the parameters, the sigmas and v; never a.fac.
+// ---------------------------------------------------------------------------------------------------
+#ifndef DTO_WIDE_KMUL_S
+#define DTO_WIDE_KMUL_S 8
+#endif
+template <class M>
+struct KmulLds {
+  static constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
+  static constexpr int SC = (3 * NU + NU * NU + 7) & ~7;
+  // four matrices, x y lam vx vy vl carry next-carry sigma [9 N], au fu vu [3 NU N], model outputs, u / W_uu / vu / sigma_u
+  static constexpr int DOUBLES = 4 * Dims<N>::MAT + (9 + 3 * NU) * N + M::MAX_NH + M::MAX_SNH + M::MAX_NJV + SC;
+  static constexpr int BYTES = DOUBLES * (int)sizeof(double);
+};
+template <class M>
+__global__ __launch_bounds__(WG) void k_wide_kmul(dto_wide_args a) {
+  constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
+  static_assert(N == 64, "wide path is built for 64 states (one row or column per four threads)");
+  static_assert(NU >= 1 && NU <= 4, "wide path: one to four actions per stage");
+  using D = Dims<N, NU>;
+  using KL = KmulLds<M>;
+  static_assert(KL::BYTES <= StepLds<M>::BYTES && KL::BYTES <= 160 * 1024, "K v: within the LDS image of k_wide_step and the 160 KB of a workgroup");
+  constexpr int LD = D::LD, MAT = D::MAT;
+  extern __shared__ double sm[];
+  double* MA = sm;
+  double* MF = MA + MAT;
+  double* MV = MF + MAT;
+  double* ME = MV + MAT;
+  double* xv = ME + MAT;       // the point of the stage
+  double* yv = xv + N;
+  double* lamv = yv + N;
+  double* px = lamv + N;       // v at x_t, x_{t+1}, lam_t
+  double* py = px + N;
+  double* pl = py + N;
+  double* cy = pl + N;         // carried terms of the rows of x_t (from stage t-1)
+  double* cyn = cy + N;
+  double* sgx = cyn + N;       // dw + sigma_x of x_t
+  double* au = sgx + N;        // A_xu [NU][N], F_u [NU][N], V_u [NU][N] as in k_wide_step
+  double* fu = au + NU * N;
+  double* vu = fu + NU * N;
+  double* hv = vu + NU * N;
+  double* chv = hv + M::MAX_NH;
+  double* jvv = chv + M::MAX_SNH;
+  double* sc = jvv + M::MAX_NJV;   // u [NU], W_uu [NU][NU], v at u_t [NU], dw + sigma_x of u_t [NU]
+  double* auu = sc + NU;
+  double* pu = auu + NU * NU;
+  double* sgu = pu + NU;
+
+  const int tid = threadIdx.x, w = wave_id(), l = lane_id();
+  const int64_t b = blockIdx.x;
+  const int S = a.kmul_s > 0 ? a.kmul_s : DTO_WIDE_KMUL_S;
+  const int t_first = (int)blockIdx.y * S;                     // stages whose rows this workgroup writes: t_first .. t_last - 1
+  const int t_last = min(t_first + S, a.T - 1);
+  if (t_first > a.T - 1 || (t_first == a.T - 1 && a.T > 1)) return;   // (the grid is sized so that this does not happen)
+  const bool terminal = t_last == a.T - 1;
+  const double* z = a.z + b * a.ldz;
+  const double* mu = a.mu + b * a.ldmu;
+  const double* sgxb = a.sigma_x ? a.sigma_x + b * a.ldsx : nullptr;
+  const double* sgcb = a.sigma_c ? a.sigma_c + b * a.ldsc : nullptr;
+  const double* vxb = a.rhs_x + b * a.ldrx;
+  const double* vcb = a.rhs_c + b * a.ldrc;
+  double* oxb = a.dz + b * a.lddz;
+  double* ocb = a.dmu + b * a.lddmu;
+  const double dw = a.delta_w, dc = a.delta_c;
+
+  for (int i = tid; i < MAT; i += WG) MA[i] = 0.0;
+  if (tid < N) cy[tid] = 0.0;
+  lds_barrier();
+
+  for (int t = max(t_first - 1, 0); t < t_last; ++t) {
+    const bool emit = t >= t_first;   // (workgroup-uniform)
+    const int wk = M::wk_of_kind(a.kind[t]);
+    M::dispatch_wk(wk, [&](auto wkc) {
+      constexpr int WKI = decltype(wkc)::value;
+      using KD = typename M::template WKind<WKI>;
+      if constexpr (KD::DYN >= 0) {
+        using DY = typename M::template Dyn<KD::DYN>;
+        using CO = typename M::template Cost<KD::COST>;
+        static_assert(DY::NX == N && DY::NY == N && DY::NU == NU, "uniform wide stages expected");
+        const double* wp = a.params + b * a.ldw + a.woff[t];
+        // ---- the point, v, the constant Jacobian part (phase 0 of the sweep)
+        if (tid < N) {
+          const int ix = a.zoff[t] + tid, iy = a.zoff[t + 1] + tid, ic = a.cdoff[t] + tid;
+          xv[tid] = z[ix]; yv[tid] = z[iy]; lamv[tid] = mu[ic];
+          px[tid] = vxb[ix]; py[tid] = vxb[iy]; pl[tid] = vcb[ic];
+#pragma unroll
+          for (int j = 0; j < NU; ++j) { au[j * N + tid] = 0.0; vu[j * N + tid] = 0.0; }
+          const double sg = dw + (sgxb ? sgxb[ix] : 0.0);
+          sgx[tid] = sg;
+          MA[tid * LD + tid] += sg;
+        }
+        if (tid >= 64 && tid < 64 + NU) {
+          const int iu = a.zoff[t] + N + (tid - 64);
+          sc[tid - 64] = z[iu]; pu[tid - 64] = vxb[iu];
+          sgu[tid - 64] = dw + (sgxb ? sgxb[iu] : 0.0);
+        }
+        if (tid >= 128 && tid < 128 + NU * NU) auu[tid - 128] = 0.0;
+        {
+          constexpr int NC = 2 * N + NU;
+          const double* fe = DY::fe_const();
+#pragma unroll 1
+          for (int part = 0; part < N / 16; ++part) {   // four rows of both matrices per pass: eight loads in flight
+            const int r0 = w + 16 * part;
+            double fr[4], er[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { fr[i] = fe[(r0 + 4 * i) * NC + l]; er[i] = fe[(r0 + 4 * i) * NC + N + NU + l]; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { MF[(r0 + 4 * i) * LD + l] = fr[i]; ME[(r0 + 4 * i) * LD + l] = er[i]; }
+          }
+          for (int i = tid; i < N * NU; i += WG) fu[i] = fe[(i % N) * NC + N + i / N];
+          for (int i = tid; i < MAT; i += WG) MV[i] = 0.0;
+        }
+        lds_barrier();
+        // ---- model code (phase 1: wave-uniform values, one wavefront per function)
+        if (w == 1) {
+          DY::jac_var(xv, sc, yv, wp, jvv);
+        } else if (w == 2) {
+          if constexpr (DY::NH > 0) DY::hess(xv, sc, yv, wp, lamv, hv);
+        } else if (w == 3) {
+          if constexpr (CO::SNH > 0) CO::shess(xv, sc, wp, chv);
+        }
+        lds_barrier();
+        // ---- variable Jacobian entries, cost Hessian; then the dynamics Hessian (phase 3)
+        if (tid < DY::NJV) {
+          const int r = DY::jv_row(tid), c = DY::jv_col(tid);
+          const double v = jvv[tid];
+          if (c < N) MF[r * LD + c] = v;
+          else if (c < N + NU) fu[(c - N) * N + r] = v;
+          else ME[r * LD + c - N - NU] = v;
+        }
+        if constexpr (CO::SNH > 0) {
+          if (tid < CO::SNH) {
+            const int r = CO::sh_row(tid), c = CO::sh_col(tid);
+            const double v = chv[tid];
+            if (r < N && c < N) MA[r * LD + c] += v;
+            else if (r < N && c >= N) au[(c - N) * N + r] += v;
+            else if (r >= N && c >= N) auu[(r - N) * NU + c - N] += v;
+          }
+        }
+        lds_barrier();
+        if constexpr (DY::NH > 0) {
+          if (tid < DY::NH) {
+            const int r = DY::h_row(tid), c = DY::h_col(tid);
+            const double v = hv[tid];
+            if (r < N) {
+              if (c < N) MA[r * LD + c] += v;
+              else if (c < N + NU) au[(c - N) * N + r] += v;
+              else MV[r * LD + c - N - NU] += v;
+            } else if (r < N + NU) {
+              if (c >= N && c < N + NU) auu[(r - N) * NU + c - N] += v;
+              else if (c >= N + NU) vu[(r - N) * N + c - N - NU] += v;
+            }
+          }
+        }
+        lds_barrier();
+        // ---- products: thread (row or column tid >> 2, quarter tid & 3), the quarters summed by quad_sum
+        {
+          const int i = tid >> 2;
+          if (emit) {
+            const double qx = quad_sum(dotq_r<N>(MA, LD, px) + dotq_r<N>(MV, LD, py) + dotq_c<N>(MF, LD, pl));
+            const double ql = quad_sum(dotq_r<N>(MF, LD, px) + dotq_r<N>(ME, LD, py));
+            if ((tid & 3) == 0) {
+              double ox = qx + cy[i], ol = ql - (dc + (sgcb ? sgcb[a.cdoff[t] + i] : 0.0)) * pl[i];
+#pragma unroll
+              for (int j = 0; j < NU; ++j) { ox += au[j * N + i] * pu[j]; ol += fu[j * N + i] * pu[j]; }
+              oxb[a.zoff[t] + i] = ox;
+              ocb[a.cdoff[t] + i] = ol;
+            }
+          }
+          const double qy = quad_sum(dotq_c<N>(MV, LD, px) + dotq_c<N>(ME, LD, pl));
+          if ((tid & 3) == 0) {
+            double oy = qy;
+#pragma unroll
+            for (int j = 0; j < NU; ++j) oy += vu[j * N + i] * pu[j];
+            cyn[i] = oy;
+          }
+        }
+        if (emit && w == 2) {
+#pragma unroll
+          for (int j = 0; j < NU; ++j) {
+            const double part = wave_sum(au[j * N + l] * px[l] + fu[j * N + l] * pl[l] + vu[j * N + l] * py[l]);
+            if (l == 0) {
+              double ou = part + sgu[j] * pu[j];
+#pragma unroll
+              for (int k = 0; k < NU; ++k) ou += auu[j * NU + k] * pu[k];
+              oxb[a.zoff[t] + N + j] = ou;
+            }
+          }
+        }
+        lds_barrier();
+        // ---- the next knot: its carried terms, and the y-y part of this stage's Hessian as the start of its A
+        for (int i = tid; i < MAT; i += WG) MA[i] = 0.0;
+        if (tid < N) cy[tid] = cyn[tid];
+        lds_barrier();
+        if constexpr (DY::NH > 0) {
+          if (tid < DY::NH) {
+            const int r = DY::h_row(tid), c = DY::h_col(tid);
+            if (r >= N + NU && c >= N + NU) MA[(r - N - NU) * LD + c - N - NU] += hv[tid];
+          }
+        }
+        lds_barrier();
+      }
+    });
+  }
+  // ---- terminal knot: (W_T + (dw + sigma_x) I) vx + carry, with the y-y Hessian of the last stage already in A
+  if (terminal) {
+    const int t = a.T - 1;
+    const int wk = M::wk_of_kind(a.kind[t]);
+    M::dispatch_wk(wk, [&](auto wkc) {
+      constexpr int WKI = decltype(wkc)::value;
+      using KD = typename M::template WKind<WKI>;
+      if constexpr (KD::DYN < 0) {
+        using CO = typename M::template Cost<KD::COST>;
+        const double* wp = a.params + b * a.ldw + a.woff[t];
+        if (tid < N) {
+          const int ix = a.zoff[t] + tid;
+          xv[tid] = z[ix]; px[tid] = vxb[ix];
+          MA[tid * LD + tid] += dw + (sgxb ? sgxb[ix] : 0.0);
+        }
+        lds_barrier();
+        if (w == 0) {
+          if constexpr (CO::SNH > 0) CO::shess(xv, sc, wp, chv);
+        }
+        lds_barrier();
+        if constexpr (CO::SNH > 0) {
+          if (tid < CO::SNH) MA[CO::sh_row(tid) * LD + CO::sh_col(tid)] += chv[tid];
+        }
+        lds_barrier();
+        const double qx = quad_sum(dotq_r<N>(MA, LD, px));
+        if ((tid & 3) == 0) oxb[a.zoff[t] + (tid >> 2)] = qx + cy[tid >> 2];
+      }
+    });
+  }
+}
+
+// out = K v on the assembled system (dto_kkt_multiply): B x ceil((T - 1) / S) workgroups
+template <class M>
+int launch_wide_kmul(const dto_wide_args* a, void* stream) {
+  const int S = a->kmul_s > 0 ? a->kmul_s : DTO_WIDE_KMUL_S;
+  const int chunks = a->T > 1 ? (a->T - 1 + S - 1) / S : 1;
+  if (chunks > 65535) return (int)hipErrorInvalidValue;
+  constexpr int lds = KmulLds<M>::BYTES;
+  hipError_t e = hipFuncSetAttribute((const void*)k_wide_kmul<M>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL((k_wide_kmul<M>), dim3((unsigned)a->B, (unsigned)chunks), dim3(WG), lds, (hipStream_t)stream, *a);
+  return (int)hipGetLastError();
 }
 
 }  // namespace wide

@@ -787,6 +787,34 @@ class Solver:
         capi.check(self._solve_nlp._lib.dto_kkt_solve_multi(self._solve_nlp._h, int(nrhs), rhs_x_ptr, ldrx, rhs_c_ptr, ldrc,
                                                             sol_x_ptr, ldsx, sol_c_ptr, ldsc, stream or None))
 
+    def kkt_multiply(self, v_x_ptr, ldvx, v_c_ptr, ldvc, out_x_ptr, ldox, out_c_ptr, ldoc, stream=0):
+        """[out_x; out_c] = K [v_x; v_c] on the system assembled last (include/dto.h: dto_kkt_multiply), tile path only: K is
+        [[W + diag(sigma_x) + delta_w I, J'], [J, -diag(sigma_c) - delta_c I]] at the point of kkt_assemble, arrays [B][ld] in
+        the solver's layout as for kkt_solve.  Needs kkt_assemble only; the stored factor is neither read nor invalidated, so
+        the call may stand anywhere between kkt_factor / kkt_solve / kkt_solve_multi.  The product must not overlap v.  Results
+        are bit-identical from run to run.  The lane-per-instance path raises DTO_ERR_UNSUPPORTED."""
+        if not all(isinstance(v, (int, np.integer)) for v in (v_x_ptr, v_c_ptr, out_x_ptr, out_c_ptr)):
+            raise TypeError("kkt_multiply takes device pointers as integers (tensor.data_ptr())")
+        if (out_x_ptr and out_x_ptr == v_x_ptr) or (out_c_ptr and out_c_ptr == v_c_ptr):
+            raise ValueError("kkt_multiply: the product must not overlap v")
+        capi.check(self._solve_nlp._lib.dto_kkt_multiply(self._solve_nlp._h, v_x_ptr, ldvx, v_c_ptr, ldvc, out_x_ptr, ldox,
+                                                         out_c_ptr, ldoc, stream or None))
+
+    def kkt_solve_refined(self, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, sol_x_ptr, ldsx, sol_c_ptr, ldsc, passes, resid_ptr=0, stream=0):
+        """kkt_solve followed by `passes` (0 .. 4) rounds of iterative refinement against the same stored factor (include/dto.h:
+        dto_kkt_solve_refined), tile path only: r = rhs - K sol (kkt_multiply), d = K^-1 r, sol += d.  passes = 0 is kkt_solve,
+        bit for bit.  resid_ptr: DEVICE [B] doubles or 0 -- when given, one more product writes max |rhs - K sol| of the
+        returned solution per instance.  The factorisation is not repeated.  The lane-per-instance path raises
+        DTO_ERR_UNSUPPORTED (its solver refines through Options.kkt_refinement)."""
+        if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)):
+            raise TypeError("kkt_solve_refined: passes is an integer")
+        if not 0 <= passes <= 4:
+            raise ValueError("kkt_solve_refined: passes outside 0..4")
+        if (sol_x_ptr and sol_x_ptr == rhs_x_ptr) or (sol_c_ptr and sol_c_ptr == rhs_c_ptr):
+            raise ValueError("kkt_solve_refined: the solution must not overlap the right-hand side (it is read again by every pass)")
+        capi.check(self._solve_nlp._lib.dto_kkt_solve_refined(self._solve_nlp._h, int(passes), rhs_x_ptr, ldrx, rhs_c_ptr, ldrc,
+                                                              sol_x_ptr, ldsx, sol_c_ptr, ldsc, resid_ptr or None, stream or None))
+
     def iterate_batch(self, n, stream=0):
         capi.check(self._solve_nlp._lib.dto_solver_iterate(self._solve_nlp._h, int(n), stream or None))
 

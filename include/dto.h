@@ -254,7 +254,28 @@ int dto_kkt_step_batch(dto_problem* p, const dto_batch* b, const double* mu, int
  *    a stage run on the matrix cores.  The records are only read (the intermediates of a block go to a workspace of
  *    B x T x 16 x (128 + actions) doubles, allocated by the first call; the size is reported if that fails), so
  *    dto_kkt_solve and dto_kkt_solve_multi may be mixed in any order on one factorisation.  With a single right-hand side
- *    dto_kkt_solve is the cheaper call. */
+ *    dto_kkt_solve is the cheaper call.
+ *  dto_kkt_multiply writes [out_x; out_c] = K [v_x; v_c] for the system of dto_kkt_assemble,
+ *      K = [ W(x,mu) + diag(sigma_x) + delta_w I    J(x)'                      ]
+ *          [ J(x)                                   -diag(sigma_c) - delta_c I ],
+ *  per instance, v and the product as [B][ld] DEVICE arrays in the layout of rhs_x / rhs_c and sol_x / sol_c.  It needs
+ *  dto_kkt_assemble only, not a factorisation: the blocks are rebuilt from the point stage by stage, the stored factor is
+ *  neither read nor invalidated, so the call may stand anywhere among dto_kkt_factor / dto_kkt_solve / dto_kkt_solve_multi.
+ *  The product must not overlap v.  Results are bit-identical from run to run (no atomic sums).  Errors: DTO_ERR_INVALID before
+ *  dto_kkt_assemble, for a null array or a leading dimension below the row length.
+ *  dto_kkt_solve_refined is dto_kkt_solve followed by `passes` rounds of iterative refinement against the same stored factor:
+ *  r = rhs - K sol (the product above, residual in working precision), d = K^-1 r (substitution only), sol += d.  passes = 0
+ *  is dto_kkt_solve, bit for bit; 1 .. 4 are accepted, anything else is DTO_ERR_INVALID.  resid: DEVICE [B] or NULL -- when
+ *  given, one further product writes max |rhs - K sol| over the rows of each instance for the solution returned.  The
+ *  factorisation is not repeated, so a pass (one product, one substitution) costs far less than a new dto_kkt_factor; where the single
+ *  attempt of dto_kkt_factor met an indefinite block (inertia_ok 0) the unpivoted solve loses digits that the passes win back
+ *  as long as the factor is still a contraction.  Same state and same errors as dto_kkt_solve (assemble, factor, a factor not
+ *  taken by dto_kkt_step_batch or the solver); the solution must not overlap the right-hand side.  Workspace: two arrays of
+ *  B x (num_variables + num_constraint) doubles kept with the handle, allocated by the first call that needs them (the size
+ *  is reported if that fails).  Per path:
+ *  - tile path: as described;
+ *  - lane-per-instance path: both return DTO_ERR_UNSUPPORTED -- no assembled system or factor is kept there (the sweeps
+ *    rebuild the stage blocks in registers), and refinement lives in its solver (dto_options.kkt_refinement). */
 typedef struct dto_kkt_system {
   const double* mu;      int64_t ldmu;   /* [B][ldmu] multipliers inside W */
   const double* sigma_x; int64_t ldsx;   /* [B][ldsx] >= 0, or NULL */
@@ -267,6 +288,10 @@ int dto_kkt_solve(dto_problem* p, const double* rhs_x, int64_t ldrx, const doubl
                   int64_t ldsx, double* sol_c, int64_t ldsc, void* stream);
 int dto_kkt_solve_multi(dto_problem* p, int64_t nrhs, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
                         double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, void* stream);
+int dto_kkt_multiply(dto_problem* p, const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc, double* out_x,
+                     int64_t ldox, double* out_c, int64_t ldoc, void* stream);
+int dto_kkt_solve_refined(dto_problem* p, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
+                          double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, double* resid, void* stream);
 
 /* Batched interior-point solve, one independent NLP per instance, same structure, different guesses.
  * x0: DEVICE [B][ldx] initial guesses (what initialize_states!/initialize_controls! set,

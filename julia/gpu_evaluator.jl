@@ -245,6 +245,38 @@ function solve_batch(ev::GPUEvaluator, X0::Matrix{Float64}; options = Options(),
 end
 
 """
+    kkt_multiply!(ev, v_x, v_c, out_x, out_c)
+
+`[out_x; out_c] = K [v_x; v_c]` on the system of the last `dto_kkt_assemble` on `ev` (`dto_kkt_multiply`, tile path: 17..64-state
+models): DEVICE arrays, num_variables × B and num_constraint × B.  Needs no factorisation and leaves a stored one alone; the
+product must not overlap `v`.
+"""
+function kkt_multiply!(ev::GPUEvaluator, v_x::Ptr{Float64}, v_c::Ptr{Float64}, out_x::Ptr{Float64}, out_c::Ptr{Float64})
+    nz, nc = ev.num_variables, ev.num_constraint
+    dto_check(ccall((:dto_kkt_multiply, libdto), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    ev.handle, v_x, nz, v_c, nc, out_x, nz, out_c, nc, C_NULL))
+    return nothing
+end
+
+"""
+    kkt_solve_refined!(ev, rhs_x, rhs_c, sol_x, sol_c; passes = 2, resid = C_NULL)
+
+`dto_kkt_solve` followed by `passes` (0..4) rounds of iterative refinement against the factor stored by `dto_kkt_factor`
+(`dto_kkt_solve_refined`, tile path): DEVICE arrays as for `kkt_multiply!`; `resid` is a DEVICE vector of B doubles that receives
+max |rhs − K sol| per instance, or `C_NULL`.
+"""
+function kkt_solve_refined!(ev::GPUEvaluator, rhs_x::Ptr{Float64}, rhs_c::Ptr{Float64}, sol_x::Ptr{Float64}, sol_c::Ptr{Float64};
+                            passes = 2, resid = Ptr{Float64}(C_NULL))
+    nz, nc = ev.num_variables, ev.num_constraint
+    dto_check(ccall((:dto_kkt_solve_refined, libdto), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Cvoid}),
+                    ev.handle, passes, rhs_x, nz, rhs_c, nc, sol_x, nz, sol_c, nc, resid, C_NULL))
+    return nothing
+end
+
+"""
     set_bounds_batch!(ev, lower, upper)
     set_bounds_batch!(ev, nothing, nothing)
 
