@@ -241,3 +241,70 @@ class PaddedStageRows:
             H[o, o] += -2.0 * v
             H[o + 1, o + 1] += -2.0 * v
         return H
+
+
+WIDE = 64   # states per knot of the solver's layout (the tile kernels' stage width)
+
+
+def embedded_dense_kkt(model: PaddedAcrobot, rows, T: int, z, mu, dw, dc):
+    """Dense K of a problem with model.n < 64 states embedded in 64 states per knot, restated from the definition of the
+    embedding alone (numpy, PaddedAcrobot and PaddedStageRows; no product code):
+
+        z = [x_1 (64); u_1; x_2 (64); ...; x_T (64)],  mu = 64 rows per stage,  stage t maps (x, u) = knot t to y = knot t + 1,
+        rows 0 .. n-1          the model's own dynamics on x[0:n], u, y[0:n]; the model's cost on x[0:n], u
+        row  n + j             y_{n+j} - c_j(x)       row j of the stage constraints of knot t (`rows`, or none)
+        stage T-2, behind its own rows:   y_{n+k+j} - cT_j(y)    the rows of the LAST knot as functions of the next state
+        rows up to n + QS      y_q                    auxiliary slots no row of this stage feeds (QS: the most rows in one stage)
+        rows n + QS .. 63      y_q - x_q              padding
+
+    K = [[W + dw I, J'], [J, -dc I]] with W the Hessian of the costs + sum_r mu_r (row r)'' -- for an auxiliary row that is
+    -mu_r c_j''.  No bounds: auxiliary and padding states are free variables."""
+    n, m, N = model.n, model.m, WIDE
+    nz, nc = (T - 1) * (N + m) + N, (T - 1) * N
+    z, mu = np.asarray(z, float), np.asarray(mu, float)
+    assert z.shape == (nz,) and mu.shape == (nc,)
+    Q = list(rows.rows_of) if rows is not None else [0] * T
+    QS = max(Q[t] + (Q[T - 1] if t == T - 2 else 0) for t in range(T - 1))
+    assert n + QS <= N
+    if rows is not None:
+        # the closed forms of PaddedStageRows take the problem's own vector [x_1 (n); u_1; ...; x_T (n)]
+        z_own = np.concatenate([np.concatenate([z[t * (N + m):t * (N + m) + n], z[t * (N + m) + N:t * (N + m) + N + (m if t < T - 1 else 0)]])
+                                for t in range(T)])
+        Jc = rows.jacobian(z_own)
+    H = np.zeros((nz, nz)); J = np.zeros((nc, nz))
+    for t in range(T):
+        o = t * (N + m)
+        phys = np.concatenate([np.arange(o, o + n), np.arange(o + N, o + N + (m if t < T - 1 else 0))])   # x[0:n], u of knot t
+        x = z[o:o + n]
+        u = z[o + N:o + N + m] if t < T - 1 else np.zeros(0)
+        _, Wt = model.cost_grad_hess(x, u)
+        H[np.ix_(phys, phys)] += Wt
+        if t == T - 1:
+            break
+        oy = o + N + m
+        r0 = t * N
+        lam = mu[r0:r0 + N]
+        # rows 0 .. n-1
+        loc = np.concatenate([phys, np.arange(oy, oy + n)])                 # [x[0:n]; u; y[0:n]]
+        J[r0:r0 + n, loc] = model.jacobian(x, u, z[oy:oy + n])
+        H[np.ix_(loc, loc)] += model.hessian(x, u, z[oy:oy + n], lam[:n])
+        k = n
+        if rows is not None:
+            # rows of knot t, functions of x = knot t; then (t = T-2) the rows of the last knot, functions of y = knot T-1
+            feeds = [(t, o)] + ([(T - 1, oy)] if t == T - 2 else [])
+            for knot, ok in feeds:
+                oo = knot * (n + m)                                         # the knot's offset in z_own
+                for j in range(Q[knot]):
+                    rr = int(rows.off[knot]) + j
+                    J[r0 + k, oy + k] = 1.0
+                    J[r0 + k, ok:ok + n] = -Jc[rr, oo:oo + n]
+                    nu = np.zeros(rows.num); nu[rr] = -lam[k]               # Hessian term of lam (y - c): -lam c''
+                    Hc = rows.hessian(z_own, nu)
+                    H[ok:ok + n, ok:ok + n] += Hc[oo:oo + n, oo:oo + n]
+                    k += 1
+        for q in range(k, n + QS):
+            J[r0 + q, oy + q] = 1.0
+        for q in range(n + QS, N):
+            J[r0 + q, oy + q] = 1.0
+            J[r0 + q, o + q] = -1.0
+    return np.block([[H + dw * np.eye(nz), J.T], [J, -dc * np.eye(nc)]])

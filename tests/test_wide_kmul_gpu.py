@@ -3,8 +3,13 @@
 Reference everywhere: the ORACLE's dense matrix (oracle/padded_model.py: dense_kkt, plus diag([sigma_x; -sigma_c])) applied in
 np.longdouble on the host.  Bar: the project's 1e-8 of max |K v|; the componentwise figure
 max_i |out - K v|_i / (|K| |v|)_i is printed (DESIGN.md section 4.3 records it).  Shapes: one stage, two stages, three and four
-actions, and a chunk edge of the kernel's grid with one stage and with three stages behind it (T = S + 1, S + 3).
+actions, a chunk edge of the kernel's grid with one stage and with three stages behind it (T = S + 1, S + 3), and three chunks
+(T = 2 S + 2).  The chunk length itself (DTO_WIDE_KMUL_S, read once per process) is varied over child processes.
 """
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -50,22 +55,29 @@ def _dense(m, T, z, mu, dw, dc, sx=None, sc=None, parameters=None):
     return K
 
 
+def _point(m, T, sig=True):
+    """Point and sigmas of one case (no oracle matrix: the children of the chunk-length test need none)."""
+    nz, nc = (T - 1) * (64 + m) + 64, (T - 1) * 64
+    rng = np.random.default_rng(1000 * m + 10 * T + int(sig))
+    Z, MU = rng.random((B, nz)), rng.random((B, nc))
+    SX = SC = None
+    if sig:
+        SX, SC = rng.random((B, nz)) * 3.0, rng.random((B, nc)) * 0.5
+        SX[:, ::3] = 0.0
+    return dict(nz=nz, nc=nc, Z=Z, MU=MU, SX=SX, SC=SC)
+
+
 def _case(m, T, sig=True):
     """Point, sigmas and the oracle's matrices of one case: computed once, shared by the tests, never changed."""
     key = (m, T, sig)
     if key not in _CASES:
-        nz, nc = (T - 1) * (64 + m) + 64, (T - 1) * 64
-        rng = np.random.default_rng(1000 * m + 10 * T + int(sig))
-        Z, MU = rng.random((B, nz)), rng.random((B, nc))
-        SX = SC = None
-        if sig:
-            SX, SC = rng.random((B, nz)) * 3.0, rng.random((B, nc)) * 0.5
-            SX[:, ::3] = 0.0
+        c = _point(m, T, sig)
+        Z, MU, SX, SC = c["Z"], c["MU"], c["SX"], c["SC"]
         Ks = [_dense(m, T, Z[b], MU[b], DW, DC, None if SX is None else SX[b], None if SC is None else SC[b]) for b in range(B)]
         for a in (Z, MU, SX, SC, *Ks):
             if a is not None:
                 a.setflags(write=False)
-        _CASES[key] = dict(nz=nz, nc=nc, Z=Z, MU=MU, SX=SX, SC=SC, Ks=Ks)
+        _CASES[key] = dict(c, Ks=Ks)
     return _CASES[key]
 
 
@@ -125,11 +137,13 @@ def _vectors(m, T, nz, nc, rng):
 
 
 @pytest.mark.parametrize("m,T,sig,padded", [(1, 2, True, False), (1, 3, True, True), (1, 3, False, False), (3, 3, True, False),
-                                            (4, 3, True, False), (1, S + 1, True, False), (1, S + 3, True, False)])
+                                            (4, 3, True, False), (1, S + 1, True, False), (1, S + 3, True, False),
+                                            (1, 2 * S + 2, True, False)])
 def test_kkt_multiply_matches_the_oracle(m, T, sig, padded):
     """Columns and random combinations of the oracle's K: a wrong block shows as a wrong column.  sig=False: sigma_x / sigma_c
     NULL.  padded: four different leading dimensions, NaN in every padding entry -- read paddings would show as NaN in the
-    product, written ones are caught in _multiply."""
+    product, written ones are caught in _multiply.  T = 2 S + 2: three chunks, the middle one recomputes a left edge and holds
+    no terminal knot."""
     s = _solver(m, T)
     c = _case(m, T, sig)
     nz, nc = c["nz"], c["nc"]
@@ -171,6 +185,41 @@ def test_kkt_multiply_is_bit_identical_run_to_run():
     V = np.random.default_rng(3).standard_normal((B, c["nz"] + c["nc"]))
     a, b_ = _multiply(s, V, c["nz"], c["nc"]), _multiply(s, V, c["nz"], c["nc"])
     assert np.array_equal(a, b_)
+
+
+CHUNK_T = S + 3
+
+
+def _chunk_child(out_path):
+    """One process of test_kkt_multiply_is_bit_identical_for_every_chunk_length: the product of one fixed vector, saved."""
+    c = _point(1, CHUNK_T, True)
+    s = _solver(1, CHUNK_T)
+    _assemble(s, c)
+    V = np.random.default_rng(4).standard_normal((B, c["nz"] + c["nc"]))
+    out = _multiply(s, V, c["nz"], c["nc"])
+    assert np.all(np.isfinite(out))
+    with open(out_path, "wb") as f:
+        np.save(f, out)
+
+
+def test_kkt_multiply_is_bit_identical_for_every_chunk_length(tmp_path):
+    """k_wide_kmul writes every row once, by one thread, from the same operations whatever the chunk length is.  The length is
+    read from DTO_WIDE_KMUL_S once per process, so each value gets a fresh child process, one after the other (never two children
+    on the GPU at a time): 1 and 3 stages per workgroup and the default 8 on T = S + 3."""
+    outs = []
+    for chunk in ("1", "3", None):
+        env = {k: v for k, v in os.environ.items() if k != "DTO_WIDE_KMUL_S"}
+        if chunk is not None:
+            env["DTO_WIDE_KMUL_S"] = chunk
+        path = tmp_path / f"kv_{chunk}.bin"
+        r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [os.path.abspath(__file__), str(path)],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (chunk, r.returncode, r.stdout[-2000:], r.stderr[-2000:])   # (no further child after a failure)
+        with open(path, "rb") as f:
+            outs.append(np.load(f))
+    assert outs[0].shape == (B, (CHUNK_T - 1) * 129 + 64) and np.all(np.isfinite(outs[0]))
+    assert np.array_equal(outs[0], outs[2]), "1 stage per workgroup differs from the default"
+    assert np.array_equal(outs[1], outs[2]), "3 stages per workgroup differ from the default"
 
 
 def test_kkt_multiply_per_instance_parameters():
@@ -232,3 +281,7 @@ def test_kkt_multiply_leaves_the_factor_alone():
     back = _multiply(s, first, nz, nc)
     for i, K in enumerate(c["Ks"]):
         assert np.max(np.abs(back[i] - V[i])) <= 1e-8 * np.max(np.abs(first[i])) * np.max(np.sum(np.abs(K), axis=1)), i
+
+
+if __name__ == "__main__":
+    _chunk_child(sys.argv[1])

@@ -109,6 +109,66 @@ def test_wide_linear_solver_matches_dense_solves(m, T, B, dw, sig):
         _check_solves(s, Ks, rng, nz, nc, 1e-8)
 
 
+def _padded(a, ld):
+    """[B][ld] with NaN in every padding entry"""
+    out = np.full((a.shape[0], ld), np.nan)
+    out[:, :a.shape[1]] = a
+    return out
+
+
+def test_wide_linear_solver_padded_leading_dimensions():
+    """dto_kkt_assemble copies its five inputs row by row with the caller's leading dimensions, dto_kkt_solve reads and writes with
+    four more: all nine above the row lengths and all different, NaN in every padding entry (a read one would reach the factor or
+    the solution), NaN-filled outputs whose padding must stay NaN.  Bit-identical to the tight call on the same data, and within
+    1e-8 of the dense solve."""
+    import torch
+    import dto_amd
+    from dto_amd import problems as P
+    from oracle.padded_model import PaddedAcrobot
+    T, B, dw, dc = 4, 2, 2.0, 1e-5
+    p = P.build_acrobot_padded(T=T, parameters=(1.3, 0.7))
+    s = dto_amd.Solver(p["dynamics"], p["objective"], p["constraints"], p["bounds"], evaluate_hessian=True,
+                       parameters=p["parameters"], name="acrobot_padded_par")
+    nz, nc, nw = s.nlp.num_variables, s.nlp.num_constraint, s.nlp.num_parameters
+    pairs = [(0.8, 1.5), (1.6, 0.4)]
+    W = np.array([np.tile(pr, T) for pr in pairs])
+    assert W.shape == (B, nw)
+    rng = np.random.default_rng(91)
+    Z, MU = rng.random((B, nz)), rng.random((B, nc))
+    SX, SC = rng.random((B, nz)) * 3.0, rng.random((B, nc)) * 0.5
+    SX[:, ::3] = 0.0
+    RX, RC = rng.standard_normal((B, nz)), rng.standard_normal((B, nc))
+    ok, neg = _assemble_factor(s, Z, MU, dw, dc, SX, SC, W)
+    assert np.all(neg == nc) and np.all(ok == 1)
+    tight = _solve(s, RX, RC)
+    # the same system through padded arrays
+    ldx, ldmu, ldsx, ldsc, ldp = nz + 3, nc + 1, nz + 8, nc + 5, nw + 1
+    keep = [_dev(_padded(a, ld)) for a, ld in ((Z, ldx), (MU, ldmu), (SX, ldsx), (SC, ldsc), (W, ldp))]
+    s.kkt_assemble(keep[0].data_ptr(), B, ldx, keep[1].data_ptr(), ldmu, dw, dc, sigma_x_ptr=keep[2].data_ptr(), ldsx=ldsx,
+                   sigma_c_ptr=keep[3].data_ptr(), ldsc=ldsc, params_ptr=keep[4].data_ptr(), ldp=ldp)
+    ok, neg = s.kkt_factor()
+    assert np.all(neg == nc) and np.all(ok == 1)
+    ldrx, ldrc, ldox, ldoc = nz + 5, nc + 3, nz + 7, nc + 2
+    dRX, dRC = _dev(_padded(RX, ldrx)), _dev(_padded(RC, ldrc))
+    oX = torch.full((B, ldox), float("nan"), device="cuda", dtype=torch.float64)
+    oC = torch.full((B, ldoc), float("nan"), device="cuda", dtype=torch.float64)
+    s.kkt_solve(dRX.data_ptr(), ldrx, dRC.data_ptr(), ldrc, oX.data_ptr(), ldox, oC.data_ptr(), ldoc)
+    torch.cuda.synchronize()
+    oX, oC = oX.cpu().numpy(), oC.cpu().numpy()
+    assert np.all(np.isnan(oX[:, nz:])) and np.all(np.isnan(oC[:, nc:])), "the padding of the outputs must stay untouched"
+    assert np.all(np.isfinite(tight[0])) and np.all(np.isfinite(tight[1]))
+    assert np.array_equal(oX[:, :nz], tight[0]) and np.array_equal(oC[:, :nc], tight[1])
+    for b in range(B):
+        K = _dense(PaddedAcrobot(64, 1, pairs[b]), T, Z[b], MU[b], dw, dc, SX[b], SC[b])[0]
+        eig = np.linalg.eigvalsh(K)
+        assert (int(np.sum(eig > 0)), int(np.sum(eig < 0))) == (nz, nc), "test point must be quasi-definite; raise dw"
+        sol = np.linalg.solve(K, np.concatenate([RX[b], RC[b]]))
+        scale = np.max(np.abs(sol))
+        ex, ec = np.max(np.abs(oX[b, :nz] - sol[:nz])), np.max(np.abs(oC[b, :nc] - sol[nz:]))
+        print(f"  instance {b}: error {ex:.2e} / {ec:.2e}, solution scale {scale:.2e}")
+        assert ex <= 1e-8 * scale and ec <= 1e-8 * scale, (b, ex, ec, scale)
+
+
 def test_wide_linear_solver_agrees_with_the_newton_step():
     """sigmas NULL and the right-hand side of the Newton system (-[grad L; c], what dense_kkt returns): dto_kkt_solve must give
     the step of dto_kkt_step_batch at the same point, 1e-8 of the solution scale."""

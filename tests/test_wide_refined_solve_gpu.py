@@ -12,8 +12,8 @@ about 25 times above it, which leaves room for the last-bit differences between 
 entries.  Forward error after two passes: the project's 1e-8 of max |solution| for every instance, the
 indefinite ones included (condition numbers <= 3.4e3 times the omega bar is 5e-11).
 
-test_refined_backward_and_forward_error prints omega and the forward error for passes = 0 / 1 / 2 before it asserts; no MI355X
-run of this file exists yet (DESIGN.md section 4.3 says so where the table belongs).
+test_refined_backward_and_forward_error prints omega and the forward error for passes = 0 / 1 / 2 before it asserts; DESIGN.md
+section 4.3 holds the table of the first MI355X run.
 """
 import numpy as np
 import pytest
@@ -152,6 +152,35 @@ def test_refined_backward_and_forward_error(name):
               f"forward error 0/1/2 = {fe[0]:.2e} / {fe[1]:.2e} / {fe[2]:.2e}, bar {(q + 1) * 2.0 ** -53:.2e}")
         assert om[2] <= (q + 1) * 2.0 ** -53, (name, b, om, q)
         assert fe[2] <= 1e-8, (name, b, fe)
+
+
+def test_refined_padded_leading_dimensions():
+    """kkt_solve_refined(passes=2) with four different leading dimensions above the row lengths: NaN in every padding entry of the
+    right-hand side, NaN-filled outputs whose padding must stay NaN (the passes read the right-hand side again and update the
+    solution in place, each with the caller's strides).  Bit-identical to the tight call, within 1e-8 of the dense solve."""
+    import torch
+    c = _system("qd_3_5")
+    s = _solver(c["m"], c["T"])
+    nz, nc, B = c["nz"], c["nc"], c["B"]
+    _assemble_factor(s, c)
+    tight = _refined(s, c["R"], nz, nc, 2)
+    ldrx, ldrc, ldsx, ldsc = nz + 5, nc + 3, nz + 7, nc + 2
+    hX, hC = np.full((B, ldrx), np.nan), np.full((B, ldrc), np.nan)
+    hX[:, :nz], hC[:, :nc] = c["R"][:, :nz], c["R"][:, nz:]
+    dRX, dRC = _dev(hX), _dev(hC)
+    oX = torch.full((B, ldsx), float("nan"), device="cuda", dtype=torch.float64)
+    oC = torch.full((B, ldsc), float("nan"), device="cuda", dtype=torch.float64)
+    s.kkt_solve_refined(dRX.data_ptr(), ldrx, dRC.data_ptr(), ldrc, oX.data_ptr(), ldsx, oC.data_ptr(), ldsc, 2)
+    torch.cuda.synchronize()
+    oX, oC = oX.cpu().numpy(), oC.cpu().numpy()
+    assert np.all(np.isnan(oX[:, nz:])) and np.all(np.isnan(oC[:, nc:])), "the padding of the outputs must stay untouched"
+    sol = np.concatenate([oX[:, :nz], oC[:, :nc]], axis=1)
+    assert np.all(np.isfinite(tight)) and np.array_equal(sol, tight)
+    for b in range(B):
+        scale = np.max(np.abs(c["dense"][b]))
+        fe = float(np.max(np.abs(sol[b] - c["dense"][b])) / scale)
+        print(f"  instance {b}: forward error {fe:.2e}")
+        assert fe <= 1e-8, (b, fe)
 
 
 def test_refined_residual_norm():
