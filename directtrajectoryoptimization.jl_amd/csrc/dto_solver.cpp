@@ -3812,14 +3812,24 @@ int dto_kkt_factor(dto_problem* h, int32_t* inertia_ok, int32_t* num_negative, v
   return DTO_OK;
 }
 
+// The checks of the entry points that take vectors against the assembled system, in the order the callers report them: has
+// dto_kkt_assemble been called (on the path of this handle), `bad` (the entry point's own check of nrhs or passes: its message,
+// or nullptr), null vectors, leading dimensions.  (in, out): the vectors of the variables and of the constraint rows.
+static int check_kkt_vectors(const Problem* p, const char* bad, const double* in_x, int64_t ldix, const double* in_c, int64_t ldic,
+                             const double* out_x, int64_t ldox, const double* out_c, int64_t ldoc) {
+  if (!p || (p->vt->launch_wide ? !p->wide_kkt || !p->wide_kkt->assembled : !p->solver || !p->solver->assembled))
+    return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (bad) return set_error(DTO_ERR_INVALID, bad);
+  if (!in_x || !out_x || (p->L.Nc > 0 && (!in_c || !out_c))) return set_error(DTO_ERR_INVALID, "null argument");
+  if (ldix < p->L.Nz || ldox < p->L.Nz || ldic < p->L.Nc || ldoc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  return DTO_OK;
+}
+
 int dto_kkt_solve(dto_problem* h, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, double* sol_x,
                   int64_t ldsx, double* sol_c, int64_t ldsc, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
-  const bool wide = p && p->vt->launch_wide;
-  if (!p || (wide ? !p->wide_kkt || !p->wide_kkt->assembled : !p->solver || !p->solver->assembled))
-    return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
-  if (!rhs_x || !sol_x || (p->L.Nc > 0 && (!rhs_c || !sol_c))) return set_error(DTO_ERR_INVALID, "null argument");
-  if (ldrx < p->L.Nz || ldsx < p->L.Nz || ldrc < p->L.Nc || ldsc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (int bad = check_kkt_vectors(p, nullptr, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc)) return bad;
+  const bool wide = p->vt->launch_wide != nullptr;
   if (wide) return dto::wide_kkt_solve(p, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, (hipStream_t)stream);
   hipStream_t st = (hipStream_t)stream;
   dto_kkt_args a;
@@ -3845,11 +3855,7 @@ int dto_kkt_solve_multi(dto_problem* h, int64_t nrhs, const double* rhs_x, int64
   int rc = p->ensure_device();   // (allocates the tables of the handle once, launches nothing)
   if (rc) return rc;
   const bool wide = p->vt->launch_wide != nullptr;
-  if (wide ? !p->wide_kkt || !p->wide_kkt->assembled : !p->solver || !p->solver->assembled)
-    return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
-  if (nrhs < 1) return set_error(DTO_ERR_INVALID, "nrhs < 1");
-  if (!rhs_x || !sol_x || (p->L.Nc > 0 && (!rhs_c || !sol_c))) return set_error(DTO_ERR_INVALID, "null argument");
-  if (ldrx < p->L.Nz || ldsx < p->L.Nz || ldrc < p->L.Nc || ldsc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if ((rc = check_kkt_vectors(p, nrhs < 1 ? "nrhs < 1" : nullptr, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc))) return rc;
   if (wide) return dto::wide_kkt_solve_multi(p, nrhs, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, (hipStream_t)stream);
   // lane-per-instance path: no stored factor, so nrhs passes of the single solve -- right-hand side r of every instance is a
   // batch of its own with the rows nrhs apart
@@ -3870,9 +3876,7 @@ int dto_kkt_multiply(dto_problem* h, const double* v_x, int64_t ldvx, const doub
   if (!p->vt->launch_wide)
     return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_multiply: tile path only (the lane-per-instance path keeps no assembled system: its sweeps "
                                           "rebuild the stage blocks in registers)");
-  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
-  if (!v_x || !out_x || (p->L.Nc > 0 && (!v_c || !out_c))) return set_error(DTO_ERR_INVALID, "null argument");
-  if (ldvx < p->L.Nz || ldox < p->L.Nz || ldvc < p->L.Nc || ldoc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if ((rc = check_kkt_vectors(p, nullptr, v_x, ldvx, v_c, ldvc, out_x, ldox, out_c, ldoc))) return rc;
   return dto::wide_kkt_multiply(p, v_x, ldvx, v_c, ldvc, out_x, ldox, out_c, ldoc, (hipStream_t)stream);
 }
 
@@ -3885,10 +3889,8 @@ int dto_kkt_solve_refined(dto_problem* h, int passes, const double* rhs_x, int64
   if (!p->vt->launch_wide)
     return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_solve_refined: tile path only (the lane-per-instance path stores no factor; its solver "
                                           "refines through dto_options.kkt_refinement)");
-  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
-  if (passes < 0 || passes > 4) return set_error(DTO_ERR_INVALID, "passes outside 0..4");
-  if (!rhs_x || !sol_x || (p->L.Nc > 0 && (!rhs_c || !sol_c))) return set_error(DTO_ERR_INVALID, "null argument");
-  if (ldrx < p->L.Nz || ldsx < p->L.Nz || ldrc < p->L.Nc || ldsc < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if ((rc = check_kkt_vectors(p, passes < 0 || passes > 4 ? "passes outside 0..4" : nullptr, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc)))
+    return rc;
   return dto::wide_kkt_solve_refined(p, passes, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, resid, (hipStream_t)stream);
 }
 

@@ -12,7 +12,7 @@
 // Stage t couples (x_t, u_t, lam_t) with y = x_{t+1}.  Elimination order inside a stage: u (scalar pivots),
 // x (A = L_A D_A L_A'), lam (-(D + F~ D_A^-1 F~') = -L_M D_M L_M'); the Schur complement
 //     P' = YY - V~' D_A^-1 V~ + E~' D_M^-1 E~          (F~ = F L_A^-T, V~ = L_A^-1 V, E~ = L_M^-1 (E - F~ D_A^-1 V~))
-// is carried to stage t+1.  Factors go to HBM for the backward sweep (same kernel, same workgroup).
+// is carried to stage t+1.  Factors go to HBM for the backward sweep (k_wide_bwd, the next launch; same workgroup).
 // Inertia = number of negative pivots (Sylvester), must equal the number of constraints.
 #pragma once
 
@@ -93,9 +93,6 @@ namespace wide {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-#ifndef DTO_WIDE_LDL_RANK1
-#define DTO_WIDE_LDL_RANK1 1   // 0: the blocked LDL^T with one-wavefront diagonal tiles (rounds 1-3), kept for A/B runs
-#endif
 #ifndef DTO_WIDE_PROFILE
 #define DTO_WIDE_PROFILE 0     // 1: cycle stamps of workgroup 0 compiled in (tools/wide_profile.py builds its plugin with it)
 #endif
@@ -109,12 +106,6 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 #ifndef DTO_WIDE_DBG_JITTER
 #define DTO_WIDE_DBG_JITTER 0  // 1: every wavefront sleeps a pseudo-random time after each barrier: a hand-off that is not ordered fails
 #endif
-#ifndef DTO_WIDE_SPLIT_BWD
-#define DTO_WIDE_SPLIT_BWD 1   // 1: the backward sweep is its own kernel (k_wide_bwd) that prefetches the next stage's factor record
-#endif                         //    into registers while it works on the current one; 0: the tail of k_wide_step (rounds 1-4)
-#ifndef DTO_WIDE_PACK_L
-#define DTO_WIDE_PACK_L DTO_WIDE_SPLIT_BWD   // 1: the two triangular factors of a stage go to the record as their ten lower 16 x 16
-#endif                                        //    tiles (2 560 instead of 4 160 doubles each); needs the split backward sweep
 #ifndef DTO_WIDE_LDL_INLINE
 #define DTO_WIDE_LDL_INLINE __attribute__((noinline))
 #endif
@@ -129,14 +120,14 @@ struct Dims {
   static constexpr int LI_LD = TB + 1;
   static constexpr int LI = NT * TB * LI_LD;   // inverses of the unit-lower diagonal tiles
   // factor record of one stage in HBM
-  // triangular factors: lower tiles only (DTO_WIDE_PACK_L), tile-major [NT (NT + 1) / 2][TB][TB]
-  static constexpr int LTILES = NT * (NT + 1) / 2, PKL = DTO_WIDE_PACK_L ? LTILES * TB * TB : MAT;
+  // triangular factors: their lower tiles only (2 560 instead of 4 160 doubles each), tile-major [NT (NT + 1) / 2][TB][TB]
+  static constexpr int LTILES = NT * (NT + 1) / 2, PKL = LTILES * TB * TB;
   static constexpr int F_LA = 0, F_FT = PKL, F_VT = PKL + MAT, F_LM = PKL + 2 * MAT, F_ET = 2 * PKL + 2 * MAT, F_VEC = 2 * PKL + 3 * MAT;
   // vectors: D_A^-1, D_M^-1, bx~, bd^, the NU action rows (A_xu, F_u, V_u after the elimination inside the action block), cost
-  // gradient [N + 8], scalars of the action block (V_SC: 1 / pivot [NU], reduced right-hand side [NU], unit-lower factor [NU][NU])
+  // gradient [N + 8], NSC scalars of the action block (V_SC: 1 / pivot [NU], reduced right-hand side [NU], unit-lower factor [NU][NU])
   static constexpr int V_DA = 0, V_DM = N, V_BX = 2 * N, V_BD = 3 * N, V_AU = 4 * N, V_FU = V_AU + NU * N, V_VU = V_FU + NU * N,
-                       V_GC = V_VU + NU * N, V_SC = V_GC + N + 8;
-  static constexpr int FAC = F_VEC + V_SC + ((NU * (NU + 2) + 7) & ~7);
+                       V_GC = V_VU + NU * N, V_SC = V_GC + N + 8, NSC = (NU * (NU + 2) + 7) & ~7;
+  static constexpr int FAC = F_VEC + V_SC + NSC;
 };
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
@@ -226,80 +217,11 @@ __device__ __forceinline__ void mm_row4(d4 (&c)[4], const double* A, int m0, con
   }
 }
 
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_readlane(lo, lane);
-  hi = __builtin_amdgcn_readlane(hi, lane);
-  return __hiloint2double(hi, lo);
-}
-
-// ---- unblocked LDL^T of the 16x16 diagonal tile at (o, o) by one wavefront: lane i (< 16) holds row i of the
-//      symmetric tile in registers; values travel between lanes by v_readlane (lane indices are literals after
-//      unrolling), each broadcast value is consumed by the next instruction.  Step j, critical path: reciprocal of the
-//      lane's own diagonal -> scaled pivot row s_c = a_jc / d_j (which is also L[c][j]) -> broadcast -> one FMA.
-//      The inverse X of the unit-lower factor (lane c = column c) is built row by row inside the same loop: row j+1
-//      of L is final after step j, and its work fills the latency gaps of the factorisation chain.
-//      d/dinv get the pivots; cnt[0] += negative pivots, cnt[1] |= tiny pivot seen.
-__device__ __forceinline__ void diag_tile(double* Mx, int ld, int o, double* d, double* dinv, double* LIk, int li_ld,
-                                          double piv_tol, int* cnt, long long* prof = nullptr) {
-  const int l = lane_id();
-  const int i = l & 15;
-  long long tq_ = prof ? clock64() : 0;
-  double a[TB];
-#pragma unroll
-  for (int c = 0; c < TB; ++c) a[c] = (c <= i) ? Mx[(o + i) * ld + o + c] : Mx[(o + c) * ld + o + i];
-  const double diag0 = fabs(Mx[(o + i) * ld + o + i]);
-  if (prof && threadIdx.x == 0) { const long long t_ = clock64(); prof[24] += t_ - tq_; tq_ = t_; }
-  int nneg = 0, tiny = 0;
-  double dj_mine = 0.0, idj_mine = 0.0;
-  double X[TB];
-  X[0] = (l == 0) ? 1.0 : 0.0;
-#pragma unroll
-  for (int j = 0; j < TB; ++j) {
-    const double pv = a[j];
-    double rc = __builtin_amdgcn_rcp(pv);
-    rc = fma(fma(-pv, rc, 1.0), rc, rc);
-    rc = fma(fma(-pv, rc, 1.0), rc, rc);
-    const double aij = a[j];
-#pragma unroll
-    for (int c = j + 1; c < TB; ++c) {
-      const double sc = readlane_d(a[c] * rc, j);
-      if (i > j) a[c] -= aij * sc;
-    }
-    const double dj = readlane_d(pv, j);
-    const double d0 = readlane_d(diag0, j);
-    const double rcj = readlane_d(rc, j);
-    if (!(fabs(dj) > piv_tol * fmax(1.0, d0))) tiny = 1;
-    if (dj < 0.0) ++nneg;
-    if (l == j) { dj_mine = pv; idj_mine = rc; }
-    if (i > j) a[j] = aij * rcj;
-    // row j+1 of the inverse: X[j+1][c] = -sum_{k<=j} L[j+1][k] X[k][c]
-    if (j + 1 < TB) {
-      double sacc = 0.0;
-#pragma unroll
-      for (int k = 0; k <= j; ++k) sacc += readlane_d(a[k], j + 1) * X[k];
-      X[j + 1] = (l == j + 1) ? 1.0 : (l < j + 1 ? -sacc : 0.0);
-    }
-  }
-  if (prof && threadIdx.x == 0) { const long long t_ = clock64(); prof[25] += t_ - tq_; tq_ = t_; }
-  if (l < TB) {
-    d[o + l] = dj_mine;
-    dinv[o + l] = idj_mine;
-#pragma unroll
-    for (int k = 0; k < TB - 1; ++k)
-      if (k < l) Mx[(o + l) * ld + o + k] = a[k];
-#pragma unroll
-    for (int r = 0; r < TB; ++r) LIk[r * li_ld + l] = X[r];
-  }
-  if (l == 0) { cnt[0] += nneg; cnt[1] |= tiny; }
-  if (prof && threadIdx.x == 0) { const long long t_ = clock64(); prof[26] += t_ - tq_; tq_ = t_; }
-}
-
 // barrier for phases that exchange data through LDS only: __syncthreads() also waits for every outstanding global STORE of the
 // wavefront (the factor records streaming to HBM) -- a full memory round trip at each of the barriers that follow a copy
 // INVARIANT: only LDS data is handed from thread to thread across this barrier.  No global write of k_wide_step is read
 // by another thread of the same launch (the factor records are consumed by k_wide_bwd, the next launch); a hand-off through
-// global memory needs __syncthreads() (+ a fence), as the in-kernel backward sweep (DTO_WIDE_SPLIT_BWD = 0) does.
+// global memory would need __syncthreads() (+ a fence), as the in-kernel backward sweep of rounds 1-4 did.
 #if DTO_WIDE_DBG_JITTER
 __device__ __forceinline__ void dbg_jitter() {
   // xorshift of (wavefront, clock): 0..63 x 64 cycles of s_sleep, different in every wavefront at every barrier
@@ -332,57 +254,15 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// ---- blocked right-looking LDL^T of the N x N matrix in LDS (lower tiles), all WG threads.
-//      On exit: strict lower part = L, d/dinv = pivots, LI = inverses of the unit-lower diagonal tiles.
-template <int N>
-__device__ __forceinline__ void ldl_blocked(double* Mx, double* d, double* dinv, double* LI, double piv_tol, int* cnt, long long* prof = nullptr) {
-  using D = Dims<N>;
-  constexpr int LD = D::LD, NT = D::NT;
-  const int w = wave_id();
-  for (int kb = 0; kb < NT; ++kb) {
-    const int o = kb * TB;
-    double* LIk = LI + kb * TB * D::LI_LD;
-    long long t0_ = 0;
-    if (prof && threadIdx.x == 0) t0_ = clock64();
-    if (w == 0) diag_tile(Mx, LD, o, d, dinv, LIk, D::LI_LD, piv_tol, cnt, prof);
-    if (prof && threadIdx.x == 0) { const long long t1_ = clock64(); prof[20] += t1_ - t0_; t0_ = t1_; }
-    __syncthreads();
-    if (prof && threadIdx.x == 0) { const long long t1_ = clock64(); prof[21] += t1_ - t0_; t0_ = t1_; }
-    // panel: L(ib,kb) = A(ib,kb) * Linv' * D^-1
-    for (int ib = kb + 1 + w; ib < NT; ib += 4) {
-      d4 c = {0.0, 0.0, 0.0, 0.0};
-      c = mm_nt(c, Mx + o, LD, ib * TB, LIk, D::LI_LD, 0, 0, TB, nullptr, 1.0);
-      const double sc = dinv[o + (lane_id() & 15)];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) c[j] *= sc;
-      tile_store(Mx, LD, ib * TB, o, c);
-    }
-    __syncthreads();
-    if (prof && threadIdx.x == 0) { const long long t1_ = clock64(); prof[22] += t1_ - t0_; t0_ = t1_; }
-    // trailing update of the lower tiles: A(ib,jb) -= L(ib,kb) D_kb L(jb,kb)'
-    int idx = 0;
-    for (int ib = kb + 1; ib < NT; ++ib) {
-      for (int jb = kb + 1; jb <= ib; ++jb, ++idx) {
-        if ((idx & 3) != w) continue;
-        d4 c = tile_load(Mx, LD, ib * TB, jb * TB);
-        c = mm_nt(c, Mx + o, LD, ib * TB, Mx + o, LD, jb * TB, 0, TB, d + o, -1.0);
-        tile_store(Mx, LD, ib * TB, jb * TB, c);
-      }
-    }
-    __syncthreads();
-    if (prof && threadIdx.x == 0) { const long long t1_ = clock64(); prof[23] += t1_ - t0_; t0_ = t1_; }
-  }
-}
-
 // ---- right-looking LDL^T of the N x N matrix in LDS with the matrix held in REGISTERS (round 4).
-//      The blocked form above spends its time in the eight 16 x 16 diagonal tiles of a stage, each factorised by ONE wavefront
-//      through v_readlane broadcasts while the other three wait at a barrier (profiles/r04/wide_phase_cycles_*: 15.6 k cycles per
-//      tile, 125 k of the 363 k cycles of a stage).  Here all 256 threads hold a 4 x 4 comb of the symmetric matrix
+//      The blocked form of rounds 1-3 spent its time in the eight 16 x 16 diagonal tiles of a stage, each factorised by ONE
+//      wavefront through v_readlane broadcasts while the other three waited at a barrier (profiles/r04/wide_phase_cycles_*: 15.6 k
+//      cycles per tile, 125 k of the 363 k cycles of a stage).  Here all 256 threads hold a 4 x 4 comb of the symmetric matrix
 //      (rows ti + 16 a, columns tj + 16 b: 16 doubles per thread) for the whole factorisation; step k costs one exchange of
 //      column k through a 64-double LDS buffer (ping-pong: one barrier per step), nine LDS reads and at most sixteen
 //      multiply-adds per thread -- the chain is 64 short steps instead of 8 long tiles plus 24 barriers.  L (strict lower part),
 //      the pivots and the inverses of the unit-lower diagonal tiles (for the MFMA triangular solves that follow) are written back
-//      at the end; negative / tiny pivots are counted like in ldl_blocked (same test, same order of pivots).
+//      at the end; negative / tiny pivots are counted in the order of the pivots.
 // (out of line, LDS pointers by address space: the caller's kernel is already at 256 + 182 registers, inlined three times the
 // comb pushed it into scratch)
 typedef __attribute__((address_space(3))) double lds_double;
@@ -666,8 +546,8 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   return __hiloint2double(hi, lo);
 }
 // v <- L^-1 v (unit lower, strict lower part of Lm), one wavefront, lanes = rows.  Sixteen columns of the lane's row are loaded
-// (ldl_rank1 leaves zeros on and above the diagonal; with the blocked factorisation they are masked to the strict lower part:
-// 126 lane masks that the compiler hoists out of the stage loop and spills from the scalar registers) ahead of the sixteen dependent steps that use them: a step is two v_readlane and one fma
+// (unmasked: ldl_rank1 leaves zeros on and above the diagonal) ahead of the sixteen dependent steps that use them: a step is two
+// v_readlane and one fma
 // (rounds 1-4: one LDS load, a ds_bpermute broadcast and a predicated fma per step, ~190 cycles each at one wavefront per SIMD).
 template <int N>
 __device__ __forceinline__ void trsv_lower(const double* Lm, double* v) {
@@ -679,7 +559,7 @@ __device__ __forceinline__ void trsv_lower(const double* Lm, double* v) {
   for (int kb = 0; kb < N; kb += 16) {
     double col[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) col[j] = (DTO_WIDE_LDL_RANK1 || l > kb + j) ? Lm[l * LD + kb + j] : 0.0;
+    for (int j = 0; j < 16; ++j) col[j] = Lm[l * LD + kb + j];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       if (kb + j < N - 1) mine = __builtin_fma(-col[j], readlane_f64(mine, kb + j), mine);
@@ -698,7 +578,7 @@ __device__ __forceinline__ void trsv_lower_t(const double* Lm, double* v) {
   for (int kb = N - 16; kb >= 0; kb -= 16) {
     double row[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) row[j] = (DTO_WIDE_LDL_RANK1 || l < kb + j) ? Lm[(kb + j) * LD + l] : 0.0;
+    for (int j = 0; j < 16; ++j) row[j] = Lm[(kb + j) * LD + l];
 #pragma unroll
     for (int j = 15; j >= 0; --j) {
       if (kb + j >= 1) mine = __builtin_fma(-row[j], readlane_f64(mine, kb + j), mine);
@@ -707,20 +587,8 @@ __device__ __forceinline__ void trsv_lower_t(const double* Lm, double* v) {
   v[l] = mine;
 }
 
-// whole-matrix copies between LDS and the factor record in HBM, 16 bytes per lane (MAT is even and every matrix starts
-// on a 16-byte boundary: MAT * 8 = 33 280 bytes)
-template <int MAT>
-__device__ __forceinline__ void copy_mat(double* dst, const double* src) {
-  static_assert(MAT % 2 == 0, "matrix size must be even for 16-byte copies");
-  // (left to the compiler's own pipelining: all nine pieces of a thread in registers at once made this kernel spill, three at a
-  // time with the loop kept rolled was slower than this plain form -- 65 k against 38 k cycles for the four loads of a stage of
-  // the backward sweep, profiles/r04/wide_phase_cycles.txt)
-  const double2* s2 = reinterpret_cast<const double2*>(src);
-  double2* d2 = reinterpret_cast<double2*>(dst);
-  for (int i = threadIdx.x; i < MAT / 2; i += WG) d2[i] = s2[i];
-}
-
-// LDS -> factor record: three pieces per thread in flight (an LDS round trip per piece otherwise: ~130 cycles x 9 x 5 matrices)
+// LDS -> factor record, a whole matrix in 16-byte pieces (MAT is even and every matrix of the record starts on a 16-byte
+// boundary): three pieces per thread in flight (an LDS round trip per piece otherwise: ~130 cycles x 9 x 5 matrices)
 template <int MAT>
 __device__ __forceinline__ void store_fac(double* dst, const double* src) {
   typedef double v2d __attribute__((ext_vector_type(2)));
@@ -761,7 +629,7 @@ __device__ __forceinline__ void store_ltiles(double* dst, const double* Mx) {
   for (int k = 0; k < NPL; ++k) d2[threadIdx.x + k * WG] = v[k];
 }
 
-// dot products over N terms, fully unrolled with four independent accumulators (LDS loads all in flight)
+// dot product over N terms, fully unrolled with four independent accumulators (LDS loads all in flight)
 template <int N>
 __device__ __forceinline__ double dot_rr(const double* a, const double* v) {
   double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
@@ -771,36 +639,6 @@ __device__ __forceinline__ double dot_rr(const double* a, const double* v) {
   }
 #pragma unroll
   for (int c = N & ~3; c < N; ++c) s0 += a[c] * v[c];   // (evaluator plugins of 17 .. 63 states: any N)
-  return (s0 + s1) + (s2 + s3);
-}
-template <int N>
-__device__ __forceinline__ double dot_rrs(const double* a, const double* v, const double* sc) {
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-  for (int c = 0; c < N; c += 4) {
-    s0 += a[c] * v[c] * sc[c]; s1 += a[c + 1] * v[c + 1] * sc[c + 1];
-    s2 += a[c + 2] * v[c + 2] * sc[c + 2]; s3 += a[c + 3] * v[c + 3] * sc[c + 3];
-  }
-  return (s0 + s1) + (s2 + s3);
-}
-// column of a row-major matrix (stride ld) against a vector
-template <int N>
-__device__ __forceinline__ double dot_cr(const double* a, int ld, const double* v) {
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-  for (int c = 0; c < N; c += 4) {
-    s0 += a[c * ld] * v[c]; s1 += a[(c + 1) * ld] * v[c + 1]; s2 += a[(c + 2) * ld] * v[c + 2]; s3 += a[(c + 3) * ld] * v[c + 3];
-  }
-  return (s0 + s1) + (s2 + s3);
-}
-template <int N>
-__device__ __forceinline__ double dot_crs(const double* a, int ld, const double* v, const double* sc) {
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-  for (int c = 0; c < N; c += 4) {
-    s0 += a[c * ld] * v[c] * sc[c]; s1 += a[(c + 1) * ld] * v[c + 1] * sc[c + 1];
-    s2 += a[(c + 2) * ld] * v[c + 2] * sc[c + 2]; s3 += a[(c + 3) * ld] * v[c + 3] * sc[c + 3];
-  }
   return (s0 + s1) + (s2 + s3);
 }
 __device__ __forceinline__ double wave_sum(double v) {
@@ -825,9 +663,6 @@ __device__ __forceinline__ double quad_sum(double v) {
 #endif
 #ifndef DTO_WIDE_RMW_UNROLL
 #define DTO_WIDE_RMW_UNROLL 2   // element-wise passes over the LDS matrices (rank-one terms of the actions): iterations in flight
-#endif
-#ifndef DTO_WIDE_DOTQ
-#define DTO_WIDE_DOTQ 15   // bit per site of the forward sweep (phases 2, 4, 8, 11) that uses the workgroup-wide dot products
 #endif
 #ifndef DTO_DOTQ_UNROLL
 #define DTO_DOTQ_UNROLL 2
@@ -953,7 +788,7 @@ struct WK {
 };
 
 // ---------------------------------------------------------------------------------------------------
-// the kernel: forward factor/solve sweep, terminal solve, backward sweep.  grid = B, block = 256.
+// the kernel: forward factor/solve sweep and terminal solve (the backward sweep is k_wide_bwd).  grid = B, block = 256.
 // ---------------------------------------------------------------------------------------------------
 // BAR: instantiation with the barrier terms of finite variable bounds (launch_wide picks it when the caller passes bound
 // multipliers); the plain KKT step carries none of that code
@@ -1138,7 +973,6 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         lds_barrier();
         DTO_WIDE_TICK(1);
         // ---- phase 2: residual from the constant part (variable Jacobian entries are still zero in MF/ME/fu)
-#if DTO_WIDE_DOTQ & 1
         {
           const double part = quad_sum(dotq_r<N>(MF, LD, xv) + dotq_r<N>(ME, LD, yv));
           if ((tid & 3) == 0) {
@@ -1149,14 +983,6 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
             bd[row] = -acc;
           }
         }
-#else
-        if (tid < N) {
-          double acc = nlf[tid] + fu[tid] * sc[0] + dot_rr<N>(MF + tid * LD, xv) + dot_rr<N>(ME + tid * LD, yv);
-#pragma unroll
-          for (int j = 1; j < NU; ++j) acc += fu[j * N + tid] * sc[j];
-          bd[tid] = -acc;
-        }
-#endif
         lds_barrier();
         DTO_WIDE_TICK(2);
         // ---- phase 3: variable Jacobian entries, Hessian blocks
@@ -1206,7 +1032,6 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         lds_barrier();
         DTO_WIDE_TICK(3);
         // ---- phase 4: gradient of the Lagrangian -> right-hand sides
-#if DTO_WIDE_DOTQ & 2
         {
           const double pf_ = quad_sum(dotq_c<N>(MF, LD, lamv)), pe_ = quad_sum(dotq_c<N>(ME, LD, lamv));
           if ((tid & 3) == 0) {
@@ -1215,13 +1040,6 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
             gyn[col] = pe_;
           }
         }
-#else
-        if (w == 0) {
-          bx[l] = -(gc[l] + gyp[l] + dot_cr<N>(MF + l, LD, lamv)) + byc[l] + (BAR ? brx[l] : 0.0);
-        } else if (w == 1) {
-          gyn[l] = dot_cr<N>(ME + l, LD, lamv);
-        }
-#endif
         if (w == 2) {
 #pragma unroll
           for (int j = 0; j < NU; ++j) {
@@ -1381,8 +1199,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         lds_barrier();
         DTO_WIDE_TICK(5);
         // ---- phase 6: A = L_A D_A L_A'
-        if (DTO_WIDE_LDL_RANK1) ldl_rank1<N>((lds_double*)MA, (lds_double*)dA, (lds_double*)dAi, (lds_double*)LI, (lds_double*)colb, (lds_double*)dg0, a.piv_tol, (lds_int*)cnt, (DTO_WIDE_PROFILE && blockIdx.x == 0) ? a.prof : nullptr);
-        else ldl_blocked<N>(MA, dA, dAi, LI, a.piv_tol, cnt, (DTO_WIDE_PROFILE && blockIdx.x == 0) ? a.prof : nullptr);
+        ldl_rank1<N>((lds_double*)MA, (lds_double*)dA, (lds_double*)dAi, (lds_double*)LI, (lds_double*)colb, (lds_double*)dg0, a.piv_tol, (lds_int*)cnt, (DTO_WIDE_PROFILE && blockIdx.x == 0) ? a.prof : nullptr);
         DTO_WIDE_TICK(6);
         // ---- phase 7: F~ = F L_A^-T (row tiles), V~ = L_A^-1 V (column tiles), bx~ = L_A^-1 bx
         if (w == 0) trsv_lower<N>(MA, bx);
@@ -1404,7 +1221,7 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           nf_ = (lo_b && lo_b[a.zoff[t + 1] + tid] == hi_b[a.zoff[t + 1] + tid]) ? 1.0 : 0.0;
           if (tid < NU) nu_ = z[a.zoff[t + 1] + N + tid];
         }
-        if (DTO_WIDE_PACK_L) store_ltiles<N>(fac + D::F_LA, MA); else store_fac<MAT>(fac + D::F_LA, MA);
+        store_ltiles<N>(fac + D::F_LA, MA);
         store_fac<MAT>(fac + D::F_FT, MF);
         store_fac<MAT>(fac + D::F_VT, MV);
         DTO_WIDE_TICK(24);
@@ -1434,14 +1251,10 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           for (int jb = 0; jb < NT; ++jb) tile_store(ME, LD, w * TB, jb * TB, eacc[jb]);
         }
         DTO_WIDE_TICK(26);
-#if DTO_WIDE_DOTQ & 4
         {
           const double part = quad_sum(dotq_rs<N>(MF, LD, bx, dAi));
           if ((tid & 3) == 0) tmp[tid >> 2] = bd[tid >> 2] - part;
         }
-#else
-        if (tid < N) tmp[tid] = bd[tid] - dot_rrs<N>(MF + tid * LD, bx, dAi);
-#endif
         if (pre_ && tid < N) {
           xv[tid] = nx_; yv[tid] = ny_; lamv[tid] = nl_; fxm[tid] = nf_;
           if (tid < NU) sc[tid] = nu_;
@@ -1461,13 +1274,12 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           int* cm = cnt + 2;  // scratch counters for M
           if (tid == 0) { cm[0] = 0; cm[1] = 0; }
           lds_barrier();
-          if (DTO_WIDE_LDL_RANK1) ldl_rank1<N>((lds_double*)MA, (lds_double*)dM, (lds_double*)dMi, (lds_double*)LI, (lds_double*)colb, (lds_double*)dg0, a.piv_tol, (lds_int*)cm);
-          else ldl_blocked<N>(MA, dM, dMi, LI, a.piv_tol, cm);
+          ldl_rank1<N>((lds_double*)MA, (lds_double*)dM, (lds_double*)dMi, (lds_double*)LI, (lds_double*)colb, (lds_double*)dg0, a.piv_tol, (lds_int*)cm);
           if (tid == 0) { cnt[0] -= cm[0]; cnt[1] |= cm[1]; }
         }
         DTO_WIDE_TICK(9);
         // ---- phase 10: E~ = L_M^-1 E'', bd^ = L_M^-1 bd~
-        if (DTO_WIDE_PACK_L) store_ltiles<N>(fac + D::F_LM, MA); else store_fac<MAT>(fac + D::F_LM, MA);
+        store_ltiles<N>(fac + D::F_LM, MA);
         if (w == 0) trsv_lower<N>(MA, bd);
         trsm_left_coltile<N>(ME, MA, LI, w);
         lds_barrier();
@@ -1499,14 +1311,10 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         for (int jb = 0; jb < NT; ++jb) macc[jb] = d4{0.0, 0.0, 0.0, 0.0};
         mm_row4<2, N>(macc, MV, w * TB, MV, dAi, -1.0);
         mm_row4<2, N>(macc, ME, w * TB, ME, dMi, 1.0);
-#if DTO_WIDE_DOTQ & 8
         {
           const double part = quad_sum(dotq_cs<N>(ME, LD, bd, dMi) - dotq_cs<N>(MV, LD, bx, dAi));
           if ((tid & 3) == 0) tmp[tid >> 2] = byn[tid >> 2] + part;
         }
-#else
-        if (tid < N) tmp[tid] = byn[tid] - dot_crs<N>(MV + tid, LD, bx, dAi) + dot_crs<N>(ME + tid, LD, bd, dMi);
-#endif
         lds_barrier();
 #pragma unroll
         for (int jb = 0; jb < NT; ++jb) tile_store(MA, LD, w * TB, jb * TB, macc[jb]);
@@ -1607,11 +1415,9 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           if (tid < N && fxm[tid] != 0.0) bx[tid] = 0.0;
           __syncthreads();
         }
-        if (DTO_WIDE_LDL_RANK1) ldl_rank1<N>((lds_double*)MA, (lds_double*)dA, (lds_double*)dAi, (lds_double*)LI, (lds_double*)colb, (lds_double*)dg0, a.piv_tol, (lds_int*)cnt);
-        else ldl_blocked<N>(MA, dA, dAi, LI, a.piv_tol, cnt);
+        ldl_rank1<N>((lds_double*)MA, (lds_double*)dA, (lds_double*)dAi, (lds_double*)LI, (lds_double*)colb, (lds_double*)dg0, a.piv_tol, (lds_int*)cnt);
         if constexpr (LIN) {
           // the terminal factor, record T-1 (allocated with the others, unused by the step: its solve is the code below)
-          static_assert(!LIN || (DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD), "k_wide_fsub reads packed triangular factors");
           double* facT = facb + (int64_t)t * D::FAC;
           store_ltiles<N>(facT + D::F_LA, MA);
           if (tid < N) facT[D::F_VEC + D::V_DA + tid] = dAi[tid];
@@ -1643,115 +1449,88 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
   DTO_WIDE_TICK(13);
   if (tid == 0) a.flags[b] = (cnt[0] == (int)a.Nc && cnt[1] == 0) ? 1 : 0;
   if constexpr (LIN) { if (tid == 0 && a.nneg) a.nneg[b] = cnt[0]; }
-#if DTO_WIDE_SPLIT_BWD
   // the backward sweep is k_wide_bwd (next launch on the same stream): it picks up the statistics from here
-  if (a.stats && tid < DTO_WIDE_NSTAT) a.stats[b * DTO_WIDE_NSTAT + tid] = stat[tid];
-  return;
-#endif
-  // ---- backward sweep: y = x_{t+1} is in yv.  The factor records were written by all threads of this workgroup.
-  __threadfence_block();
-  __syncthreads();
-  for (int t = a.T - 2; t >= 0; --t) {
-    const double* fac = facb + (int64_t)t * D::FAC;
-    const double* fv = fac + D::F_VEC;
-    copy_mat<MAT>(ME, fac + D::F_ET);
-    static_assert(DTO_WIDE_SPLIT_BWD || !DTO_WIDE_PACK_L, "the in-kernel backward sweep reads unpacked factors");
-    copy_mat<MAT>(MA, fac + D::F_LM);
-    copy_mat<MAT>(MF, fac + D::F_FT);
-    copy_mat<MAT>(MV, fac + D::F_VT);
-    if (tid < N) {
-      dAi[tid] = fv[D::V_DA + tid];
-      dMi[tid] = fv[D::V_DM + tid];
-      bx[tid] = fv[D::V_BX + tid];
-      bd[tid] = fv[D::V_BD + tid];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) {
-        au[j * N + tid] = fv[D::V_AU + j * N + tid];
-        fu[j * N + tid] = fv[D::V_FU + j * N + tid];
-        vu[j * N + tid] = fv[D::V_VU + j * N + tid];
-      }
-    }
-    __syncthreads();
-    DTO_WIDE_TICK(14);
-    // lam = L_M^-T D_M^-1 (E~ y - bd^)
-    if (tid < N) {
-      lamv[tid] = (dot_rr<N>(ME + tid * LD, yv) - bd[tid]) * dMi[tid];
-    }
-    __syncthreads();
-    if (w == 0) trsv_lower_t<N>(MA, lamv);
-    __syncthreads();
-    DTO_WIDE_TICK(15);
-    // x = L_A^-T D_A^-1 (bx~ - F~' lam - V~ y)
-    if (tid < N) {
-      xv[tid] = (bx[tid] - dot_cr<N>(MF + tid, LD, lamv) - dot_rr<N>(MV + tid * LD, yv)) * dAi[tid];
-    }
-    __syncthreads();
-    copy_mat<MAT>(MA, fac + D::F_LA);
-    __syncthreads();
-    if (w == 0) trsv_lower_t<N>(MA, xv);
-    __syncthreads();
-    if (tid < N) {
-      a.dz[b * a.lddz + a.zoff[t] + tid] = xv[tid];
-      a.dmu[b * a.lddmu + a.cdoff[t] + tid] = lamv[tid];
-    }
-    if (w == 1) {
-      // u_j = (bu_j - au_j'x - fu_j'lam - vu_j'y) / piv_j - sum_{k > j} L_u[k][j] u_k, last action first
-      double duv[NU];
-#pragma unroll
-      for (int j = NU - 1; j >= 0; --j) {
-        const double part = wave_sum(au[j * N + l] * xv[l] + fu[j * N + l] * lamv[l] + vu[j * N + l] * yv[l]);
-        double uj = (fv[D::V_SC + NU + j] - part) * fv[D::V_SC + j];
-#pragma unroll
-        for (int k = j + 1; k < NU; ++k) uj -= fv[D::V_SC + 2 * NU + k * NU + j] * duv[k];
-        duv[j] = uj;
-      }
-      double du = duv[0];   // lane j < NU: its own action
-#pragma unroll
-      for (int j = 1; j < NU; ++j) du = (l == j) ? duv[j] : du;
-      if (l < NU) a.dz[b * a.lddz + a.zoff[t] + N + l] = du;
-      if (a.stats) {
-        // gradient of the barrier objective along the step, fraction-to-the-boundary limits of this knot (x: lane, u: lane 0)
-        double brl = 0.0, ap = 1.0, ad = 1.0;
-        if (barrier) {
-          const int gi = a.zoff[t] + l;
-          const double xo = z[gi], lo = lo_b[gi], hi = hi_b[gi];
-          brl = wide_bar(xo, lo, hi, zlb[gi], zub[gi], mub).br;
-          wide_bar_step(xo, xv[l], lo, hi, zlb[gi], zub[gi], mub, taub, ap, ad);
-          if (l < NU) {
-            const int gu = a.zoff[t] + N + l;
-            const double uo = z[gu], ulo = lo_b[gu], uhi = hi_b[gu];
-            wide_bar_step(uo, du, ulo, uhi, zlb[gu], zub[gu], mub, taub, ap, ad);
-          }
-          ap = wave_min(ap); ad = wave_min(ad);
-        }
-        double gl = (fv[D::V_GC + l] - brl) * xv[l];
-        if (l < NU) {
-          double bru = 0.0;
-          if (barrier) {
-            const int gu = a.zoff[t] + N + l;
-            bru = wide_bar(z[gu], lo_b[gu], hi_b[gu], zlb[gu], zub[gu], mub).br;
-          }
-          gl += (fv[D::V_GC + N + l] - bru) * du;
-        }
-        const double gpart = wave_sum(gl);
-        if (l == 0) {
-          if (barrier) { stat[DTO_WIDE_APMAX] = fmin(stat[DTO_WIDE_APMAX], ap); stat[DTO_WIDE_ADMAX] = fmin(stat[DTO_WIDE_ADMAX], ad); }
-          stat[4] += gpart;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid < N) yv[tid] = xv[tid];
-    __syncthreads();
-    DTO_WIDE_TICK(16);
-  }
   if (a.stats && tid < DTO_WIDE_NSTAT) a.stats[b * DTO_WIDE_NSTAT + tid] = stat[tid];
 }
 
 // ---------------------------------------------------------------------------------------------------
-// backward sweep as a kernel of its own (DTO_WIDE_SPLIT_BWD): same arithmetic as the tail of k_wide_step, but the factor
-// record of stage t-1 travels from HBM into REGISTERS while stage t is worked on from LDS (45 x 16 bytes per thread: five
-// matrices; inside k_wide_step there were no registers for that -- 256 + 240 in use -- and no LDS for a second stage).
+// A stage's factor record on its way HBM -> registers -> LDS: the one definition of how the record (Dims<N, NU>) travels in
+// k_wide_bwd, k_wide_fsub, k_wide_fsub_multi and k_wide_bwd_multi.  Each of them requests the record of the stage it works on
+// next into registers, works on the current one from LDS and writes the registers to LDS at the top of the next stage.  The
+// kernel keeps the register arrays, the order of its loads (its `issue`) and what only it reads: right-hand sides, workspace
+// panels, V_BX / V_BD / V_GC.  A kernel instantiates the struct once with its thread index.  (Members of a struct that holds
+// tid reproduce the instruction streams that the kernels' own lambdas gave; DESIGN.md section 4.3 lists the one exception.)
+// ---------------------------------------------------------------------------------------------------
+template <int N, int NU>
+struct RecordStage {
+  using D = Dims<N, NU>;
+  typedef double v2d __attribute__((ext_vector_type(2)));   // (HIP's double2 is a class: arrays of it stay in scratch)
+  static constexpr int NP = (D::MAT / 2 + WG - 1) / WG;        // 16-byte pieces of a full matrix per thread
+  static constexpr int NPL = D::LTILES * TB * TB / 2 / WG;     // pieces of a packed triangular factor per thread
+  static_assert(NPL * WG * 2 == D::LTILES * TB * TB, "whole pieces per thread");
+  static_assert(D::NSC <= 32, "scalars of the action block: one lane each");
+  const int tid;
+
+  // full matrices F~, V~, E~ (the last piece of a thread may lie past the end)
+  __device__ __forceinline__ void load_mat(v2d (&r)[NP], const double* src) const {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < D::MAT / 2) r[k] = s2[i];
+    }
+  }
+  __device__ __forceinline__ void store_mat(double* dst, const v2d (&r)[NP]) const {
+    v2d* d2 = reinterpret_cast<v2d*>(dst);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + k * WG;
+      if (i < D::MAT / 2) d2[i] = r[k];
+    }
+  }
+  // triangular factors L_A, L_M: the ten lower tiles straight from the record
+  __device__ __forceinline__ void load_l(v2d (&r)[NPL], const double* src) const {
+    const v2d* s2 = reinterpret_cast<const v2d*>(src);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) r[k] = s2[tid + k * WG];
+  }
+  // ... to their places in an LD-strided LDS matrix (the vector kernels; its upper tiles are zeroed once and never written)
+  __device__ __forceinline__ void store_l(double* dst, const v2d (&r)[NPL]) const {
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) { const int e = ltile_elem<N>(tid + k * WG); dst[e] = r[k].x; dst[e + 1] = r[k].y; }
+  }
+  // ... or tile-major as they are in the record (the panel kernels: MultiLds::LT)
+  __device__ __forceinline__ void store_l_packed(double* dst, const v2d (&r)[NPL]) const {
+    v2d* d2 = reinterpret_cast<v2d*>(dst);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) d2[tid + k * WG] = r[k];
+  }
+  // vector part, thread tid < N: 1 / d_A and 1 / d_M (two registers at r), the NU action rows A_xu, F_u, V_u (3 NU registers at r)
+  // -- slices of the kernel's one array pvec, which also holds what only that kernel reads
+  __device__ __forceinline__ void load_diag(double* r, const double* fv) const {
+    r[0] = fv[D::V_DA + tid]; r[1] = fv[D::V_DM + tid];
+  }
+  __device__ __forceinline__ void store_diag(double* dAi, double* dMi, const double* r) const {
+    dAi[tid] = r[0]; dMi[tid] = r[1];
+  }
+  __device__ __forceinline__ void load_act(double* r, const double* fv) const {
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      r[3 * j] = fv[D::V_AU + j * N + tid]; r[3 * j + 1] = fv[D::V_FU + j * N + tid]; r[3 * j + 2] = fv[D::V_VU + j * N + tid];
+    }
+  }
+  __device__ __forceinline__ void store_act(double* au, double* fu, double* vu, const double* r) const {
+#pragma unroll
+    for (int j = 0; j < NU; ++j) { au[j * N + tid] = r[3 * j]; fu[j * N + tid] = r[3 * j + 1]; vu[j * N + tid] = r[3 * j + 2]; }
+  }
+  // (the D::NSC scalars of the action block -- 1 / pivots, reduced right-hand sides, L_u; one lane each -- are read by an
+  //  expression in each kernel's `issue`: returned from a function here, the same select compiled to another schedule in all four)
+};
+
+// ---------------------------------------------------------------------------------------------------
+// backward sweep, a kernel of its own since round 4: the factor record of stage t-1 travels from HBM into REGISTERS while
+// stage t is worked on from LDS (three full matrices and two packed triangular factors, 16 bytes per piece; as the tail of
+// k_wide_step there were no registers for that -- 256 + 240 in use -- and no LDS for a second stage).
 // grid = B, block = 256.
 // ---------------------------------------------------------------------------------------------------
 template <class M>
@@ -1765,8 +1544,9 @@ template <class M, bool BAR>
 __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
   constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
   using D = Dims<N, NU>;
-  constexpr int LD = D::LD, MAT = D::MAT;
-  constexpr int NP = (MAT / 2 + WG - 1) / WG;   // 16-byte pieces of one matrix per thread
+  using RS = RecordStage<N, NU>;
+  using v2d = typename RS::v2d;
+  constexpr int LD = D::LD, MAT = D::MAT, NP = RS::NP, NPL = RS::NPL;
   extern __shared__ double sm[];
   double* MA = sm;
   double* MF = MA + MAT;
@@ -1802,79 +1582,40 @@ __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
   if (tid < N) yv[tid] = a.dz[b * a.lddz + a.zoff[a.T - 1] + tid];
   if (tid < DTO_WIDE_NSTAT) stat[tid] = a.stats ? a.stats[b * DTO_WIDE_NSTAT + tid] : 0.0;
 
-  typedef double v2d __attribute__((ext_vector_type(2)));   // (HIP's double2 is a class: arrays of it stay in scratch)
-  constexpr int NPL = DTO_WIDE_PACK_L ? D::LTILES * TB * TB / 2 / WG : NP;   // pieces of a triangular factor
+  const RS rs{tid};
   v2d pe[NP], pm[NPL], pf[NP], pv[NP], pa[NPL];
-  double pvec[5 + 3 * NU], psc = 0.0;
-  auto load_mat = [&](v2d (&r)[NP], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) r[k] = s2[i];
-    }
-  };
-  auto store_mat = [&](double* dst, const v2d (&r)[NP]) {
-    v2d* d2 = reinterpret_cast<v2d*>(dst);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) d2[i] = r[k];
-    }
-  };
-  // triangular factors: the ten lower tiles straight from the record, written to their places in LDS (the upper tiles of MA
-  // are zeroed once below and never written)
-  auto load_l = [&](v2d (&r)[NPL], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-      const int i = tid + k * WG;
-      if (DTO_WIDE_PACK_L || i < MAT / 2) r[k] = s2[i];
-    }
-  };
-  auto store_l = [&](double* dst, const v2d (&r)[NPL]) {
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-      const int i = tid + k * WG;
-      if (DTO_WIDE_PACK_L) { const int e = ltile_elem<N>(i); dst[e] = r[k].x; dst[e + 1] = r[k].y; }
-      else if (i < MAT / 2) reinterpret_cast<v2d*>(dst)[i] = r[k];
-    }
-  };
-  if (DTO_WIDE_PACK_L) {
-    for (int i = tid; i < MAT; i += WG) MA[i] = 0.0;
-  }
+  double pvec[5 + 3 * NU], psc = 0.0;   // 1 / d_A, 1 / d_M, bx~, bd^, cost gradient, action rows
+  // (the upper tiles of MA are zeroed once and never written: the triangular factors arrive as their lower tiles)
+  for (int i = tid; i < MAT; i += WG) MA[i] = 0.0;
   auto issue = [&](int t) {
     const double* fac = facb + (int64_t)t * D::FAC;
     const double* fv = fac + D::F_VEC;
-    load_mat(pe, fac + D::F_ET);
-    load_l(pm, fac + D::F_LM);
-    load_mat(pf, fac + D::F_FT);
-    load_mat(pv, fac + D::F_VT);
+    rs.load_mat(pe, fac + D::F_ET);
+    rs.load_l(pm, fac + D::F_LM);
+    rs.load_mat(pf, fac + D::F_FT);
+    rs.load_mat(pv, fac + D::F_VT);
     if (tid < N) {
-      pvec[0] = fv[D::V_DA + tid]; pvec[1] = fv[D::V_DM + tid]; pvec[2] = fv[D::V_BX + tid]; pvec[3] = fv[D::V_BD + tid];
-      pvec[4] = fv[D::V_GC + tid];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) {
-        pvec[5 + 3 * j] = fv[D::V_AU + j * N + tid]; pvec[6 + 3 * j] = fv[D::V_FU + j * N + tid]; pvec[7 + 3 * j] = fv[D::V_VU + j * N + tid];
-      }
+      rs.load_diag(pvec, fv);
+      pvec[2] = fv[D::V_BX + tid]; pvec[3] = fv[D::V_BD + tid]; pvec[4] = fv[D::V_GC + tid];
+      rs.load_act(pvec + 5, fv);
     } else if (tid < N + 32) {
-      // [0, 8): cost gradient of the actions; [8, 8 + NU (NU + 2)): 1 / pivots, reduced right-hand sides, L_u
+      // [0, 8): cost gradient of the actions; [8, 8 + NU (NU + 2)): the scalars of the action block
       const int q = tid - N;
-      psc = (q < 8) ? fv[D::V_GC + N + q] : (q - 8 < ((NU * (NU + 2) + 7) & ~7) ? fv[D::V_SC + q - 8] : 0.0);
+      psc = (q < 8) ? fv[D::V_GC + N + q] : (q - 8 < D::NSC ? fv[D::V_SC + q - 8] : 0.0);
     }
   };
   issue(a.T - 2);
-  load_l(pa, facb + (int64_t)(a.T - 2) * D::FAC + D::F_LA);
+  rs.load_l(pa, facb + (int64_t)(a.T - 2) * D::FAC + D::F_LA);
   for (int t = a.T - 2; t >= 0; --t) {
     __syncthreads();
-    store_mat(ME, pe);
-    store_l(MA, pm);
-    store_mat(MF, pf);
-    store_mat(MV, pv);
+    rs.store_mat(ME, pe);
+    rs.store_l(MA, pm);
+    rs.store_mat(MF, pf);
+    rs.store_mat(MV, pv);
     if (tid < N) {
-      dAi[tid] = pvec[0]; dMi[tid] = pvec[1]; bx[tid] = pvec[2]; bd[tid] = pvec[3]; gcv[tid] = pvec[4];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) { au[j * N + tid] = pvec[5 + 3 * j]; fu[j * N + tid] = pvec[6 + 3 * j]; vu[j * N + tid] = pvec[7 + 3 * j]; }
+      rs.store_diag(dAi, dMi, pvec);
+      bx[tid] = pvec[2]; bd[tid] = pvec[3]; gcv[tid] = pvec[4];
+      rs.store_act(au, fu, vu, pvec + 5);
     } else if (tid < N + 32) {
       const int q = tid - N;
       if (q < 8) gcv[N + q] = psc; else scv[q - 8] = psc;
@@ -1896,8 +1637,8 @@ __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
       const double part = quad_sum(dotq_c<N>(MF, LD, lamv) + dotq_r<N>(MV, LD, yv));
       if ((tid & 3) == 0) xv[tid >> 2] = (bx[tid >> 2] - part) * dAi[tid >> 2];
     }
-    store_l(MA, pa);   // L_M is done with (the trsv above ended at the last barrier)
-    if (t > 0) load_l(pa, facb + (int64_t)(t - 1) * D::FAC + D::F_LA);
+    rs.store_l(MA, pa);   // L_M is done with (the trsv above ended at the last barrier)
+    if (t > 0) rs.load_l(pa, facb + (int64_t)(t - 1) * D::FAC + D::F_LA);
     __syncthreads();
     if (w == 0) trsv_lower_t<N>(MA, xv);
     __syncthreads();
@@ -1968,23 +1709,17 @@ __global__ __launch_bounds__(WG) void k_wide_bwd(dto_wide_args a) {
 // and the terminal block x_T = L_A^-T D_A^-1 L_A^-1 (rx_T + by) from record T-1.  bu^, bx~ and bd^ go to the right-hand-side
 // slots of the records, x_T to dz: k_wide_bwd<M, false> then runs unchanged.  The matrices of the records are only read.
 // No O(n^3) work: per stage five matrix loads, two triangular solves by one wavefront and three workgroup-wide products.
-// PRE: the record of stage t+1 travels into registers while stage t is worked on (as in k_wide_bwd); 0: loaded at the top of
-// its own stage (kept for A/B runs, -DDTO_WIDE_FSUB_PREFETCH=0).  grid = B, block = 256, LDS as k_wide_bwd.
+// The record of stage t+1 travels into registers while stage t is worked on, as in k_wide_bwd.  grid = B, block = 256, LDS as
+// k_wide_bwd.
 // ---------------------------------------------------------------------------------------------------
-#ifndef DTO_WIDE_FSUB_PREFETCH
-#define DTO_WIDE_FSUB_PREFETCH 1
-#endif
-template <class M, bool PRE>
+template <class M>
 __global__ __launch_bounds__(WG) void k_wide_fsub(dto_wide_args a) {
   constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
   static_assert(N == 64, "wide path is built for 64 states");
-  static_assert(DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD, "reads packed triangular factors");
   using D = Dims<N, NU>;
-  constexpr int LD = D::LD, MAT = D::MAT;
-  constexpr int NP = (MAT / 2 + WG - 1) / WG;            // 16-byte pieces of one matrix per thread
-  constexpr int NPL = D::LTILES * TB * TB / 2 / WG;      // pieces of a triangular factor
-  constexpr int NSC = (NU * (NU + 2) + 7) & ~7;          // scalars of the action block in the record
-  static_assert(NSC <= 32 && NU <= 32, "scalars of the action block: one lane each");
+  using RS = RecordStage<N, NU>;
+  using v2d = typename RS::v2d;
+  constexpr int LD = D::LD, MAT = D::MAT, NP = RS::NP, NPL = RS::NPL;
   extern __shared__ double sm[];
   double* MA = sm;
   double* MF = MA + MAT;
@@ -2009,51 +1744,23 @@ __global__ __launch_bounds__(WG) void k_wide_fsub(dto_wide_args a) {
   const double* rx = a.rhs_x + b * a.ldrx;
   const double* rc = a.rhs_c + b * a.ldrc;
 
-  typedef double v2d __attribute__((ext_vector_type(2)));
+  const RS rs{tid};
   v2d pa[NPL], pf[NP], pv[NP], pe[NP], pm[NPL];
-  double pvec[4 + 3 * NU], psc = 0.0;
-  auto load_mat = [&](v2d (&r)[NP], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) r[k] = s2[i];
-    }
-  };
-  auto store_mat = [&](double* dst, const v2d (&r)[NP]) {
-    v2d* d2 = reinterpret_cast<v2d*>(dst);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) d2[i] = r[k];
-    }
-  };
-  auto load_l = [&](v2d (&r)[NPL], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) r[k] = s2[tid + k * WG];
-  };
-  auto store_l = [&](double* dst, const v2d (&r)[NPL]) {
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) { const int e = ltile_elem<N>(tid + k * WG); dst[e] = r[k].x; dst[e + 1] = r[k].y; }
-  };
+  double pvec[4 + 3 * NU], psc = 0.0;   // 1 / d_A, 1 / d_M, the caller's right-hand side of x_t and of the constraint rows, action rows
   auto issue = [&](int t) {
     const double* fac = facb + (int64_t)t * D::FAC;
     const double* fv = fac + D::F_VEC;
-    load_l(pa, fac + D::F_LA);
-    load_mat(pf, fac + D::F_FT);
-    load_mat(pv, fac + D::F_VT);
-    load_mat(pe, fac + D::F_ET);
+    rs.load_l(pa, fac + D::F_LA);
+    rs.load_mat(pf, fac + D::F_FT);
+    rs.load_mat(pv, fac + D::F_VT);
+    rs.load_mat(pe, fac + D::F_ET);
     if (tid < N) {
-      pvec[0] = fv[D::V_DA + tid]; pvec[1] = fv[D::V_DM + tid];
+      rs.load_diag(pvec, fv);
       pvec[2] = rx[a.zoff[t] + tid]; pvec[3] = rc[a.cdoff[t] + tid];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) {
-        pvec[4 + 3 * j] = fv[D::V_AU + j * N + tid]; pvec[5 + 3 * j] = fv[D::V_FU + j * N + tid]; pvec[6 + 3 * j] = fv[D::V_VU + j * N + tid];
-      }
+      rs.load_act(pvec + 4, fv);
     } else if (tid < N + 32) {
       const int q = tid - N;
-      psc = q < NSC ? fv[D::V_SC + q] : 0.0;
+      psc = q < D::NSC ? fv[D::V_SC + q] : 0.0;
     } else if (tid < N + 32 + NU) {
       psc = rx[a.zoff[t] + N + (tid - N - 32)];
     }
@@ -2061,26 +1768,25 @@ __global__ __launch_bounds__(WG) void k_wide_fsub(dto_wide_args a) {
   // the upper tiles of MA are zeroed once and never written (the triangular factors arrive as their lower tiles)
   for (int i = tid; i < MAT; i += WG) MA[i] = 0.0;
   if (tid < N) byc[tid] = 0.0;
-  if (PRE && a.T > 1) { issue(0); load_l(pm, facb + D::F_LM); }
+  if (a.T > 1) { issue(0); rs.load_l(pm, facb + D::F_LM); }
   for (int t = 0; t < a.T - 1; ++t) {
     double* fac = facb + (int64_t)t * D::FAC;
-    if (!PRE) { issue(t); load_l(pm, fac + D::F_LM); }
     __syncthreads();
-    store_l(MA, pa);
-    store_mat(MF, pf);
-    store_mat(MV, pv);
-    store_mat(ME, pe);
+    rs.store_l(MA, pa);
+    rs.store_mat(MF, pf);
+    rs.store_mat(MV, pv);
+    rs.store_mat(ME, pe);
     if (tid < N) {
-      dAi[tid] = pvec[0]; dMi[tid] = pvec[1]; bx[tid] = pvec[2] + byc[tid]; bd[tid] = pvec[3];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) { au[j * N + tid] = pvec[4 + 3 * j]; fu[j * N + tid] = pvec[5 + 3 * j]; vu[j * N + tid] = pvec[6 + 3 * j]; }
+      rs.store_diag(dAi, dMi, pvec);
+      bx[tid] = pvec[2] + byc[tid]; bd[tid] = pvec[3];
+      rs.store_act(au, fu, vu, pvec + 4);
     } else if (tid < N + 32) {
       scv[tid - N] = psc;
     } else if (tid < N + 32 + NU) {
       ruv[tid - N - 32] = psc;
     }
     __syncthreads();
-    if (PRE && t + 1 < a.T - 1) issue(t + 1);
+    if (t + 1 < a.T - 1) issue(t + 1);
     // ---- eliminate u: bu^ = L_u^-1 ru (every lane of wavefront 0 for itself, NU <= 4), its terms in bx, bd and by; bx~ = L_A^-1 bx
     if (w == 0) {
       double bu[NU];
@@ -2111,8 +1817,8 @@ __global__ __launch_bounds__(WG) void k_wide_fsub(dto_wide_args a) {
       const double part = quad_sum(dotq_rs<N>(MF, LD, bx, dAi));
       if ((tid & 3) == 0) bd[tid >> 2] -= part;
     }
-    store_l(MA, pm);   // L_A is done with (the trsv above ended at the last barrier)
-    if (PRE && t + 1 < a.T - 1) load_l(pm, facb + (int64_t)(t + 1) * D::FAC + D::F_LM);
+    rs.store_l(MA, pm);   // L_A is done with (the trsv above ended at the last barrier)
+    if (t + 1 < a.T - 1) rs.load_l(pm, facb + (int64_t)(t + 1) * D::FAC + D::F_LM);
     __syncthreads();
     // ---- bd^ = L_M^-1 bd~
     if (w == 0) {
@@ -2131,8 +1837,8 @@ __global__ __launch_bounds__(WG) void k_wide_fsub(dto_wide_args a) {
     const int t = a.T - 1;
     const double* facT = facb + (int64_t)t * D::FAC;
     __syncthreads();
-    load_l(pa, facT + D::F_LA);
-    store_l(MA, pa);
+    rs.load_l(pa, facT + D::F_LA);
+    rs.store_l(MA, pa);
     if (tid < N) {
       dAi[tid] = facT[D::F_VEC + D::V_DA + tid];
       bx[tid] = rx[a.zoff[t] + tid] + byc[tid];
@@ -2268,15 +1974,14 @@ __global__ __launch_bounds__(WG) void k_wide_fsub_multi(dto_wide_args a) {
   constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
   static_assert(N == 64, "wide path is built for 64 states");
   static_assert(NU >= 1 && NU <= 4, "wide path: one to four actions per stage");
-  static_assert(DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD && DTO_WIDE_LDL_RANK1, "reads packed triangular factors with clean diagonal tiles");
   using D = Dims<N, NU>;
   using ML = MultiLds<M, R>;
   constexpr int LD = D::LD, MAT = D::MAT, PLD = ML::PLD, PAN = ML::PAN;
-  constexpr int NP = (MAT / 2 + WG - 1) / WG;            // 16-byte pieces of one matrix per thread
-  constexpr int NPL = ML::LT / 2 / WG;                   // pieces of a triangular factor
-  constexpr int NSC = (NU * (NU + 2) + 7) & ~7;          // scalars of the action block in the record
+  using RS = RecordStage<N, NU>;
+  using v2d = typename RS::v2d;
+  constexpr int NP = RS::NP, NPL = RS::NPL;
   constexpr int CPT = R / 4;                             // panel entries per thread
-  static_assert(NSC <= 32 && NU * R <= N && NPL * WG * 2 == ML::LT, "thread maps of the small pieces");
+  static_assert(NU * R <= N, "right-hand sides of the actions: one thread each");
   extern __shared__ double sm[];
   double* LT = sm;             // L_A, then L_M: packed lower tiles
   double* MF = LT + ML::LT;
@@ -2303,42 +2008,19 @@ __global__ __launch_bounds__(WG) void k_wide_fsub_multi(dto_wide_args a) {
   const int grow = tid & 63, gc = tid >> 6;              // caller's arrays <-> panels: lanes along a row of the caller (coalesced), columns gc + 4 k
   const int pc = tid & 15, pr = tid >> 4;                // panels <-> workspace: entry (pr + 16 k, pc) = linear index tid + 256 k
 
-  typedef double v2d __attribute__((ext_vector_type(2)));
+  const RS rs{tid};
   v2d pa[NPL], pf[NP], pv[NP], pe[NP], pm[NPL];
   double pvec[2 + 3 * NU], psc = 0.0, prx[CPT], prc[CPT], pru = 0.0;
-  auto load_mat = [&](v2d (&rg)[NP], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) rg[k] = s2[i];
-    }
-  };
-  auto store_mat = [&](double* dst, const v2d (&rg)[NP]) {
-    v2d* d2 = reinterpret_cast<v2d*>(dst);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) d2[i] = rg[k];
-    }
-  };
-  auto load_l = [&](v2d (&rg)[NPL], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) rg[k] = s2[tid + k * WG];
-  };
-  auto store_l = [&](const v2d (&rg)[NPL]) {
-    v2d* d2 = reinterpret_cast<v2d*>(LT);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) d2[tid + k * WG] = rg[k];
-  };
+  // (LT reaches the store through this capture, not as an argument at the three call sites: only so does this kernel keep the
+  //  instruction stream it had with a store lambda of its own)
+  auto store_l = [&](const v2d (&rg)[NPL]) { rs.store_l_packed(LT, rg); };
   auto issue = [&](int t) {
     const double* fac = facb + (int64_t)t * D::FAC;
     const double* fv = fac + D::F_VEC;
-    load_l(pa, fac + D::F_LA);
-    load_mat(pf, fac + D::F_FT);
-    load_mat(pv, fac + D::F_VT);
-    load_mat(pe, fac + D::F_ET);
+    rs.load_l(pa, fac + D::F_LA);
+    rs.load_mat(pf, fac + D::F_FT);
+    rs.load_mat(pv, fac + D::F_VT);
+    rs.load_mat(pe, fac + D::F_ET);
     const int zo = a.zoff[t], co = a.cdoff[t];
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
@@ -2348,29 +2030,25 @@ __global__ __launch_bounds__(WG) void k_wide_fsub_multi(dto_wide_args a) {
     }
     if (tid < NU * R) { const int c = tid % R; pru = c < ncol ? a.rhs_x[(row0 + c) * a.ldrx + zo + N + tid / R] : 0.0; }
     if (tid < N) {
-      pvec[0] = fv[D::V_DA + tid]; pvec[1] = fv[D::V_DM + tid];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) {
-        pvec[2 + 3 * j] = fv[D::V_AU + j * N + tid]; pvec[3 + 3 * j] = fv[D::V_FU + j * N + tid]; pvec[4 + 3 * j] = fv[D::V_VU + j * N + tid];
-      }
+      rs.load_diag(pvec, fv);
+      rs.load_act(pvec + 2, fv);
     } else if (tid < N + 32) {
-      const int s = tid - N;
-      psc = s < NSC ? fv[D::V_SC + s] : 0.0;
+      const int q = tid - N;
+      psc = q < D::NSC ? fv[D::V_SC + q] : 0.0;
     }
   };
   for (int i = tid; i < PAN; i += WG) BY[i] = 0.0;
-  if (a.T > 1) { issue(0); load_l(pm, facb + D::F_LM); }
+  if (a.T > 1) { issue(0); rs.load_l(pm, facb + D::F_LM); }
   for (int t = 0; t < a.T - 1; ++t) {
     double* wst = wsb + (int64_t)t * ML::WS;
     __syncthreads();
     store_l(pa);
-    store_mat(MF, pf);
-    store_mat(MV, pv);
-    store_mat(ME, pe);
+    rs.store_mat(MF, pf);
+    rs.store_mat(MV, pv);
+    rs.store_mat(ME, pe);
     if (tid < N) {
-      dAi[tid] = pvec[0]; dMi[tid] = pvec[1];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) { au[j * N + tid] = pvec[2 + 3 * j]; fu[j * N + tid] = pvec[3 + 3 * j]; vu[j * N + tid] = pvec[4 + 3 * j]; }
+      rs.store_diag(dAi, dMi, pvec);
+      rs.store_act(au, fu, vu, pvec + 2);
     } else if (tid < N + 32) {
       scv[tid - N] = psc;
     }
@@ -2423,7 +2101,7 @@ __global__ __launch_bounds__(WG) void k_wide_fsub_multi(dto_wide_args a) {
       tile_store(BD, PLD, w * TB, 0, c);
     }
     store_l(pm);   // L_A is done with (the substitution above ended at the last barrier)
-    if (t + 1 < a.T - 1) load_l(pm, facb + (int64_t)(t + 1) * D::FAC + D::F_LM);
+    if (t + 1 < a.T - 1) rs.load_l(pm, facb + (int64_t)(t + 1) * D::FAC + D::F_LM);
     __syncthreads();
     // ---- bd^ = L_M^-1 bd~
     if (w == 0) panel_trsm_lower<N, PLD>(LT, BD);
@@ -2453,7 +2131,7 @@ __global__ __launch_bounds__(WG) void k_wide_fsub_multi(dto_wide_args a) {
     const double* facT = facb + (int64_t)t * D::FAC;
     const int zo = a.zoff[t];
     __syncthreads();
-    load_l(pa, facT + D::F_LA);
+    rs.load_l(pa, facT + D::F_LA);
     store_l(pa);
     if (tid < N) dAi[tid] = facT[D::F_VEC + D::V_DA + tid];
 #pragma unroll
@@ -2485,15 +2163,14 @@ __global__ __launch_bounds__(WG) void k_wide_bwd_multi(dto_wide_args a) {
   constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
   static_assert(N == 64, "wide path is built for 64 states");
   static_assert(NU >= 1 && NU <= 4, "wide path: one to four actions per stage");
-  static_assert(DTO_WIDE_PACK_L && DTO_WIDE_SPLIT_BWD && DTO_WIDE_LDL_RANK1, "reads packed triangular factors with clean diagonal tiles");
   using D = Dims<N, NU>;
   using ML = MultiLds<M, R>;
   constexpr int LD = D::LD, MAT = D::MAT, PLD = ML::PLD, PAN = ML::PAN;
-  constexpr int NP = (MAT / 2 + WG - 1) / WG;
-  constexpr int NPL = ML::LT / 2 / WG;
-  constexpr int NSC = (NU * (NU + 2) + 7) & ~7;
+  using RS = RecordStage<N, NU>;
+  using v2d = typename RS::v2d;
+  constexpr int NP = RS::NP, NPL = RS::NPL;
   constexpr int CPT = R / 4;
-  static_assert(NSC <= 32 && NU * R <= N && NPL * WG * 2 == ML::LT, "thread maps of the small pieces");
+  static_assert(NU * R <= N, "bu^ of the block: one thread each");
   extern __shared__ double sm[];
   double* LT = sm;             // L_M, then L_A: packed lower tiles
   double* MF = LT + ML::LT;
@@ -2520,43 +2197,18 @@ __global__ __launch_bounds__(WG) void k_wide_bwd_multi(dto_wide_args a) {
   const int grow = tid & 63, gc = tid >> 6;
   const int pc = tid & 15, pr = tid >> 4;
 
-  typedef double v2d __attribute__((ext_vector_type(2)));
+  const RS rs{tid};
   v2d pe[NP], pm[NPL], pf[NP], pv[NP], pa[NPL];
   double pvec[2 + 3 * NU], psc = 0.0, pbx[4], pbd[4], pbu = 0.0;
-  auto load_mat = [&](v2d (&rg)[NP], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) rg[k] = s2[i];
-    }
-  };
-  auto store_mat = [&](double* dst, const v2d (&rg)[NP]) {
-    v2d* d2 = reinterpret_cast<v2d*>(dst);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      const int i = tid + k * WG;
-      if (i < MAT / 2) d2[i] = rg[k];
-    }
-  };
-  auto load_l = [&](v2d (&rg)[NPL], const double* src) {
-    const v2d* s2 = reinterpret_cast<const v2d*>(src);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) rg[k] = s2[tid + k * WG];
-  };
-  auto store_l = [&](const v2d (&rg)[NPL]) {
-    v2d* d2 = reinterpret_cast<v2d*>(LT);
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) d2[tid + k * WG] = rg[k];
-  };
+  auto store_l = [&](const v2d (&rg)[NPL]) { rs.store_l_packed(LT, rg); };   // (as in k_wide_fsub_multi)
   auto issue = [&](int t) {
     const double* fac = facb + (int64_t)t * D::FAC;
     const double* fv = fac + D::F_VEC;
     const double* wst = wsb + (int64_t)t * ML::WS;
-    load_mat(pe, fac + D::F_ET);
-    load_l(pm, fac + D::F_LM);
-    load_mat(pf, fac + D::F_FT);
-    load_mat(pv, fac + D::F_VT);
+    rs.load_mat(pe, fac + D::F_ET);
+    rs.load_l(pm, fac + D::F_LM);
+    rs.load_mat(pf, fac + D::F_FT);
+    rs.load_mat(pv, fac + D::F_VT);
     // bx~ and bd^ of the block as this lane's accumulator entries of tile-row w
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
@@ -2565,14 +2217,11 @@ __global__ __launch_bounds__(WG) void k_wide_bwd_multi(dto_wide_args a) {
     }
     if (tid < NU * R) pbu = wst[2 * N * R + tid];
     if (tid < N) {
-      pvec[0] = fv[D::V_DA + tid]; pvec[1] = fv[D::V_DM + tid];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) {
-        pvec[2 + 3 * j] = fv[D::V_AU + j * N + tid]; pvec[3 + 3 * j] = fv[D::V_FU + j * N + tid]; pvec[4 + 3 * j] = fv[D::V_VU + j * N + tid];
-      }
+      rs.load_diag(pvec, fv);
+      rs.load_act(pvec + 2, fv);
     } else if (tid < N + 32) {
-      const int s = tid - N;
-      psc = s < NSC ? fv[D::V_SC + s] : 0.0;
+      const int q = tid - N;
+      psc = q < D::NSC ? fv[D::V_SC + q] : 0.0;
     }
   };
   {
@@ -2583,17 +2232,16 @@ __global__ __launch_bounds__(WG) void k_wide_bwd_multi(dto_wide_args a) {
       YP[grow * PLD + c] = c < ncol ? a.dz[(row0 + c) * a.lddz + zo + grow] : 0.0;
     }
   }
-  if (a.T > 1) { issue(a.T - 2); load_l(pa, facb + (int64_t)(a.T - 2) * D::FAC + D::F_LA); }
+  if (a.T > 1) { issue(a.T - 2); rs.load_l(pa, facb + (int64_t)(a.T - 2) * D::FAC + D::F_LA); }
   for (int t = a.T - 2; t >= 0; --t) {
     __syncthreads();
-    store_mat(ME, pe);
+    rs.store_mat(ME, pe);
     store_l(pm);
-    store_mat(MF, pf);
-    store_mat(MV, pv);
+    rs.store_mat(MF, pf);
+    rs.store_mat(MV, pv);
     if (tid < N) {
-      dAi[tid] = pvec[0]; dMi[tid] = pvec[1];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) { au[j * N + tid] = pvec[2 + 3 * j]; fu[j * N + tid] = pvec[3 + 3 * j]; vu[j * N + tid] = pvec[4 + 3 * j]; }
+      rs.store_diag(dAi, dMi, pvec);
+      rs.store_act(au, fu, vu, pvec + 2);
     } else if (tid < N + 32) {
       scv[tid - N] = psc;
     }
@@ -2625,7 +2273,7 @@ __global__ __launch_bounds__(WG) void k_wide_bwd_multi(dto_wide_args a) {
       tile_store(XP, PLD, w * TB, 0, cx);
     }
     store_l(pa);   // L_M is done with (the substitution above ended at the last barrier)
-    if (t > 0) load_l(pa, facb + (int64_t)(t - 1) * D::FAC + D::F_LA);
+    if (t > 0) rs.load_l(pa, facb + (int64_t)(t - 1) * D::FAC + D::F_LA);
     __syncthreads();
     if (w == 0) panel_trsm_upper<N, PLD>(LT, XP);
     __syncthreads();
@@ -3082,13 +2730,8 @@ int wide_info(dto_wide_info* out) {
   out->nu = M::WIDE_NU;
   out->fac_stage = D::FAC;
   out->lds_bytes = StepLds<M>::BYTES;
-#if DTO_WIDE_SPLIT_BWD && DTO_WIDE_PACK_L && DTO_WIDE_LDL_RANK1
   out->multi_r = DTO_WIDE_MULTI_R;
   out->multi_ws_stage = MultiLds<M, DTO_WIDE_MULTI_R>::WS;
-#else
-  out->multi_r = 0;
-  out->multi_ws_stage = 0;
-#endif
   return 0;
 }
 
@@ -3098,81 +2741,57 @@ int launch_wide_multi(const dto_wide_args* a, void* stream);
 template <class M>
 int launch_wide_kmul(const dto_wide_args* a, void* stream);
 
+// one launch of a kernel of this file, `grid` workgroups of WG threads: its dynamic-LDS limit is raised first.  Returns the
+// error of that call; a launch error is left to the hipGetLastError() that ends every launch_wide*
+template <class K>
+hipError_t launch_kernel(K kernel, dim3 grid, int lds, void* stream, const dto_wide_args* a) {
+  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, grid, dim3(WG), lds, (hipStream_t)stream, *a);
+  return hipSuccess;
+}
+
 template <class M>
 int launch_wide(int op, const dto_wide_args* a, void* stream) {
+  const dim3 grid((unsigned)a->B);
+  constexpr int step_lds = StepLds<M>::BYTES, bwd_lds = BwdLds<M>::BYTES;
+  hipError_t e;
   if (op == DTO_WIDE_MERIT) {
     constexpr int N = M::WIDE_N, NU = M::WIDE_NU;
     const int lds = (int)sizeof(double) * (N * (2 * N + NU) + 4 * (3 * (N + NU + 1) + 3 * N + 16) + 4 * 2 * DTO_WIDE_TRIALS);
-    hipError_t em = hipFuncSetAttribute((const void*)k_wide_merit<M>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (em != hipSuccess) return (int)em;
-    hipLaunchKernelGGL(k_wide_merit<M>, dim3((unsigned)a->B), dim3(WG), lds, (hipStream_t)stream, *a);
-    return (int)hipGetLastError();
-  }
-  dto_wide_info info;
-  wide_info<M>(&info);
-#if DTO_WIDE_SPLIT_BWD && DTO_WIDE_PACK_L
-  if (op == DTO_WIDE_FACTOR) {
+    e = launch_kernel(k_wide_merit<M>, grid, lds, stream, a);
+  } else if (op == DTO_WIDE_FACTOR) {
     // the linear solver alone: one sweep, factors (terminal block included) to the records, nothing solved
-    hipError_t ef = hipFuncSetAttribute((const void*)k_wide_step<M, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, info.lds_bytes);
-    if (ef != hipSuccess) return (int)ef;
-    hipLaunchKernelGGL((k_wide_step<M, false, true>), dim3((unsigned)a->B), dim3(WG), info.lds_bytes, (hipStream_t)stream, *a);
-    return (int)hipGetLastError();
-  }
-  if (op == DTO_WIDE_SOLVE) {
+    e = launch_kernel(k_wide_step<M, false, true>, grid, step_lds, stream, a);
+  } else if (op == DTO_WIDE_SOLVE) {
     // substitution only: forward over the stored records with the caller's right-hand side, then the backward sweep of the step
-    constexpr bool PRE = DTO_WIDE_FSUB_PREFETCH != 0;
-    hipError_t es = hipFuncSetAttribute((const void*)k_wide_fsub<M, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<M>::BYTES);
-    if (es != hipSuccess) return (int)es;
-    hipLaunchKernelGGL((k_wide_fsub<M, PRE>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
-    es = hipFuncSetAttribute((const void*)k_wide_bwd<M, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<M>::BYTES);
-    if (es != hipSuccess) return (int)es;
-    hipLaunchKernelGGL((k_wide_bwd<M, false>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
-    return (int)hipGetLastError();
+    e = launch_kernel(k_wide_fsub<M>, grid, bwd_lds, stream, a);
+    if (e == hipSuccess) e = launch_kernel(k_wide_bwd<M, false>, grid, bwd_lds, stream, a);
+  } else if (op == DTO_WIDE_SOLVE_MULTI) {
+    return launch_wide_multi<M>(a, stream);
+  } else if (op == DTO_WIDE_KMUL) {
+    return launch_wide_kmul<M>(a, stream);
+  } else if (op != DTO_WIDE_STEP) {
+    return (int)hipErrorInvalidValue;
+  } else if (a->zl) {   // the step: forward sweep, then the backward sweep over its records; with the barrier terms of finite bounds ...
+    e = launch_kernel(k_wide_step<M, true>, grid, step_lds, stream, a);
+    if (e == hipSuccess) e = launch_kernel(k_wide_bwd<M, true>, grid, bwd_lds, stream, a);
+  } else {              // ... or without
+    e = launch_kernel(k_wide_step<M, false>, grid, step_lds, stream, a);
+    if (e == hipSuccess) e = launch_kernel(k_wide_bwd<M, false>, grid, bwd_lds, stream, a);
   }
-#if DTO_WIDE_LDL_RANK1
-  if (op == DTO_WIDE_SOLVE_MULTI) return launch_wide_multi<M>(a, stream);
-#endif
-  if (op == DTO_WIDE_KMUL) return launch_wide_kmul<M>(a, stream);
-#endif
-  if (op != DTO_WIDE_STEP) return (int)hipErrorInvalidValue;
-  if (a->zl) {
-    hipError_t eb = hipFuncSetAttribute((const void*)k_wide_step<M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, info.lds_bytes);
-    if (eb != hipSuccess) return (int)eb;
-    hipLaunchKernelGGL((k_wide_step<M, true>), dim3((unsigned)a->B), dim3(WG), info.lds_bytes, (hipStream_t)stream, *a);
-#if DTO_WIDE_SPLIT_BWD
-    eb = hipFuncSetAttribute((const void*)k_wide_bwd<M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<M>::BYTES);
-    if (eb != hipSuccess) return (int)eb;
-    hipLaunchKernelGGL((k_wide_bwd<M, true>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
-#endif
-    return (int)hipGetLastError();
-  }
-  hipError_t e = hipFuncSetAttribute((const void*)k_wide_step<M, false>, hipFuncAttributeMaxDynamicSharedMemorySize, info.lds_bytes);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((k_wide_step<M, false>), dim3((unsigned)a->B), dim3(WG), info.lds_bytes, (hipStream_t)stream, *a);
-#if DTO_WIDE_SPLIT_BWD
-  e = hipFuncSetAttribute((const void*)k_wide_bwd<M, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BwdLds<M>::BYTES);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((k_wide_bwd<M, false>), dim3((unsigned)a->B), dim3(WG), BwdLds<M>::BYTES, (hipStream_t)stream, *a);
-#endif
-  return (int)hipGetLastError();
+  return e != hipSuccess ? (int)e : (int)hipGetLastError();
 }
 
 // one block of right-hand sides: forward and backward panel substitution over the stored records, which are only read
 template <class M>
 int launch_wide_multi(const dto_wide_args* a, void* stream) {
-#if DTO_WIDE_SPLIT_BWD && DTO_WIDE_PACK_L && DTO_WIDE_LDL_RANK1
   constexpr int R = DTO_WIDE_MULTI_R;
   constexpr int lds = MultiLds<M, R>::BYTES;
-  hipError_t e = hipFuncSetAttribute((const void*)k_wide_fsub_multi<M, R>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((k_wide_fsub_multi<M, R>), dim3((unsigned)a->B), dim3(WG), lds, (hipStream_t)stream, *a);
-  e = hipFuncSetAttribute((const void*)k_wide_bwd_multi<M, R>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((k_wide_bwd_multi<M, R>), dim3((unsigned)a->B), dim3(WG), lds, (hipStream_t)stream, *a);
-  return (int)hipGetLastError();
-#else
-  return (int)hipErrorInvalidValue;
-#endif
+  const dim3 grid((unsigned)a->B);
+  hipError_t e = launch_kernel(k_wide_fsub_multi<M, R>, grid, lds, stream, a);
+  if (e == hipSuccess) e = launch_kernel(k_wide_bwd_multi<M, R>, grid, lds, stream, a);
+  return e != hipSuccess ? (int)e : (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3431,11 +3050,8 @@ int launch_wide_kmul(const dto_wide_args* a, void* stream) {
   const int S = a->kmul_s > 0 ? a->kmul_s : DTO_WIDE_KMUL_S;
   const int chunks = a->T > 1 ? (a->T - 1 + S - 1) / S : 1;
   if (chunks > 65535) return (int)hipErrorInvalidValue;
-  constexpr int lds = KmulLds<M>::BYTES;
-  hipError_t e = hipFuncSetAttribute((const void*)k_wide_kmul<M>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((k_wide_kmul<M>), dim3((unsigned)a->B, (unsigned)chunks), dim3(WG), lds, (hipStream_t)stream, *a);
-  return (int)hipGetLastError();
+  const hipError_t e = launch_kernel(k_wide_kmul<M>, dim3((unsigned)a->B, (unsigned)chunks), KmulLds<M>::BYTES, stream, a);
+  return e != hipSuccess ? (int)e : (int)hipGetLastError();
 }
 
 }  // namespace wide

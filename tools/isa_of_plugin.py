@@ -5,7 +5,9 @@ kernels' code generation alone (what decides k_kkt_fwd_se
     python tools/isa_of_plugin.py acrobot [out.s]      # summary on stdout
     python tools/isa_of_plugin.py acrobot_padded       # a tile-path plugin (csrc/dto_wide_kernels.hpp): its flags, one line per
                                                        # instantiation (k_wide_step<M, BAR, LIN>: ...Lb0ELb0E, Lb1ELb0E, Lb0ELb1E)
+    python tools/isa_of_plugin.py acrobot_padded m=3   # keywords of the model's builder (here: three actions per knot, NU = 3)
 """
+import ast
 import os
 import re
 import sys
@@ -47,17 +49,28 @@ def kernel_stats(isa):
 def main():
     import check_exec_merge as C
     from dto_amd import plugin as PL, problems as P
-    model = sys.argv[1] if len(sys.argv) > 1 else "acrobot"
-    p = getattr(P, f"build_{model}")(T=5, evaluate_hessian=True)
+    # (name=value arguments are keywords of the model's builder; what else follows the model is the output file)
+    args = [a for a in sys.argv[1:] if "=" not in a]
+    kw = dict(T=5, evaluate_hessian=True)
+    for a in sys.argv[1:]:
+        if "=" in a:
+            k, v = a.split("=", 1)
+            try:
+                kw[k] = ast.literal_eval(v)
+            except (ValueError, SyntaxError):
+                kw[k] = v
+    model = args[0] if args else "acrobot"
+    p = getattr(P, f"build_{model}")(**kw)
     st = PL.Structure(p["dynamics"], p["objective"], p["constraints"], None, True)
     src = PL.generate_source(st, model)
-    path = os.path.join(PL.PLUGIN_DIR, f"_isa_{model}.hip")
+    os.makedirs(PL.PLUGIN_DIR, exist_ok=True)
+    path = os.path.join(PL.PLUGIN_DIR, f"_isa_{model}_{os.getpid()}.hip")
     with open(path, "w") as f:
         f.write(src)
     isa = C.compile_to_isa(path, PL.BASE_CXXFLAGS + (PL.WIDE_CXXFLAGS if st.wide else []) + PL._extra_flags())
     os.remove(path)
-    if len(sys.argv) > 2:
-        with open(sys.argv[2], "w") as f:
+    if len(args) > 1:
+        with open(args[1], "w") as f:
             f.write(isa)
     # metadata block: per-kernel register counts
     meta = {}
