@@ -1,0 +1,227 @@
+// Border algebra of dto_kkt_border_factor / dto_kkt_border_solve (include/dto.h): model-independent kernels of the runtime
+// library, not of the model plugin.  For every instance
+//     [ K   G' ] [ v ]   [ r ]      G: nb x N border rows (nb <= 16, N = num_variables + num_constraint),  C: nb x nb
+//     [ G   C  ] [ y ] = [ s ]
+// is solved by the Schur complement on the border: Y = K^-1 G' and v0 = K^-1 r come from the path's own solves
+// (dto_kkt_solve_multi / dto_kkt_solve), the four kernels below do the rest:
+//     k_border_gram   P = G Y'              16 x 16 per instance, inner dimension N, on v_mfma_f64_16x16x4_f64
+//     k_border_schur  S = sym(C) - sym(P)   Cholesky of -S (flag), LU with partial pivoting (kept), zero-pivot flag
+//     k_border_rhs    y = S^-1 (s - Y r)    (G K^-1 r = Y r: K is symmetric)
+//     k_border_sub    v = v0 - Y' y
+// A vector of length N lives in two arrays (the variables' part and the constraint rows' part) with a leading dimension each,
+// so every k range below is two segments.  Nothing is read beyond the row lengths: the callers' padding may hold anything.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace dto {
+
+constexpr int KB_MAX = 16;              // border rows of one panel
+constexpr int KB_KT = 128;              // doubles of k per LDS slab
+// row stride of a slab: a fragment read is slab[r][k + q] with r = lane & 15, q = lane >> 4; ds_read_b64 banks are (dword
+// address) mod 64 and the two 32-lane halves are served separately, so r * LD + q must be distinct mod 32 for r < 16, q < 2 --
+// LD = 2 (mod 32) makes it 2 r + q
+constexpr int KB_LD = KB_KT + 2;
+constexpr int KB_THREADS = 256;         // four wavefronts: each takes a quarter (32 doubles of k) of every slab
+constexpr int KB_RHS_THREADS = 1024;    // k_border_rhs: one workgroup per instance
+constexpr int KB_CHUNK_DEFAULT = 2048;  // doubles of k per workgroup ("bordered solves": how it was chosen)
+constexpr int KB_ROW_BLOCKS = 64;       // workgroups per instance of k_border_sub (as AXPY_BLOCKS_PER_ROW)
+
+typedef double kb_d4 __attribute__((ext_vector_type(4)));
+
+// element k of row `row` of a vector stored as two segments
+__device__ __forceinline__ double kb_seg(const double* x, int64_t ldx, const double* c, int64_t ldc, int64_t row, int64_t k, int64_t nx) {
+  return k < nx ? x[row * ldx + k] : c[row * ldc + (k - nx)];
+}
+
+// P = G Y' per instance and chunk of k: grid.x = B * chunks, workgroup (b, ch) covers k in [ch * chunk, min(N, (ch + 1) * chunk))
+// and writes its partial 16 x 16 (row-major: P[a][q] = sum_k G[a][k] Y[q][k]) to part[(b * chunks + ch) * 256].  No atomics: the
+// partials are summed in chunk order by k_border_schur, so a result depends on the chunk length and on nothing else.
+// Row j of instance b is row b * nb + j of (g_x, g_c) and of (y_x, y_c); n_c = 0 skips the second segment.  Rows nb .. 15 and
+// the tail of the last slab are zeros in LDS.  Every row element is loaded once, a wavefront reading 64 consecutive doubles of
+// one row per instruction; the loads of slab i + 1 are in flight while the matrix cores work on slab i.
+static __global__ __launch_bounds__(KB_THREADS) void k_border_gram(int nb, int64_t n_x, int64_t n_c, int64_t chunk, int chunks,
+                                                                   const double* g_x, int64_t ldgx, const double* g_c, int64_t ldgc,
+                                                                   const double* y_x, int64_t ldyx, const double* y_c, int64_t ldyc,
+                                                                   double* part) {
+  __shared__ double sG[KB_MAX * KB_LD], sY[KB_MAX * KB_LD];
+  const int64_t b = blockIdx.x / chunks;
+  const int ch = (int)(blockIdx.x % chunks);
+  const int64_t N = n_x + n_c;
+  const int64_t k_lo = (int64_t)ch * chunk, k_hi = k_lo + chunk < N ? k_lo + chunk : N;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int col = t & (KB_KT - 1), half = t >> 7;   // this thread stages column `col` of rows half, half + 2, ...
+  const int r = lane & 15, q = lane >> 4;
+  double vg[8], vy[8];
+  auto fetch = [&](int64_t k0) {
+    const int64_t k = k0 + col;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = 2 * i + half;
+      const bool in = row < nb && k < k_hi;
+      vg[i] = in ? kb_seg(g_x, ldgx, g_c, ldgc, b * nb + row, k, n_x) : 0.0;
+      vy[i] = in ? kb_seg(y_x, ldyx, y_c, ldyc, b * nb + row, k, n_x) : 0.0;
+    }
+  };
+  kb_d4 acc = {0.0, 0.0, 0.0, 0.0};
+  if (k_lo < k_hi) fetch(k_lo);
+  for (int64_t k0 = k_lo; k0 < k_hi; k0 += KB_KT) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      sG[(2 * i + half) * KB_LD + col] = vg[i];
+      sY[(2 * i + half) * KB_LD + col] = vy[i];
+    }
+    __syncthreads();   // the slab is complete before any wavefront reads fragments of it
+    if (k0 + KB_KT < k_hi) fetch(k0 + KB_KT);
+    const double* a = sG + r * KB_LD + wave * (KB_KT / 4) + q;
+    const double* y = sY + r * KB_LD + wave * (KB_KT / 4) + q;
+#pragma unroll
+    for (int kk = 0; kk < KB_KT / 4; kk += 4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], y[kk], acc, 0, 0, 0);
+    __syncthreads();   // every fragment has been read before the slab is overwritten
+  }
+  // the four accumulators, added in wavefront order (C/D layout: col = lane & 15, row = (lane >> 4) + 4 j); sG is free after
+  // the barrier that ended the loop
+  double* red = sG;   // [4][256]
+#pragma unroll
+  for (int j = 0; j < 4; ++j) red[wave * 256 + (q + 4 * j) * 16 + r] = acc[j];
+  __syncthreads();
+  part[((int64_t)b * chunks + ch) * 256 + t] = ((red[t] + red[256 + t]) + red[512 + t]) + red[768 + t];
+}
+static_assert(4 * 256 <= KB_MAX * KB_LD, "the reduction of k_border_gram reuses one slab");
+
+// One wavefront per instance: P = sum of the partials in chunk order, S = (C + C')/2 - (P + P')/2, then lane 0: is -S positive
+// definite (Cholesky attempt), LU of S with partial pivoting into lu [B][256] (row-major, stride 16: unit-lower multipliers
+// below the diagonal, U on and above) and piv [B][16] (row exchanged with row k at step k); flags [2][B]: negdef, singular
+// (a pivot that is zero -- or not a number -- was met; the elimination of that column is skipped).
+static __global__ __launch_bounds__(64) void k_border_schur(int64_t B, int nb, int chunks, const double* part, const double* c, int64_t ldc,
+                                                            double* lu, int* piv, int* flags) {
+  __shared__ double P[256], S[256], L[256];
+  const int64_t b = blockIdx.x;
+  const int l = threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    double acc = 0.0;
+    for (int ch = 0; ch < chunks; ++ch) acc += part[(b * chunks + ch) * 256 + l + 64 * e];
+    P[l + 64 * e] = acc;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int i = l + 64 * e, a = i >> 4, q = i & 15;
+    double v = 0.0;
+    if (a < nb && q < nb) {
+      const double cs = c ? 0.5 * (c[b * ldc + a * nb + q] + c[b * ldc + q * nb + a]) : 0.0;
+      v = cs - 0.5 * (P[a * 16 + q] + P[q * 16 + a]);
+    }
+    S[i] = v;
+  }
+  __syncthreads();
+  if (l != 0) return;
+  bool negdef = true, singular = false;
+  for (int a = 0; a < nb && negdef; ++a)
+    for (int q = 0; q <= a; ++q) {
+      double acc = -S[a * 16 + q];
+      for (int k = 0; k < q; ++k) acc -= L[a * 16 + k] * L[q * 16 + k];
+      if (a == q) { if (!(acc > 0.0)) { negdef = false; break; } L[a * 16 + a] = sqrt(acc); }
+      else L[a * 16 + q] = acc / L[q * 16 + q];
+    }
+  for (int k = 0; k < nb; ++k) {
+    int pv = k;
+    for (int i = k + 1; i < nb; ++i) if (fabs(S[i * 16 + k]) > fabs(S[pv * 16 + k])) pv = i;
+    piv[b * 16 + k] = pv;
+    if (pv != k)
+      for (int q = 0; q < nb; ++q) { const double tmp = S[k * 16 + q]; S[k * 16 + q] = S[pv * 16 + q]; S[pv * 16 + q] = tmp; }
+    const double d = S[k * 16 + k];
+    if (!(fabs(d) > 0.0)) { singular = true; continue; }
+    for (int i = k + 1; i < nb; ++i) {
+      const double f = S[i * 16 + k] / d;
+      S[i * 16 + k] = f;
+      for (int q = k + 1; q < nb; ++q) S[i * 16 + q] -= f * S[k * 16 + q];
+    }
+  }
+  for (int i = 0; i < 256; ++i) lu[b * 256 + i] = S[i];
+  flags[b] = negdef ? 1 : 0;
+  flags[B + b] = singular ? 1 : 0;
+}
+
+// One workgroup of sixteen wavefronts per instance (the dot products stream nb x N doubles per instance: at 256 instances one
+// workgroup per compute unit has to keep the memory system busy on its own): t_j = s_j - Y_j . r for the nb rows of Y -- thread t
+// adds elements t, t + 1024, ... of every row in that order, a shuffle tree inside the wavefront, the sixteen wavefront sums in
+// wavefront order: the same order every run -- then thread 0 solves S y = t with the stored LU.  y goes to sol_b and to
+// yw [B][16]; a singular instance gets NaN.
+static __global__ __launch_bounds__(KB_RHS_THREADS) void k_border_rhs(int nb, int64_t n_x, int64_t n_c, const double* y_x, int64_t ldyx,
+                                                                      const double* y_c, int64_t ldyc, const double* r_x, int64_t ldrx,
+                                                                      const double* r_c, int64_t ldrc, const double* s, int64_t lds,
+                                                                      const double* lu, const int* piv, const int* singular, double* sol_b,
+                                                                      int64_t ldsb, double* yw) {
+  __shared__ double red[KB_MAX][KB_RHS_THREADS / 64];
+  const int64_t b = blockIdx.x;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t N = n_x + n_c;
+  double acc[KB_MAX];
+#pragma unroll
+  for (int j = 0; j < KB_MAX; ++j) acc[j] = 0.0;
+  for (int64_t k = t; k < N; k += KB_RHS_THREADS) {
+    const double rk = kb_seg(r_x, ldrx, r_c, ldrc, b, k, n_x);
+#pragma unroll
+    for (int j = 0; j < KB_MAX; ++j)
+      if (j < nb) acc[j] += kb_seg(y_x, ldyx, y_c, ldyc, b * nb + j, k, n_x) * rk;
+  }
+#pragma unroll
+  for (int j = 0; j < KB_MAX; ++j) {
+    double v = acc[j];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) red[j][wave] = v;
+  }
+  __syncthreads();   // the wavefront sums are in LDS before thread 0 reads them
+  if (t != 0) return;
+  double v[KB_MAX];
+  const double* A = lu + b * 256;
+  if (singular[b]) {
+    for (int j = 0; j < nb; ++j) v[j] = __builtin_nan("");
+  } else {
+    for (int j = 0; j < nb; ++j) {
+      double dot = 0.0;
+      for (int w = 0; w < KB_RHS_THREADS / 64; ++w) dot += red[j][w];
+      v[j] = s[b * lds + j] - dot;
+    }
+    // (the exchanges of the factorisation moved whole rows, multipliers included: all of them first, then the unit-lower solve)
+    for (int k = 0; k < nb; ++k) {
+      const int pv = piv[b * 16 + k];
+      if (pv != k) { const double tmp = v[k]; v[k] = v[pv]; v[pv] = tmp; }
+    }
+    for (int k = 0; k < nb; ++k)
+      for (int i = k + 1; i < nb; ++i) v[i] -= A[i * 16 + k] * v[k];
+    for (int k = nb - 1; k >= 0; --k) {
+      double a = v[k];
+      for (int q = k + 1; q < nb; ++q) a -= A[k * 16 + q] * v[q];
+      v[k] = a / A[k * 16 + k];
+    }
+  }
+  for (int j = 0; j < nb; ++j) { sol_b[b * ldsb + j] = v[j]; yw[b * 16 + j] = v[j]; }
+}
+
+// sol = v0 - sum_j y_j Y_j (j ascending) over the N entries of every instance: grid.x = B * KB_ROW_BLOCKS, the outputs with their
+// own leading dimensions, nothing written beyond the row lengths.  A NaN in y reaches every entry.
+static __global__ __launch_bounds__(KB_THREADS) void k_border_sub(int nb, int64_t n_x, int64_t n_c, const double* v0, const double* y_x,
+                                                                  int64_t ldyx, const double* y_c, int64_t ldyc, const double* yw,
+                                                                  double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc) {
+  const int64_t b = blockIdx.x / KB_ROW_BLOCKS, blk = blockIdx.x % KB_ROW_BLOCKS;
+  const int64_t N = n_x + n_c;
+  double y[KB_MAX];
+#pragma unroll
+  for (int j = 0; j < KB_MAX; ++j) y[j] = j < nb ? yw[b * 16 + j] : 0.0;
+  for (int64_t k = blk * KB_THREADS + threadIdx.x; k < N; k += (int64_t)KB_ROW_BLOCKS * KB_THREADS) {
+    double v = v0[b * N + k];
+#pragma unroll
+    for (int j = 0; j < KB_MAX; ++j)
+      if (j < nb) v -= y[j] * kb_seg(y_x, ldyx, y_c, ldyc, b * nb + j, k, n_x);
+    if (k < n_x) sol_x[b * ldsx + k] = v;
+    else sol_c[b * ldsc + (k - n_x)] = v;
+  }
+}
+
+}  // namespace dto

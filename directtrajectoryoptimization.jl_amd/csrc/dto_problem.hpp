@@ -18,6 +18,7 @@ struct SolverState;  // dto_solver.cpp
 struct ImState;      // dto_solver.cpp: instance-major engine
 struct WideState;    // dto_solver.cpp: solver state of the tile (MFMA) path
 struct WideKkt;      // dto_solver.cpp: tile path, the linear solver alone (dto_kkt_assemble / factor / solve)
+struct KktBorder;    // dto_solver.cpp: workspace of dto_kkt_border_factor / dto_kkt_border_solve
 
 // dto_solver_trace: a HIP event pair around every kernel launch of the solver entry points, on the stream the kernel is launched
 // on (the caller's, or the low-priority one of the early back substitutions) -- so that a caller can report what each kernel
@@ -62,6 +63,7 @@ struct Problem {
   ImState* im = nullptr;
   WideState* wide = nullptr;   // tile path: iterate, multipliers and host records of the batch begun last
   WideKkt* wide_kkt = nullptr; // tile path: the system assembled last by dto_kkt_assemble; its factor lives in wide_fac
+  KktBorder* kkt_border = nullptr;   // both paths: Y = K^-1 G' and the LU of the Schur complement of dto_kkt_border_factor
   int* d_shift_keep = nullptr; // dto_solver_shift_keep_rows: [Nc] 1 = the multiplier of this row stays with its knot (NULL: none)
   double* d_bnd = nullptr;     // dto_solver_set_bounds (tile path): per-instance bounds [2][bnd_B][Nz], lower then upper (NULL: shared)
   int64_t bnd_B = 0;

@@ -19,6 +19,7 @@
 #include "dto_kkt_kernels.hpp"
 #include "dto_im_kernels.hpp"
 #include "dto_wide_kernels.hpp"
+#include "dto_border_kernels.hpp"
 #include "dto_problem.hpp"
 
 #define HIP_TRY(expr)                                       \
@@ -147,10 +148,12 @@ struct ImState {
 
 static void release_wide(Problem* p);
 static void release_wide_kkt(Problem* p);
+static void release_kkt_border(Problem* p);
 
 void Problem::free_solver() {
   release_wide(this);
   release_wide_kkt(this);
+  release_kkt_border(this);
   if (solver) {
     solver->release();
     delete solver;
@@ -259,9 +262,37 @@ struct WideKkt {
 static void release_wide_kkt(Problem* p) {
   if (p->wide_kkt) { p->wide_kkt->release(); delete p->wide_kkt; p->wide_kkt = nullptr; }
 }
+// ---- both paths: what dto_kkt_border_factor left for dto_kkt_border_solve (dto_border_kernels.hpp).  `valid` is cleared by
+//      dto_kkt_assemble, dto_kkt_factor and everything that takes the factor or the assembled system
+struct KktBorder {
+  bool valid = false;
+  int nb = 0;
+  int64_t B = 0;
+  double *g = nullptr, *y = nullptr;   // [B * nb][Nz + Nc] each: the panel of border rows (the right-hand sides) and Y = K^-1 G'
+  double *part = nullptr;              // [B][chunks][256]: partial products of k_border_gram
+  double *lu = nullptr, *yw = nullptr; // [B][256] LU of S, [B][16] border unknowns of the last solve
+  double *v0 = nullptr;                // [B][Nz + Nc]: K^-1 r of the last solve
+  size_t cap_g = 0, cap_y = 0, cap_part = 0, cap_lu = 0, cap_yw = 0, cap_v0 = 0;   // doubles allocated
+  int* iw = nullptr;                   // [B][16] pivots, then [2][B] flags (negdef, singular)
+  size_t cap_iw = 0;
+  void release() {
+    for (void* q : {(void*)g, (void*)y, (void*)part, (void*)lu, (void*)yw, (void*)v0, (void*)iw})
+      if (q) (void)hipFree(q);
+    g = y = part = lu = yw = v0 = nullptr; iw = nullptr;
+    cap_g = cap_y = cap_part = cap_lu = cap_yw = cap_v0 = cap_iw = 0;
+    valid = false; nb = 0; B = 0;
+  }
+};
+static void release_kkt_border(Problem* p) {
+  if (p->kkt_border) { p->kkt_border->release(); delete p->kkt_border; p->kkt_border = nullptr; }
+}
+static inline void kkt_border_taken(Problem* p) {
+  if (p->kkt_border) p->kkt_border->valid = false;
+}
 // every other writer of p->wide_fac calls this before it launches
 static inline void wide_fac_taken(Problem* p) {
   if (p->wide_kkt) p->wide_kkt->factored = false;
+  kkt_border_taken(p);
 }
 static inline void wide_args_no_linear(dto_wide_args& a) {
   a.sigma_x = a.sigma_c = nullptr; a.ldsx = a.ldsc = 0; a.nneg = nullptr;
@@ -356,6 +387,7 @@ static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_syste
   if (!p->wide_kkt) p->wide_kkt = new WideKkt();
   WideKkt& K = *p->wide_kkt;
   K.assembled = K.factored = false;
+  kkt_border_taken(p);
   dto_wide_info info;
   p->vt->wide_info(&info);
   const size_t B = (size_t)b->B, Nz = (size_t)L.Nz, Nc = (size_t)std::max<int64_t>(1, L.Nc), Nw = (size_t)L.Nw;
@@ -404,6 +436,7 @@ static int wide_kkt_factor(Problem* p, int32_t* inertia_ok, int32_t* num_negativ
   if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
   WideKkt& K = *p->wide_kkt;
   K.factored = false;
+  kkt_border_taken(p);
   dto_wide_info info;
   p->vt->wide_info(&info);
   if (p->wide_fac_len < (size_t)K.B * (size_t)p->L.T * (size_t)info.fac_stage) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
@@ -3758,6 +3791,7 @@ int dto_kkt_assemble(dto_problem* h, const dto_batch* b, const dto_kkt_system* s
   if ((sys->sigma_x && sys->ldsx < p->L.Nz) || (sys->sigma_c && sys->ldsc < p->L.Nc)) return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if (p->vt->launch_wide) return dto::wide_kkt_assemble(p, b, sys);   // tile path: the factor is stored, a solve is substitution only
   // models with GeneralConstraint rows: this is the STAGE part of K (dynamics + stage rows); the border is the caller's
+  dto::kkt_border_taken(p);
   int rc = dto::ensure_state(p, b->B, true);
   if (rc) return rc;
   p->im_active = false;
@@ -3794,6 +3828,7 @@ int dto_kkt_factor(dto_problem* h, int32_t* inertia_ok, int32_t* num_negative, v
   Problem* p = reinterpret_cast<Problem*>(h);
   if (p && p->vt->launch_wide) return dto::wide_kkt_factor(p, inertia_ok, num_negative, (hipStream_t)stream);
   if (!p || !p->solver || !p->solver->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  dto::kkt_border_taken(p);
   SolverState& S = *p->solver;
   hipStream_t st = (hipStream_t)stream;
   dto_kkt_args a;
@@ -3892,6 +3927,115 @@ int dto_kkt_solve_refined(dto_problem* h, int passes, const double* rhs_x, int64
   if ((rc = check_kkt_vectors(p, passes < 0 || passes > 4 ? "passes outside 0..4" : nullptr, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc)))
     return rc;
   return dto::wide_kkt_solve_refined(p, passes, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, resid, (hipStream_t)stream);
+}
+
+// ---- bordered solves against the factor (dto_border_kernels.hpp): [K G'; G C] [v; y] = [r; s] by the Schur complement on the
+//      border.  Y = K^-1 G' and v0 = K^-1 r come from the entry points above -- the panel substitution and the single
+//      substitution of the tile path, nb + 1 sweeps of the lane path -- so both paths share everything below.
+int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t ldgx, const double* g_c, int64_t ldgc, const double* c,
+                          int64_t ldc, int32_t* schur_negdef, int32_t* schur_singular, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  const bool wide = p->vt->launch_wide != nullptr;
+  if (wide ? !p->wide_kkt || !p->wide_kkt->assembled : !p->solver || !p->solver->assembled)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (nb < 1) return set_error(DTO_ERR_INVALID, "dto_kkt_border_factor: nb < 1");
+  if (nb > dto::KB_MAX) return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_border_factor: more than 16 border rows (one panel of right-hand sides)");
+  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc;
+  if (!g_x) return set_error(DTO_ERR_INVALID, "null argument");
+  if (ldgx < Nz || (g_c && ldgc < Nc) || (c && ldc < nb * nb)) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (wide && !p->wide_kkt->factored)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_factor has not been called (or dto_kkt_step_batch / the solver has used the factor storage since)");
+  const int64_t B = wide ? p->wide_kkt->B : p->solver->B;
+  if (!p->kkt_border) p->kkt_border = new dto::KktBorder();
+  dto::KktBorder& W = *p->kkt_border;
+  W.valid = false;
+  // doubles of k per workgroup of k_border_gram, rounded up to the slab; read at every call so that a test can force several
+  // chunks on a small system (the sums of a result depend on it, nothing else does)
+  int64_t chunk = dto::KB_CHUNK_DEFAULT;
+  if (const char* e = getenv("DTO_BORDER_GRAM_CHUNK")) {
+    const long long v = atoll(e);
+    if (v > 0) chunk = std::min<long long>(v, (long long)1 << 40);
+  }
+  chunk = (chunk + dto::KB_KT - 1) / dto::KB_KT * dto::KB_KT;
+  const int64_t n_c = g_c ? Nc : 0;   // without g_c the constraint part of every border row is zero: the product skips it
+  const int chunks = (int)((Nz + n_c + chunk - 1) / chunk);
+  const size_t rows = (size_t)B * (size_t)nb;
+  auto grow = [&](double** ptr, size_t* cap, size_t need, const char* name, const std::string& shape) {
+    return dto::wide_kkt_grow(ptr, cap, need, ("dto_kkt_border_factor: hipMalloc of " + std::string(name) + " (" + std::to_string(need * sizeof(double)) +
+                                               " bytes: " + shape + ")").c_str());
+  };
+  const std::string panel = std::to_string(B) + " instances x " + std::to_string(nb) + " rows x " + std::to_string(N) + " doubles";
+  if ((rc = grow(&W.g, &W.cap_g, rows * (size_t)N, "the border panel", panel))) return rc;
+  if ((rc = grow(&W.y, &W.cap_y, rows * (size_t)N, "K^-1 G'", panel))) return rc;
+  if ((rc = grow(&W.part, &W.cap_part, (size_t)B * (size_t)chunks * 256, "the partial products",
+                 std::to_string(B) + " instances x " + std::to_string(chunks) + " chunks x 256 doubles"))) return rc;
+  if ((rc = grow(&W.lu, &W.cap_lu, (size_t)B * 256, "the LU of the Schur complement", std::to_string(B) + " instances x 256 doubles"))) return rc;
+  if ((rc = grow(&W.yw, &W.cap_yw, (size_t)B * 16, "the border unknowns", std::to_string(B) + " instances x 16 doubles"))) return rc;
+  if ((rc = grow(&W.v0, &W.cap_v0, (size_t)B * (size_t)N, "K^-1 r", std::to_string(B) + " instances x " + std::to_string(N) + " doubles"))) return rc;
+  if (W.cap_iw < (size_t)B * 18) {
+    if (W.iw) (void)hipFree(W.iw);
+    W.iw = nullptr; W.cap_iw = 0;
+    hipError_t e = hipMalloc((void**)&W.iw, (size_t)B * 18 * sizeof(int));
+    if (e != hipSuccess) return dto::hip_fail(e, ("dto_kkt_border_factor: hipMalloc of pivots and flags (" + std::to_string((size_t)B * 18 * sizeof(int)) + " bytes)").c_str());
+    W.cap_iw = (size_t)B * 18;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the panel of right-hand sides: row b * nb + j = [g_x row; g_c row or zeros]
+  const size_t pitch = (size_t)N * sizeof(double);
+  HIP_TRY(hipMemcpy2DAsync(W.g, pitch, g_x, (size_t)ldgx * sizeof(double), (size_t)Nz * sizeof(double), rows, hipMemcpyDeviceToDevice, st));
+  if (Nc > 0) {
+    if (g_c) HIP_TRY(hipMemcpy2DAsync(W.g + Nz, pitch, g_c, (size_t)ldgc * sizeof(double), (size_t)Nc * sizeof(double), rows, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(hipMemset2DAsync(W.g + Nz, pitch, 0, (size_t)Nc * sizeof(double), rows, st));
+  }
+  if ((rc = dto_kkt_solve_multi(h, nb, W.g, N, W.g + Nz, N, W.y, N, W.y + Nz, N, stream))) return rc;
+  int* piv = W.iw;
+  int* flags = W.iw + (size_t)B * 16;
+  hipLaunchKernelGGL(dto::k_border_gram, dim3((unsigned)(B * chunks)), dim3(dto::KB_THREADS), 0, st, (int)nb, Nz, n_c, chunk, chunks,
+                     (const double*)W.g, N, (const double*)(W.g + Nz), N, (const double*)W.y, N, (const double*)(W.y + Nz), N, W.part);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dto::k_border_schur, dim3((unsigned)B), dim3(64), 0, st, B, (int)nb, chunks, (const double*)W.part, c, ldc, W.lu, piv, flags);
+  HIP_TRY(hipGetLastError());
+  // g_x / g_c / c have been consumed when this returns (and the flags are there)
+  std::vector<int> fl(2 * (size_t)B);
+  if (schur_negdef || schur_singular) HIP_TRY(hipMemcpyAsync(fl.data(), flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < B; ++i) {
+    if (schur_negdef) schur_negdef[i] = fl[(size_t)i];
+    if (schur_singular) schur_singular[i] = fl[(size_t)(B + i)];
+  }
+  W.nb = (int)nb; W.B = B;
+  W.valid = true;
+  return DTO_OK;
+}
+
+int dto_kkt_border_solve(dto_problem* h, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, const double* rhs_b,
+                         int64_t ldrb, double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, double* sol_b, int64_t ldsb, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  if (!p->kkt_border || !p->kkt_border->valid)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_border_factor has not been called (or dto_kkt_assemble, dto_kkt_factor, dto_kkt_step_batch or the "
+                                      "solver has run since)");
+  if ((rc = check_kkt_vectors(p, nullptr, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc))) return rc;
+  dto::KktBorder& W = *p->kkt_border;
+  if (!rhs_b || !sol_b) return set_error(DTO_ERR_INVALID, "null argument");
+  if (ldrb < W.nb || ldsb < W.nb) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc, B = W.B;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = dto_kkt_solve(h, rhs_x, ldrx, rhs_c, ldrc, W.v0, N, W.v0 + Nz, N, stream))) return rc;
+  const int* singular = W.iw + (size_t)B * 17;
+  hipLaunchKernelGGL(dto::k_border_rhs, dim3((unsigned)B), dim3(dto::KB_RHS_THREADS), 0, st, W.nb, Nz, Nc, (const double*)W.y, N,
+                     (const double*)(W.y + Nz), N, rhs_x, ldrx, rhs_c, ldrc, rhs_b, ldrb, (const double*)W.lu, (const int*)W.iw, singular, sol_b, ldsb,
+                     W.yw);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dto::k_border_sub, dim3((unsigned)(B * dto::KB_ROW_BLOCKS)), dim3(dto::KB_THREADS), 0, st, W.nb, Nz, Nc, (const double*)W.v0,
+                     (const double*)W.y, N, (const double*)(W.y + Nz), N, (const double*)W.yw, sol_x, ldsx, sol_c, ldsc);
+  HIP_TRY(hipGetLastError());
+  return DTO_OK;
 }
 
 int dto_shard_range(int64_t total, int rank, int world, int64_t* first, int64_t* count) {

@@ -815,6 +815,34 @@ class Solver:
         capi.check(self._solve_nlp._lib.dto_kkt_solve_refined(self._solve_nlp._h, int(passes), rhs_x_ptr, ldrx, rhs_c_ptr, ldrc,
                                                               sol_x_ptr, ldsx, sol_c_ptr, ldsc, resid_ptr or None, stream or None))
 
+    def kkt_border_factor(self, nb, g_x_ptr, ldgx, g_c_ptr=0, ldgc=0, c_ptr=0, ldc=0, stream=0):
+        """Border of nb (1 .. 16) rows per instance against the system factorised last (include/dto.h: dto_kkt_border_factor):
+        [[K, G'], [G, C]] with row j of instance b in row b * nb + j of g_x ([B * nb][ldgx]) and g_c ([B * nb][ldgc], 0 = zero),
+        C as [B][ldc] row-major nb x nb of which the symmetric part is used (0 = zero block).  Device pointers in the SOLVER's
+        layout: for a 17 .. 63-state problem the rows of G are in the embedding's layout, as the right-hand sides of
+        kkt_solve are (pad_batch maps the variables' part: the padding states get zero). Computes Y = K^-1 G' (one kkt_solve_multi) and the pivoted LU of S = C - G Y, waits for the
+        stream, and returns (negdef[B], singular[B]): -S positive definite, a zero pivot in the LU of S (kkt_border_solve then
+        returns NaN for that instance).  kkt_assemble, kkt_factor, kkt_step_batch and the solver invalidate the border."""
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (nb, g_x_ptr, g_c_ptr, c_ptr)):
+            raise TypeError("kkt_border_factor takes nb and device pointers as integers (tensor.data_ptr())")
+        B = getattr(self, "_B", 0) or 0
+        negdef, singular = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        capi.check(self._solve_nlp._lib.dto_kkt_border_factor(self._solve_nlp._h, int(nb), g_x_ptr or None, ldgx, g_c_ptr or None, ldgc,
+                                                              c_ptr or None, ldc, negdef.ctypes.data_as(capi.c_int32_p),
+                                                              singular.ctypes.data_as(capi.c_int32_p), stream or None))
+        return negdef, singular
+
+    def kkt_border_solve(self, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, rhs_b_ptr, ldrb, sol_x_ptr, ldsx, sol_c_ptr, ldsc, sol_b_ptr, ldsb,
+                         stream=0):
+        """[[K, G'], [G, C]] [sol_x; sol_c; sol_b] = [rhs_x; rhs_c; rhs_b] for the border of kkt_border_factor (include/dto.h:
+        dto_kkt_border_solve): one right-hand side per instance, rhs_b / sol_b are [B][ld] with nb entries, the other arrays as
+        for kkt_solve (solver layout).  Substitution only: one kkt_solve and two passes over Y.  The solutions must not overlap
+        the right-hand sides."""
+        if (sol_x_ptr and sol_x_ptr == rhs_x_ptr) or (sol_c_ptr and sol_c_ptr == rhs_c_ptr) or (sol_b_ptr and sol_b_ptr == rhs_b_ptr):
+            raise ValueError("kkt_border_solve: the solutions must not overlap the right-hand sides")
+        capi.check(self._solve_nlp._lib.dto_kkt_border_solve(self._solve_nlp._h, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, rhs_b_ptr, ldrb,
+                                                             sol_x_ptr, ldsx, sol_c_ptr, ldsc, sol_b_ptr, ldsb, stream or None))
+
     def iterate_batch(self, n, stream=0):
         capi.check(self._solve_nlp._lib.dto_solver_iterate(self._solve_nlp._h, int(n), stream or None))
 

@@ -292,6 +292,46 @@ int dto_kkt_multiply(dto_problem* p, const double* v_x, int64_t ldvx, const doub
                      int64_t ldox, double* out_c, int64_t ldoc, void* stream);
 int dto_kkt_solve_refined(dto_problem* p, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
                           double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, double* resid, void* stream);
+/* Bordered solves against the factor of dto_kkt_factor.  For every instance, with K the matrix of dto_kkt_assemble
+ * (dimension N = num_variables + num_constraint):
+ *     [ K   G' ] [ v ]   [ r ]        G: nb x N (border rows, 1 <= nb <= 16)
+ *     [ G   C  ] [ y ] = [ s ]        C: nb x nb, dense; only its symmetric part is used; may be absent (zero)
+ * by the Schur complement on the border: Y = K^-1 G' (one dto_kkt_solve_multi of nb right-hand sides), S = C - G Y,
+ * v0 = K^-1 r, y = S^-1 (s - Y' r) (G K^-1 r = Y' r because K is symmetric), v = v0 - Y y.  dto_kkt_border_factor does
+ * everything that does not depend on (r, s) and keeps Y and the pivoted LU of S with the handle; dto_kkt_border_solve is one
+ * dto_kkt_solve plus two passes over Y, any number of times per border.
+ * dto_kkt_border_factor -- row j of instance b is row b * nb + j of g_x ([B * nb][ldgx], num_variables entries) and of g_c
+ * ([B * nb][ldgc], num_constraint entries; NULL = zero).  c: [B][ldc] with ldc >= nb * nb, row-major nb x nb, of which
+ * (C + C')/2 is used; NULL = zero block.  All three are DEVICE arrays; they have been consumed when the call returns (it waits
+ * for the stream) and may change afterwards.  schur_negdef (HOST [B], may be NULL): 1 when -S is positive definite (K
+ * quasi-definite and S negative definite is the inertia an interior-point caller wants), else 0.  schur_singular (HOST [B],
+ * may be NULL): 1 when the pivoted LU of S met a zero pivot; solves of that instance then return NaN in every entry of
+ * sol_x, sol_c and sol_b, the other instances are not affected.
+ * dto_kkt_border_solve -- one bordered right-hand side per instance: rhs_x / rhs_c / sol_x / sol_c as for dto_kkt_solve,
+ * rhs_b / sol_b are [B][ld] with nb entries.  The solutions must not overlap the right-hand sides.
+ * State: dto_kkt_assemble, dto_kkt_factor, dto_kkt_border_factor, then dto_kkt_border_solve any number of times.
+ * dto_kkt_border_factor before dto_kkt_assemble or (tile path) before dto_kkt_factor fails with DTO_ERR_INVALID and the
+ * messages of dto_kkt_solve_multi; dto_kkt_border_solve without a border in place fails with DTO_ERR_INVALID.  A new
+ * dto_kkt_assemble or dto_kkt_factor invalidates the border, and so does everything that takes the factor storage
+ * (dto_kkt_step_batch, the solver entry points): dto_kkt_border_factor has to be called again.  nb < 1, a null g_x, rhs_b or
+ * sol_b and a leading dimension below its row length are DTO_ERR_INVALID; nb > 16 is DTO_ERR_UNSUPPORTED (one panel of
+ * right-hand sides is the limit).  A refused call writes nothing.  dto_kkt_solve, dto_kkt_solve_multi, dto_kkt_multiply and
+ * dto_kkt_solve_refined may be interleaved freely with border solves on one factorisation and return what they return
+ * without a border, bit for bit.  Results are bit-identical from run to run (no atomic sums; G Y is summed in chunks of
+ * 2048 entries of a row, DTO_BORDER_GRAM_CHUNK in the environment of a dto_kkt_border_factor call sets another length).
+ * Workspace kept with the handle, allocated by dto_kkt_border_factor (sizes are reported if that fails): the panel of border
+ * rows and Y, B x nb x N doubles each, v0 with B x N, the partial products of G Y (256 doubles per 2048 entries of a row and
+ * instance) and a few hundred doubles per instance for the LU, the pivots and y.  Per path:
+ * - tile path: Y comes from the panel substitution (the stored records are read once forward and once backward for all nb
+ *   rows), v0 from the single substitution; nothing is factorised again;
+ * - lane-per-instance path: no factor is stored there, so dto_kkt_border_factor costs nb sweeps (dto_kkt_solve_multi) and
+ *   dto_kkt_border_solve one sweep (dto_kkt_solve) plus the two passes over Y -- against nb + 1 sweeps per right-hand side
+ *   without it.  As dto_kkt_solve on that path, the calls need dto_kkt_assemble only. */
+int dto_kkt_border_factor(dto_problem* p, int64_t nb, const double* g_x, int64_t ldgx, const double* g_c, int64_t ldgc,
+                          const double* c, int64_t ldc, int32_t* schur_negdef, int32_t* schur_singular, void* stream);
+int dto_kkt_border_solve(dto_problem* p, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
+                         const double* rhs_b, int64_t ldrb, double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc,
+                         double* sol_b, int64_t ldsb, void* stream);
 
 /* Batched interior-point solve, one independent NLP per instance, same structure, different guesses.
  * x0: DEVICE [B][ldx] initial guesses (what initialize_states!/initialize_controls! set,

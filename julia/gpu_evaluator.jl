@@ -277,6 +277,35 @@ function kkt_solve_refined!(ev::GPUEvaluator, rhs_x::Ptr{Float64}, rhs_c::Ptr{Fl
 end
 
 """
+    kkt_border_factor!(ev, nb, B, g_x, g_c, c) -> (negdef, singular)
+    kkt_border_solve!(ev, nb, rhs_x, rhs_c, rhs_b, sol_x, sol_c, sol_b)
+
+A border of `nb` (1..16) rows per instance against the factor of `dto_kkt_factor`: `[K G'; G C] [v; y] = [r; s]`
+(`dto_kkt_border_factor` / `dto_kkt_border_solve`, both paths).  DEVICE arrays: `g_x` is num_variables × (nb·B), `g_c`
+num_constraint × (nb·B) or `C_NULL` (zero), `c` (nb·nb) × B or `C_NULL` (zero; its symmetric part is used), `rhs_b` / `sol_b`
+nb × B.  `kkt_border_factor!` returns two host `Int32` vectors: −S positive definite, zero pivot in the LU of S = C − G K⁻¹ G'.
+A new `dto_kkt_assemble` / `dto_kkt_factor`, `dto_kkt_step_batch` or a solve on the handle invalidates the border.
+"""
+function kkt_border_factor!(ev::GPUEvaluator, nb::Integer, B::Integer, g_x::Ptr{Float64}, g_c::Ptr{Float64}, c::Ptr{Float64})
+    nz, nc = ev.num_variables, ev.num_constraint
+    negdef, singular = Vector{Int32}(undef, B), Vector{Int32}(undef, B)
+    dto_check(ccall((:dto_kkt_border_factor, libdto), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}),
+                    ev.handle, nb, g_x, nz, g_c, nc, c, nb * nb, negdef, singular, C_NULL))
+    return negdef, singular
+end
+
+function kkt_border_solve!(ev::GPUEvaluator, nb::Integer, rhs_x::Ptr{Float64}, rhs_c::Ptr{Float64}, rhs_b::Ptr{Float64},
+                           sol_x::Ptr{Float64}, sol_c::Ptr{Float64}, sol_b::Ptr{Float64})
+    nz, nc = ev.num_variables, ev.num_constraint
+    dto_check(ccall((:dto_kkt_border_solve, libdto), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    ev.handle, rhs_x, nz, rhs_c, nc, rhs_b, nb, sol_x, nz, sol_c, nc, sol_b, nb, C_NULL))
+    return nothing
+end
+
+"""
     set_bounds_batch!(ev, lower, upper)
     set_bounds_batch!(ev, nothing, nothing)
 
