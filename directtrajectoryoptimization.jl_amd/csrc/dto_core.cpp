@@ -53,51 +53,45 @@ using dto::set_error;
 // ------------------------------------------------------------------------------------------------
 namespace dto {
 
-static int upload_ints(const std::vector<int>& v, int** dptr) {
-  const size_t bytes = std::max<size_t>(1, v.size()) * sizeof(int);
-  HIP_TRY(hipMalloc((void**)dptr, bytes));
-  if (!v.empty()) HIP_TRY(hipMemcpy(*dptr, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+static int upload_ints(const std::vector<int>& v, DevBuf<int>& d) {
+  HIP_TRY(d.alloc(v.size()));
+  if (!v.empty()) HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
   return DTO_OK;
 }
 
+// (a call that fails half-way may be repeated: every alloc releases what an earlier attempt left in the buffer)
 int Problem::ensure_device() {
   if (dev_ready) return DTO_OK;
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n == 0) return set_error(DTO_ERR_DEVICE, "no HIP device available (the evaluator has no CPU path)");
   int rc;
-  if ((rc = upload_ints(L.kind, &d_kind))) return rc;
-  if ((rc = upload_ints(L.zoff, &d_zoff))) return rc;
-  if ((rc = upload_ints(L.woff, &d_woff))) return rc;
-  if ((rc = upload_ints(L.cdoff, &d_cdoff))) return rc;
-  if ((rc = upload_ints(L.ccoff, &d_ccoff))) return rc;
-  if ((rc = upload_ints(L.jdoff, &d_jdoff))) return rc;
-  if ((rc = upload_ints(L.jcoff, &d_jcoff))) return rc;
-  if ((rc = upload_ints(L.hoff, &d_hoff))) return rc;
-  if ((rc = upload_ints(L.hmap_cost, &d_hmap_cost))) return rc;
-  if ((rc = upload_ints(L.hmap_dyn_own, &d_hmap_dyn_own))) return rc;
-  if ((rc = upload_ints(L.hmap_dyn_next, &d_hmap_dyn_next))) return rc;
-  if ((rc = upload_ints(L.hmap_con, &d_hmap_con))) return rc;
-  HIP_TRY(hipMalloc((void**)&d_params, std::max<size_t>(1, L.Nw) * sizeof(double)));
+  if ((rc = upload_ints(L.kind, d_kind))) return rc;
+  if ((rc = upload_ints(L.zoff, d_zoff))) return rc;
+  if ((rc = upload_ints(L.woff, d_woff))) return rc;
+  if ((rc = upload_ints(L.cdoff, d_cdoff))) return rc;
+  if ((rc = upload_ints(L.ccoff, d_ccoff))) return rc;
+  if ((rc = upload_ints(L.jdoff, d_jdoff))) return rc;
+  if ((rc = upload_ints(L.jcoff, d_jcoff))) return rc;
+  if ((rc = upload_ints(L.hoff, d_hoff))) return rc;
+  if ((rc = upload_ints(L.hmap_cost, d_hmap_cost))) return rc;
+  if ((rc = upload_ints(L.hmap_dyn_own, d_hmap_dyn_own))) return rc;
+  if ((rc = upload_ints(L.hmap_dyn_next, d_hmap_dyn_next))) return rc;
+  if ((rc = upload_ints(L.hmap_con, d_hmap_con))) return rc;
+  HIP_TRY(d_params.alloc(L.Nw));
   if (L.Nw) HIP_TRY(hipMemcpy(d_params, L.params.data(), L.Nw * sizeof(double), hipMemcpyHostToDevice));
   // single-instance staging for the host-pointer callbacks
   const size_t out_len = (size_t)std::max<int64_t>({L.Nz, L.Nc, L.nnzJ, L.nnzH, (int64_t)L.T, 1});
-  HIP_TRY(hipMalloc((void**)&d_x1, std::max<size_t>(1, L.Nz) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&d_mu1, std::max<size_t>(1, L.Nc) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&d_out1, out_len * sizeof(double)));
+  HIP_TRY(d_x1.alloc(L.Nz));
+  HIP_TRY(d_mu1.alloc(L.Nc));
+  HIP_TRY(d_out1.alloc(out_len));
   HIP_TRY(hipStreamCreate(&stream));
   dev_ready = true;
   return DTO_OK;
 }
 
 int Problem::ensure_scratch(int64_t B) {
-  const size_t need = (size_t)B * (size_t)L.T;
-  if (need <= scratch_len) return DTO_OK;
-  if (d_scratch) HIP_TRY(hipFree(d_scratch));
-  d_scratch = nullptr;
-  scratch_len = 0;
-  HIP_TRY(hipMalloc((void**)&d_scratch, need * sizeof(double)));
-  scratch_len = need;
+  HIP_TRY(d_scratch.grow((size_t)B * (size_t)L.T));
   return DTO_OK;
 }
 
@@ -164,9 +158,9 @@ int Problem::build_kkt_csr() {
   int rc = ensure_device();
   if (rc) { csr_rowptr.clear(); csr_col.clear(); return rc; }
   const size_t nnz = csr_col.size();
-  HIP_TRY(hipMalloc((void**)&d_csr_h, std::max<size_t>(1, nnz) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&d_csr_j, std::max<size_t>(1, nnz) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&d_csr_diag, std::max<size_t>(1, nnz)));
+  HIP_TRY(d_csr_h.alloc(nnz));
+  HIP_TRY(d_csr_j.alloc(nnz));
+  HIP_TRY(d_csr_diag.alloc(nnz));
   HIP_TRY(hipMemcpy(d_csr_h, sh.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_csr_j, sj.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_csr_diag, sd.data(), nnz, hipMemcpyHostToDevice));
@@ -191,16 +185,10 @@ static __global__ void k_kkt_csr_values(int64_t nnz, const int* src_h, const int
 }
 
 Problem::~Problem() {
-  if (d_csr_h) (void)hipFree(d_csr_h);
-  if (d_csr_j) (void)hipFree(d_csr_j);
-  if (d_csr_diag) (void)hipFree(d_csr_diag);
-  for (int* p : {d_kind, d_zoff, d_woff, d_cdoff, d_ccoff, d_jdoff, d_jcoff, d_hoff, d_hmap_cost, d_hmap_dyn_own,
-                 d_hmap_dyn_next, d_hmap_con, d_csc_ptr, d_csc_k, d_csc_row, d_var_fixed, d_shift_keep})
-    if (p) (void)hipFree(p);
-  for (double* p : {d_params, d_x1, d_mu1, d_out1, d_scratch, wide_fac, border_ws, d_bnd})
-    if (p) (void)hipFree(p);
-  if (wide_flags) (void)hipFree(wide_flags);
   free_solver();
+  // the DevBuf members free themselves after this body; their hipFree calls used to idle the device before the stream and the
+  // plugin (which holds the kernels) go: keep that order
+  if (dev_ready) (void)hipDeviceSynchronize();
   delete trace;
   if (stream) (void)hipStreamDestroy(stream);
   if (dl) dlclose(dl);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "dto_layout.hpp"
@@ -13,6 +14,44 @@ namespace dto {
 
 int set_error(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
+
+// The one owner of device memory in the runtime library: a move-only pointer + element count that frees in its destructor.
+// alloc / alloc_zeroed / grow release what is held BEFORE they allocate (the lane state is tens of gigabytes at the bench batch:
+// old and new must never exist together) and never keep the contents; after a failure the buffer is empty and the error is
+// returned.  Converts to T* so that argument structs and kernel launches read as with a raw pointer.
+template <class T>
+class DevBuf {
+  T* p_ = nullptr;
+  size_t n_ = 0;
+
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { reset(); p_ = std::exchange(o.p_, nullptr); n_ = std::exchange(o.n_, 0); }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {   // (every hipFree is a device synchronisation: none for an empty buffer)
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr; n_ = 0;
+  }
+  hipError_t alloc(size_t n) {   // max(1, n) elements, not initialised
+    reset();
+    n = n ? n : 1;
+    const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T));
+    if (e != hipSuccess) p_ = nullptr; else n_ = n;
+    return e;
+  }
+  hipError_t alloc_zeroed(size_t n) {   // ... zero-filled on the null stream
+    hipError_t e = alloc(n);
+    if (e == hipSuccess && (e = hipMemset(p_, 0, n_ * sizeof(T))) != hipSuccess) reset();
+    return e;
+  }
+  hipError_t grow(size_t n) { return n_ >= n ? hipSuccess : alloc(n); }   // no-op while n elements fit
+  size_t size() const { return n_; }   // elements allocated
+  operator T*() const { return p_; }
+};
 
 struct SolverState;  // dto_solver.cpp
 struct ImState;      // dto_solver.cpp: instance-major engine
@@ -50,22 +89,21 @@ struct Problem {
   Layout L;
   // device tables
   bool dev_ready = false;
-  int *d_kind = nullptr, *d_zoff = nullptr, *d_woff = nullptr, *d_cdoff = nullptr, *d_ccoff = nullptr;
-  int *d_jdoff = nullptr, *d_jcoff = nullptr, *d_hoff = nullptr;
-  int *d_hmap_cost = nullptr, *d_hmap_dyn_own = nullptr, *d_hmap_dyn_next = nullptr, *d_hmap_con = nullptr;
-  double* d_params = nullptr;
+  DevBuf<int> d_kind, d_zoff, d_woff, d_cdoff, d_ccoff, d_jdoff, d_jcoff, d_hoff;
+  DevBuf<int> d_hmap_cost, d_hmap_dyn_own, d_hmap_dyn_next, d_hmap_con;
+  DevBuf<double> d_params;
   // single-instance staging for host-pointer callbacks
-  double *d_x1 = nullptr, *d_mu1 = nullptr, *d_out1 = nullptr;
-  double* d_scratch = nullptr;
-  size_t scratch_len = 0;
+  DevBuf<double> d_x1, d_mu1, d_out1;
+  DevBuf<double> d_scratch;
   hipStream_t stream = nullptr;
+  // the solver states are incomplete types outside dto_solver.cpp: raw pointers, deleted by free_solver()
   SolverState* solver = nullptr;
   ImState* im = nullptr;
   WideState* wide = nullptr;   // tile path: iterate, multipliers and host records of the batch begun last
   WideKkt* wide_kkt = nullptr; // tile path: the system assembled last by dto_kkt_assemble; its factor lives in wide_fac
   KktBorder* kkt_border = nullptr;   // both paths: Y = K^-1 G' and the LU of the Schur complement of dto_kkt_border_factor
-  int* d_shift_keep = nullptr; // dto_solver_shift_keep_rows: [Nc] 1 = the multiplier of this row stays with its knot (NULL: none)
-  double* d_bnd = nullptr;     // dto_solver_set_bounds (tile path): per-instance bounds [2][bnd_B][Nz], lower then upper (NULL: shared)
+  DevBuf<int> d_shift_keep;    // dto_solver_shift_keep_rows: [Nc] 1 = the multiplier of this row stays with its knot (empty: none)
+  DevBuf<double> d_bnd;        // dto_solver_set_bounds (tile path): per-instance bounds [2][bnd_B][Nz], lower then upper (empty: shared)
   int64_t bnd_B = 0;
   LaunchTrace* trace = nullptr;   // dto_solver_trace
   int hessian_mode_last = -1;     // dto_solver_hessian_mode: what the last solve / begun batch used
@@ -73,22 +111,19 @@ struct Problem {
   bool im_active = false;  // which engine holds the batch that was begun last
   // factor storage and inertia flags of the wide-stage KKT kernels (wide_fac is shared by dto_kkt_step_batch, the solver and
   // dto_kkt_factor: whoever writes it last owns it, WideKkt::factored says whether that is dto_kkt_factor)
-  double* wide_fac = nullptr;
-  size_t wide_fac_len = 0;
-  int* wide_flags = nullptr;
-  size_t wide_flags_len = 0;
+  DevBuf<double> wide_fac;
+  DevBuf<int> wide_flags;
   // device workspace of the bordered (multi-knot GeneralConstraint) step, kept between steps (eight hipMalloc /
   // hipFree per Newton step -- every hipFree is a device synchronisation)
-  double* border_ws = nullptr;
-  size_t border_ws_len = 0;
+  DevBuf<double> border_ws;
   // Jacobian pattern by columns (entries of a column in COO order) for the device-side products of the bordered step
-  int *d_csc_ptr = nullptr, *d_csc_k = nullptr, *d_csc_row = nullptr;
-  int* d_var_fixed = nullptr;   // [Nz] 1 where lo == hi
+  DevBuf<int> d_csc_ptr, d_csc_k, d_csc_row;
+  DevBuf<int> d_var_fixed;   // [Nz] 1 where lo == hi
 
   // CSR pattern of the KKT matrix in the reference ordering (dto_kkt_csr_structure / dto_kkt_csr_values_batch), built on first use
   std::vector<int64_t> csr_rowptr, csr_col;   // 1-based
-  int *d_csr_h = nullptr, *d_csr_j = nullptr;  // per CSR slot: 0-based index into the Hessian key / Jacobian values, -1 = none
-  signed char* d_csr_diag = nullptr;           // per CSR slot: 1 = primal diagonal (+delta_w), 2 = dual diagonal (-delta_c), 0 = off-diagonal
+  DevBuf<int> d_csr_h, d_csr_j;      // per CSR slot: 0-based index into the Hessian key / Jacobian values, -1 = none
+  DevBuf<signed char> d_csr_diag;    // per CSR slot: 1 = primal diagonal (+delta_w), 2 = dual diagonal (-delta_c), 0 = off-diagonal
   int build_kkt_csr();
 
   int ensure_device();

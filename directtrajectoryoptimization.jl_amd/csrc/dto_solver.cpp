@@ -30,56 +30,59 @@
 
 namespace dto {
 
-struct SolverState {
+// Ownership rule of this file: device memory lives in DevBuf members and locals (dto_problem.hpp) and nowhere else.  A state is
+// rebuilt release-old-then-allocate-new, and a set-up that fails after the old state was dropped leaves an EMPTY state (B = 0),
+// so that the retry hip_fail promises to callers builds it again instead of reusing half of one.
+
+// The device buffers of a SolverState: a base of their own, so that release() drops them all with one assignment.
+struct SolverBufs {
+  DevBuf<double> wtile;                     // per-instance parameters (SoA tiles), allocated on first use
+  DevBuf<int> d_inst_of_slot, d_src_slot;   // dto_solver_repack: d_inst_of_slot is empty while the map is the identity
+  DevBuf<double> repack_tmp;
+  DevBuf<double> sigx, sigc;                // linear-solver entry points: extra diagonals (SoA tiles), allocated on first use
+  DevBuf<int> d_ioff;
+  DevBuf<int64_t> d_recoff, d_facoff;
+  DevBuf<dto_stage_run> d_runs;             // the horizon as runs of one stage kind with constant strides (sequential sweeps)
+  DevBuf<double> d_lo, d_hi;
+  DevBuf<double> z, lam, zl, zu, s, zs;     // SoA state
+  DevBuf<int> tile_fwd_tag, tile_bwd_tag, fwd_started;   // sequential sweeps overlapped through a second stream (k_kkt_bwd_early)
+  DevBuf<double> qn;                        // limited-memory BFGS: history, columns and small matrices per tile (QnRows)
+  // iterative refinement (dto_options.kkt_refinement): cross-stage terms, the step being refined, copy of the records (lazy)
+  DevBuf<double> refq, refvz, refvl, rec_bak;
+  DevBuf<double> z_alt, lam_alt;            // second iterate / multiplier buffers of the fused UPDATE+EVAL pass (lazy)
+  DevBuf<double> dz, dlam, ds;
+  DevBuf<double> rec, fac, part, lspart, scal, filt;
+  DevBuf<double> csum, sfac, xsep, cacc, cpart;
+  DevBuf<int> csync;         // per tile: arrival counters of the in-launch joins of the time-partitioned form (dto_kkt_args.csync)
+  DevBuf<int> d_cstart_all;  // chunk boundaries for P = 1 .. P_cap back to back (a batch that started sequential may
+                             // switch to 2 / 4 chunks when repacking has left too few tiles to fill the GPU)
+};
+
+struct SolverState : SolverBufs {
   int64_t B = 0;
   int G = 0;
   int64_t Ni = 0, rec_total = 0, fac_total = 0, n_bnd = 0;
-  double* wtile = nullptr;      // per-instance parameters (SoA tiles), allocated on first use
   bool use_wtile = false;
   // dto_solver_repack: running instances are moved to the leading tiles; slot <-> instance maps (identity until then)
   int G_active = 0;
   std::vector<int> inst_of_slot, slot_of_inst;
-  int* d_inst_of_slot = nullptr;   // NULL while the map is the identity
-  int* d_src_slot = nullptr;
-  double* repack_tmp = nullptr;
-  size_t repack_tmp_len = 0;
-  double *sigx = nullptr, *sigc = nullptr;  // linear-solver entry points: extra diagonals (SoA tiles), allocated on first use
   bool use_sigx = false, use_sigc = false, assembled = false;
   std::vector<int> ioff;
   std::vector<int64_t> recoff, facoff;
-  int* d_ioff = nullptr;
-  int64_t *d_recoff = nullptr, *d_facoff = nullptr;
-  dto_stage_run* d_runs = nullptr;   // the horizon as runs of one stage kind with constant strides (sequential sweeps)
   int n_runs = 0;
-  double *d_lo = nullptr, *d_hi = nullptr;
-  // SoA state
-  double *z = nullptr, *lam = nullptr, *zl = nullptr, *zu = nullptr, *s = nullptr, *zs = nullptr;
-  // sequential sweeps overlapped through a second stream (k_kkt_bwd_early)
-  int *tile_fwd_tag = nullptr, *tile_bwd_tag = nullptr, *fwd_started = nullptr;
   int sweep_tag = 0;
   hipStream_t stream_lo = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  double* qn = nullptr;                          // limited-memory BFGS: history, columns and small matrices per tile (QnRows)
-  SolverState* cols = nullptr;                   // ... and, for small batches, a second state whose instances are the columns of U
-  size_t qn_len = 0;
-  // iterative refinement (dto_options.kkt_refinement): cross-stage terms, the step being refined, copy of the records (lazy)
-  double *refq = nullptr, *refvz = nullptr, *refvl = nullptr, *rec_bak = nullptr;
-  double *z_alt = nullptr, *lam_alt = nullptr;   // second iterate / multiplier buffers of the fused UPDATE+EVAL pass (lazy)
-  int fuse_state = 0;                            // 0 not decided, 1 buffers allocated, -1 not available (memory, switch)
-  double *dz = nullptr, *dlam = nullptr, *ds = nullptr;
-  double *rec = nullptr, *fac = nullptr, *part = nullptr, *lspart = nullptr, *scal = nullptr, *filt = nullptr;
-  double *csum = nullptr, *sfac = nullptr, *xsep = nullptr, *cacc = nullptr, *cpart = nullptr;
-  int* csync = nullptr; // per tile: arrival counters of the in-launch joins of the time-partitioned form (dto_kkt_args.csync)
+  SolverState* cols = nullptr;   // limited-memory BFGS, small batches: a second state whose instances are the columns of U
+  int fuse_state = 0;   // 0 not decided, 1 buffers allocated, -1 not available (memory, switch)
   int sb = 8;           // stages per wavefront of the stage-parallel kernels (dto_kkt_args.sb)
   int P = 1;            // chunks of the time-partitioned factorisation (current)
   int P0 = 1;           // ... as chosen when the batch was loaded; P_cap: what the chunk arrays are sized for
   int P_cap = 1;
   int forced_P = 0;     // 0 = choose from the batch size
   int n_simd = 1024;
-  int* d_cstart_all = nullptr;   // chunk boundaries for P = 1 .. P_cap back to back (a batch that started sequential may
-                                 // switch to 2 / 4 chunks when repacking has left too few tiles to fill the GPU)
   std::vector<int> cstart;
-  int* d_cstart = nullptr;
+  int* d_cstart = nullptr;   // the block of the current P inside d_cstart_all
   dto_kkt_info info{};
   dto_solver_opts opt{};
   dto_options user{};
@@ -87,44 +90,44 @@ struct SolverState {
   std::vector<double> h_scal;  // host copy of the scalar block
 
   void release() {
-    for (void* p : {(void*)d_ioff, (void*)d_recoff, (void*)d_facoff, (void*)d_lo, (void*)d_hi, (void*)z, (void*)lam,
-                    (void*)zl, (void*)zu, (void*)s, (void*)zs, (void*)dz, (void*)dlam, (void*)ds, (void*)rec,
-                    (void*)fac, (void*)part, (void*)lspart, (void*)scal, (void*)filt, (void*)csum, (void*)sfac, (void*)xsep,
-                    (void*)cacc, (void*)cpart, (void*)d_cstart_all, (void*)wtile, (void*)sigx, (void*)sigc, (void*)d_inst_of_slot,
-                    (void*)d_src_slot, (void*)repack_tmp, (void*)d_runs, (void*)z_alt, (void*)lam_alt, (void*)tile_fwd_tag, (void*)tile_bwd_tag, (void*)fwd_started,
-                    (void*)qn, (void*)csync, (void*)refq, (void*)refvz, (void*)refvl, (void*)rec_bak})
-      if (p) (void)hipFree(p);
-    d_ioff = nullptr; d_recoff = d_facoff = nullptr; d_lo = d_hi = nullptr; d_runs = nullptr; n_runs = 0;
-    z = lam = zl = zu = s = zs = dz = dlam = ds = rec = fac = part = lspart = scal = filt = nullptr;
-    refq = refvz = refvl = rec_bak = nullptr;
-    z_alt = lam_alt = nullptr; fuse_state = 0; qn = nullptr; qn_len = 0; tile_fwd_tag = tile_bwd_tag = fwd_started = nullptr; sweep_tag = 0;
+    static_cast<SolverBufs&>(*this) = SolverBufs();
+    d_cstart = nullptr; n_runs = 0; fuse_state = 0; sweep_tag = 0;
     if (stream_lo) { (void)hipStreamDestroy(stream_lo); stream_lo = nullptr; }
     if (ev_fork) { (void)hipEventDestroy(ev_fork); ev_fork = nullptr; }
     if (ev_join) { (void)hipEventDestroy(ev_join); ev_join = nullptr; }
-    csum = sfac = xsep = cacc = cpart = nullptr; csync = nullptr; d_cstart = nullptr; d_cstart_all = nullptr; wtile = nullptr; use_wtile = false;
-    sigx = sigc = nullptr; use_sigx = use_sigc = assembled = false;
-    d_inst_of_slot = d_src_slot = nullptr; repack_tmp = nullptr; repack_tmp_len = 0; G_active = 0;
+    use_wtile = false;
+    use_sigx = use_sigc = assembled = false;
+    G_active = 0;
     inst_of_slot.clear(); slot_of_inst.clear();
     B = 0; G = 0;
-    if (cols) { cols->release(); delete cols; cols = nullptr; }
+    delete cols; cols = nullptr;
   }
+  ~SolverState() { release(); }
+};
+// releases a state when its set-up returns early (ensure_state, ensure_im_state); `s = nullptr` once the state is complete
+template <class S>
+struct ReleaseOnError {
+  S* s;
+  ~ReleaseOnError() { if (s) s->release(); }
 };
 
 // Device state of the instance-major engine (dto_im_kernels.hpp)
-struct ImState {
+struct ImBufs {
+  DevBuf<int> d_aoff, d_doff, d_coff, d_boff, d_ioff;
+  DevBuf<double> d_lo, d_hi;
+  DevBuf<double> A, R, D, C, Bd;
+  DevBuf<double> part, lspart, scal, filt, wbuf;
+  DevBuf<int> phase;
+  DevBuf<int> lists;   // 3 x B
+  DevBuf<int> ctr;     // [0..2] list lengths, [3..4] sweep tickets, [5..6] running / work left
+};
+struct ImState : ImBufs {
   int64_t B = 0;
   dto_im_info info{};
   std::vector<int> aoff, doff, coff, boff, ioff;
-  int *d_aoff = nullptr, *d_doff = nullptr, *d_coff = nullptr, *d_boff = nullptr, *d_ioff = nullptr;
   int64_t a_total = 0, d_total = 0, c_total = 0, b_total = 0, Ni = 0, n_bnd = 0;
-  double *d_lo = nullptr, *d_hi = nullptr;
-  double *A = nullptr, *R = nullptr, *D = nullptr, *C = nullptr, *Bd = nullptr;
-  double *part = nullptr, *lspart = nullptr, *scal = nullptr, *filt = nullptr, *wbuf = nullptr;
   bool use_w = false;
-  int* phase = nullptr;
-  int* lists = nullptr;   // 3 x B
-  int* ctr = nullptr;     // [0..2] list lengths, [3..4] sweep tickets, [5..6] running / work left
-  int* h_ctr = nullptr;   // pinned host mirror
+  int* h_ctr = nullptr;   // pinned host mirror of ctr
   int nwin_e = 1, nwin_l = 1;
   dto_solver_opts opt{};
   dto_options user{};
@@ -134,37 +137,13 @@ struct ImState {
   std::vector<double> h_scal;
 
   void release() {
-    for (void* q : {(void*)d_aoff, (void*)d_doff, (void*)d_coff, (void*)d_boff, (void*)d_ioff, (void*)d_lo, (void*)d_hi, (void*)A,
-                    (void*)R, (void*)D, (void*)C, (void*)Bd, (void*)part, (void*)lspart, (void*)scal, (void*)filt, (void*)wbuf,
-                    (void*)phase, (void*)lists, (void*)ctr})
-      if (q) (void)hipFree(q);
+    static_cast<ImBufs&>(*this) = ImBufs();
     if (h_ctr) (void)hipHostFree(h_ctr);
-    d_aoff = d_doff = d_coff = d_boff = d_ioff = nullptr; d_lo = d_hi = nullptr;
-    A = R = D = C = Bd = part = lspart = scal = filt = wbuf = nullptr;
-    phase = lists = ctr = h_ctr = nullptr;
+    h_ctr = nullptr;
     B = 0; begun = false; use_w = false;
   }
+  ~ImState() { release(); }
 };
-
-static void release_wide(Problem* p);
-static void release_wide_kkt(Problem* p);
-static void release_kkt_border(Problem* p);
-
-void Problem::free_solver() {
-  release_wide(this);
-  release_wide_kkt(this);
-  release_kkt_border(this);
-  if (solver) {
-    solver->release();
-    delete solver;
-    solver = nullptr;
-  }
-  if (im) {
-    im->release();
-    delete im;
-    im = nullptr;
-  }
-}
 
 static void default_opts(dto_solver_opts& o, const dto_options& u) {
   o.tol = u.tol; o.s_max = u.s_max; o.dual_inf_tol = u.dual_inf_tol; o.constr_viol_tol = u.constr_viol_tol;
@@ -243,49 +222,25 @@ struct WideKkt {
   int64_t B = 0;
   bool assembled = false, factored = false, own_params = false, use_sigx = false, use_sigc = false;
   double delta_w = 0.0, delta_c = 0.0;
-  double *z = nullptr, *mu = nullptr, *params = nullptr, *sigx = nullptr, *sigc = nullptr;
-  size_t cap_z = 0, cap_mu = 0, cap_params = 0, cap_sigx = 0, cap_sigc = 0;   // doubles allocated
-  int* flags = nullptr;   // [2][B]: inertia flags, negative-pivot counts
-  size_t cap_flags = 0;
-  double* ws = nullptr;   // [B][T][multi_ws_stage]: intermediates of one block of right-hand sides (dto_kkt_solve_multi), allocated by
-  size_t cap_ws = 0;      // the first multi-solve
-  double *ref_r = nullptr, *ref_d = nullptr;   // [B][Nz + Nc] each: residual and correction (or K sol) of dto_kkt_solve_refined,
-  size_t cap_ref_r = 0, cap_ref_d = 0;         // allocated by its first call with passes > 0 or a residual norm to report
-  void release() {
-    for (void* q : {(void*)z, (void*)mu, (void*)params, (void*)sigx, (void*)sigc, (void*)flags, (void*)ws, (void*)ref_r, (void*)ref_d})
-      if (q) (void)hipFree(q);
-    z = mu = params = sigx = sigc = ws = ref_r = ref_d = nullptr; flags = nullptr;
-    cap_z = cap_mu = cap_params = cap_sigx = cap_sigc = cap_flags = cap_ws = cap_ref_r = cap_ref_d = 0;
-    B = 0; assembled = factored = false;
-  }
+  DevBuf<double> z, mu, params, sigx, sigc;
+  DevBuf<int> flags;             // [2][B]: inertia flags, negative-pivot counts
+  DevBuf<double> ws;             // [B][T][multi_ws_stage]: intermediates of one block of right-hand sides (dto_kkt_solve_multi), allocated
+                                 // by the first multi-solve
+  DevBuf<double> ref_r, ref_d;   // [B][Nz + Nc] each: residual and correction (or K sol) of dto_kkt_solve_refined, allocated by its
+                                 // first call with passes > 0 or a residual norm to report
 };
-static void release_wide_kkt(Problem* p) {
-  if (p->wide_kkt) { p->wide_kkt->release(); delete p->wide_kkt; p->wide_kkt = nullptr; }
-}
 // ---- both paths: what dto_kkt_border_factor left for dto_kkt_border_solve (dto_border_kernels.hpp).  `valid` is cleared by
 //      dto_kkt_assemble, dto_kkt_factor and everything that takes the factor or the assembled system
 struct KktBorder {
   bool valid = false;
   int nb = 0;
   int64_t B = 0;
-  double *g = nullptr, *y = nullptr;   // [B * nb][Nz + Nc] each: the panel of border rows (the right-hand sides) and Y = K^-1 G'
-  double *part = nullptr;              // [B][chunks][256]: partial products of k_border_gram
-  double *lu = nullptr, *yw = nullptr; // [B][256] LU of S, [B][16] border unknowns of the last solve
-  double *v0 = nullptr;                // [B][Nz + Nc]: K^-1 r of the last solve
-  size_t cap_g = 0, cap_y = 0, cap_part = 0, cap_lu = 0, cap_yw = 0, cap_v0 = 0;   // doubles allocated
-  int* iw = nullptr;                   // [B][16] pivots, then [2][B] flags (negdef, singular)
-  size_t cap_iw = 0;
-  void release() {
-    for (void* q : {(void*)g, (void*)y, (void*)part, (void*)lu, (void*)yw, (void*)v0, (void*)iw})
-      if (q) (void)hipFree(q);
-    g = y = part = lu = yw = v0 = nullptr; iw = nullptr;
-    cap_g = cap_y = cap_part = cap_lu = cap_yw = cap_v0 = cap_iw = 0;
-    valid = false; nb = 0; B = 0;
-  }
+  DevBuf<double> g, y;     // [B * nb][Nz + Nc] each: the panel of border rows (the right-hand sides) and Y = K^-1 G'
+  DevBuf<double> part;     // [B][chunks][256]: partial products of k_border_gram
+  DevBuf<double> lu, yw;   // [B][256] LU of S, [B][16] border unknowns of the last solve
+  DevBuf<double> v0;       // [B][Nz + Nc]: K^-1 r of the last solve
+  DevBuf<int> iw;          // [B][16] pivots, then [2][B] flags (negdef, singular)
 };
-static void release_kkt_border(Problem* p) {
-  if (p->kkt_border) { p->kkt_border->release(); delete p->kkt_border; p->kkt_border = nullptr; }
-}
 static inline void kkt_border_taken(Problem* p) {
   if (p->kkt_border) p->kkt_border->valid = false;
 }
@@ -313,18 +268,8 @@ static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t l
   hipStream_t st = (hipStream_t)b->stream;
   wide_fac_taken(p);
   const size_t need = (size_t)b->B * (size_t)L.T * (size_t)info.fac_stage;
-  if (p->wide_fac_len < need) {
-    if (p->wide_fac) (void)hipFree(p->wide_fac);
-    p->wide_fac = nullptr; p->wide_fac_len = 0;
-    HIP_TRY(hipMalloc((void**)&p->wide_fac, need * sizeof(double)));
-    p->wide_fac_len = need;
-  }
-  if (p->wide_flags_len < (size_t)b->B) {
-    if (p->wide_flags) (void)hipFree(p->wide_flags);
-    p->wide_flags = nullptr; p->wide_flags_len = 0;
-    HIP_TRY(hipMalloc((void**)&p->wide_flags, (size_t)b->B * sizeof(int)));
-    p->wide_flags_len = (size_t)b->B;
-  }
+  HIP_TRY(p->wide_fac.grow(need));
+  HIP_TRY(p->wide_flags.grow((size_t)b->B));
   dto_wide_args a;
   a.T = L.T; a.B = b->B;
   a.kind = p->d_kind; a.zoff = p->d_zoff; a.woff = p->d_woff; a.cdoff = p->d_cdoff;
@@ -354,14 +299,10 @@ static int wide_step(Problem* p, const dto_batch* b, const double* mu, int64_t l
 // ---- wide-stage models, the linear solver alone (dto_kkt_assemble / dto_kkt_factor / dto_kkt_solve): factor once into
 //      p->wide_fac (k_wide_step in its linear-solver mode, terminal block included), then every solve is substitution only
 //      (k_wide_fsub + k_wide_bwd).  Bounds are ignored, as on the lane path.
-static int wide_kkt_grow(double** ptr, size_t* cap, size_t need, const char* what) {
-  if (*cap >= need) return DTO_OK;
-  if (*ptr) (void)hipFree(*ptr);
-  *ptr = nullptr; *cap = 0;
-  hipError_t e = hipMalloc((void**)ptr, need * sizeof(double));
-  if (e != hipSuccess) return hip_fail(e, what);
-  *cap = need;
-  return DTO_OK;
+template <class T>
+static int grow_buf(DevBuf<T>& buf, size_t need, const char* what) {   // DevBuf::grow with the caller's message for a failure
+  const hipError_t e = buf.grow(need);
+  return e == hipSuccess ? DTO_OK : hip_fail(e, what);
 }
 static void wide_kkt_args(Problem* p, dto_wide_args& a) {
   const Layout& L = p->L;
@@ -393,30 +334,19 @@ static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_syste
   const size_t B = (size_t)b->B, Nz = (size_t)L.Nz, Nc = (size_t)std::max<int64_t>(1, L.Nc), Nw = (size_t)L.Nw;
   // the factor records: T per instance, the last one for the terminal block
   const size_t need_fac = B * (size_t)L.T * (size_t)info.fac_stage;
-  if (p->wide_fac_len < need_fac) {
-    if (p->wide_fac) (void)hipFree(p->wide_fac);
-    p->wide_fac = nullptr; p->wide_fac_len = 0;
-    hipError_t e = hipMalloc((void**)&p->wide_fac, need_fac * sizeof(double));
-    if (e != hipSuccess)
-      return hip_fail(e, ("dto_kkt_assemble: hipMalloc of the factor records (" + std::to_string(need_fac * sizeof(double)) + " bytes: " +
-                          std::to_string(b->B) + " instances x " + std::to_string(L.T) + " knots x " +
-                          std::to_string(info.fac_stage * (int64_t)sizeof(double)) + " bytes)").c_str());
-    p->wide_fac_len = need_fac;
-  }
-  if ((rc = wide_kkt_grow(&K.z, &K.cap_z, B * Nz, "dto_kkt_assemble: hipMalloc of the point"))) return rc;
-  if ((rc = wide_kkt_grow(&K.mu, &K.cap_mu, B * Nc, "dto_kkt_assemble: hipMalloc of the multipliers"))) return rc;
+  if (const hipError_t e = p->wide_fac.grow(need_fac); e != hipSuccess)
+    return hip_fail(e, ("dto_kkt_assemble: hipMalloc of the factor records (" + std::to_string(need_fac * sizeof(double)) + " bytes: " +
+                        std::to_string(b->B) + " instances x " + std::to_string(L.T) + " knots x " +
+                        std::to_string(info.fac_stage * (int64_t)sizeof(double)) + " bytes)").c_str());
+  if ((rc = grow_buf(K.z, B * Nz, "dto_kkt_assemble: hipMalloc of the point"))) return rc;
+  if ((rc = grow_buf(K.mu, B * Nc, "dto_kkt_assemble: hipMalloc of the multipliers"))) return rc;
   K.own_params = b->params != nullptr && Nw > 0;
-  if (K.own_params && (rc = wide_kkt_grow(&K.params, &K.cap_params, B * Nw, "dto_kkt_assemble: hipMalloc of the parameters"))) return rc;
+  if (K.own_params && (rc = grow_buf(K.params, B * Nw, "dto_kkt_assemble: hipMalloc of the parameters"))) return rc;
   K.use_sigx = sys->sigma_x != nullptr;
   K.use_sigc = sys->sigma_c != nullptr && L.Nc > 0;
-  if (K.use_sigx && (rc = wide_kkt_grow(&K.sigx, &K.cap_sigx, B * Nz, "dto_kkt_assemble: hipMalloc of sigma_x"))) return rc;
-  if (K.use_sigc && (rc = wide_kkt_grow(&K.sigc, &K.cap_sigc, B * Nc, "dto_kkt_assemble: hipMalloc of sigma_c"))) return rc;
-  if (K.cap_flags < 2 * B) {
-    if (K.flags) (void)hipFree(K.flags);
-    K.flags = nullptr; K.cap_flags = 0;
-    HIP_TRY(hipMalloc((void**)&K.flags, 2 * B * sizeof(int)));
-    K.cap_flags = 2 * B;
-  }
+  if (K.use_sigx && (rc = grow_buf(K.sigx, B * Nz, "dto_kkt_assemble: hipMalloc of sigma_x"))) return rc;
+  if (K.use_sigc && (rc = grow_buf(K.sigc, B * Nc, "dto_kkt_assemble: hipMalloc of sigma_c"))) return rc;
+  HIP_TRY(K.flags.grow(2 * B));
   hipStream_t st = (hipStream_t)b->stream;
   auto copy = [&](double* dst, size_t n, const double* src, int64_t ld) {
     return hipMemcpy2DAsync(dst, n * sizeof(double), src, (size_t)ld * sizeof(double), n * sizeof(double), B, hipMemcpyDeviceToDevice, st);
@@ -439,7 +369,7 @@ static int wide_kkt_factor(Problem* p, int32_t* inertia_ok, int32_t* num_negativ
   kkt_border_taken(p);
   dto_wide_info info;
   p->vt->wide_info(&info);
-  if (p->wide_fac_len < (size_t)K.B * (size_t)p->L.T * (size_t)info.fac_stage) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (p->wide_fac.size() < (size_t)K.B * (size_t)p->L.T * (size_t)info.fac_stage) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
   dto_wide_args a;
   wide_kkt_args(p, a);
   a.sigma_x = K.use_sigx ? K.sigx : nullptr; a.ldsx = p->L.Nz;
@@ -485,16 +415,10 @@ static int wide_kkt_solve_multi(Problem* p, int64_t nrhs, const double* rhs_x, i
   p->vt->wide_info(&info);
   if (info.multi_r < 1) return set_error(DTO_ERR_UNSUPPORTED, "this plugin was built without the panel substitution kernels");
   const size_t need = (size_t)K.B * (size_t)p->L.T * (size_t)info.multi_ws_stage;
-  if (K.cap_ws < need) {
-    if (K.ws) (void)hipFree(K.ws);
-    K.ws = nullptr; K.cap_ws = 0;
-    hipError_t e = hipMalloc((void**)&K.ws, need * sizeof(double));
-    if (e != hipSuccess)
-      return hip_fail(e, ("dto_kkt_solve_multi: hipMalloc of the workspace (" + std::to_string(need * sizeof(double)) + " bytes: " +
-                          std::to_string(K.B) + " instances x " + std::to_string(p->L.T) + " knots x " +
-                          std::to_string(info.multi_ws_stage * (int64_t)sizeof(double)) + " bytes)").c_str());
-    K.cap_ws = need;
-  }
+  if (const hipError_t e = K.ws.grow(need); e != hipSuccess)
+    return hip_fail(e, ("dto_kkt_solve_multi: hipMalloc of the workspace (" + std::to_string(need * sizeof(double)) + " bytes: " +
+                        std::to_string(K.B) + " instances x " + std::to_string(p->L.T) + " knots x " +
+                        std::to_string(info.multi_ws_stage * (int64_t)sizeof(double)) + " bytes)").c_str());
   dto_wide_args a;
   wide_kkt_args(p, a);
   a.rhs_x = rhs_x; a.ldrx = ldrx; a.rhs_c = rhs_c; a.ldrc = ldrc;
@@ -577,8 +501,8 @@ static int wide_kkt_solve_refined(Problem* p, int passes, const double* rhs_x, i
   const size_t need = (size_t)K.B * (size_t)ld;
   const std::string what = "dto_kkt_solve_refined: hipMalloc of a workspace array (" + std::to_string(need * sizeof(double)) + " bytes: " +
                            std::to_string(K.B) + " instances x " + std::to_string(ld) + " doubles)";
-  if ((rc = wide_kkt_grow(&K.ref_r, &K.cap_ref_r, need, what.c_str()))) return rc;
-  if ((rc = wide_kkt_grow(&K.ref_d, &K.cap_ref_d, need, what.c_str()))) return rc;
+  if ((rc = grow_buf(K.ref_r, need, what.c_str()))) return rc;
+  if ((rc = grow_buf(K.ref_d, need, what.c_str()))) return rc;
   double *r_x = K.ref_r, *r_c = K.ref_r + Nz, *d_x = K.ref_d, *d_c = K.ref_d + Nz;
   const dim3 grid((unsigned)(K.B * AXPY_BLOCKS_PER_ROW)), block(256);
   auto residual = [&]() -> int {   // ref_r = rhs - K sol (K sol passes through ref_d)
@@ -733,12 +657,10 @@ struct WideInst {
 
 struct WideState {
   int64_t B = 0, len = 0, n_bnd = 0;  // len: doubles per instance of z / lam / zl / zu / tmp (max(Nz, Nc): the shift swaps them)
-  int64_t ldb = 0, lo_len = 0;        // lo / hi: [Nz] shared (ldb = 0) or [B][Nz] per instance (ldb = Nz); lo_len doubles allocated
+  int64_t ldb = 0;                    // lo / hi: [Nz] shared (ldb = 0) or [B][Nz] per instance (ldb = Nz)
   bool barrier = false, begun = false, any_running = false, timed_out = false;
-  double *z = nullptr, *lam = nullptr, *dz = nullptr, *dlam = nullptr, *lo = nullptr, *hi = nullptr, *dw = nullptr,
-         *stats = nullptr, *merit = nullptr, *alpha = nullptr, *gam = nullptr, *zl = nullptr, *zu = nullptr, *mu = nullptr,
-         *alphad = nullptr, *params = nullptr, *tmp = nullptr;
-  int *flags = nullptr, *active = nullptr;
+  DevBuf<double> z, lam, dz, dlam, lo, hi, dw, stats, merit, alpha, gam, zl, zu, mu, alphad, params, tmp;
+  DevBuf<int> flags, active;
   bool own_params = false;            // the batch's per-instance parameters, copied at the begin ([B][Nw])
   dto_options user{};
   dto_solver_opts opt{};
@@ -747,21 +669,19 @@ struct WideState {
   std::vector<double> h_gam, h_dw, h_stats, h_merit, h_alpha, h_mu, h_alphad;
   std::chrono::steady_clock::time_point t_start;
   int dump_launch = 0, dump_merit = 0;
-
-  void release() {
-    for (void* q : {(void*)z, (void*)lam, (void*)dz, (void*)dlam, (void*)lo, (void*)hi, (void*)dw, (void*)stats, (void*)merit,
-                    (void*)alpha, (void*)gam, (void*)zl, (void*)zu, (void*)mu, (void*)alphad, (void*)params, (void*)tmp,
-                    (void*)flags, (void*)active})
-      if (q) (void)hipFree(q);
-    z = lam = dz = dlam = lo = hi = dw = stats = merit = alpha = gam = zl = zu = mu = alphad = params = tmp = nullptr;
-    flags = active = nullptr;
-    B = len = ldb = lo_len = 0; begun = any_running = timed_out = own_params = false;
-    I.clear();
-  }
 };
 
 static void release_wide(Problem* p) {
-  if (p->wide) { p->wide->release(); delete p->wide; p->wide = nullptr; }
+  delete p->wide;
+  p->wide = nullptr;
+}
+
+void Problem::free_solver() {
+  release_wide(this);
+  delete wide_kkt; wide_kkt = nullptr;
+  delete kkt_border; kkt_border = nullptr;
+  delete solver; solver = nullptr;
+  delete im; im = nullptr;
 }
 
 // device buffers for a batch of B (kept when the batch size is the same)
@@ -773,17 +693,22 @@ static int wide_alloc(Problem* p, int64_t B, bool barrier) {
   WideState& W = *p->wide;
   const int64_t len = std::max<int64_t>(L.Nz, std::max<int64_t>(1, L.Nc));
   const size_t n = (size_t)B * (size_t)len;
-  auto fail = [&](hipError_t e, const char* what) { release_wide(p); return hip_fail(e, what); };
-#define WALLOC(ptr, count) do { hipError_t e_ = hipMalloc((void**)&(ptr), (size_t)(count) * sizeof(*(ptr))); if (e_ != hipSuccess) return fail(e_, "hipMalloc " #ptr); } while (0)
-  WALLOC(W.z, n); WALLOC(W.lam, n); WALLOC(W.tmp, n);
-  WALLOC(W.dz, (size_t)B * L.Nz); WALLOC(W.dlam, (size_t)B * std::max<int64_t>(1, L.Nc));
-  WALLOC(W.lo, L.Nz); WALLOC(W.hi, L.Nz);   // (grown to [B][Nz] by wide_begin when per-instance bounds are set)
-  WALLOC(W.dw, B); WALLOC(W.stats, (size_t)B * DTO_WIDE_NSTAT); WALLOC(W.merit, (size_t)B * 2 * DTO_WIDE_TRIALS);
-  WALLOC(W.alpha, B); WALLOC(W.gam, B); WALLOC(W.flags, B); WALLOC(W.active, B);
-  if (barrier) { WALLOC(W.zl, n); WALLOC(W.zu, n); WALLOC(W.mu, B); WALLOC(W.alphad, B); }
-  if (L.Nw > 0) WALLOC(W.params, (size_t)B * L.Nw);
-#undef WALLOC
-  W.B = B; W.len = len; W.lo_len = L.Nz;
+  int rc;
+  if ((rc = grow_buf(W.z, n, "hipMalloc W.z")) || (rc = grow_buf(W.lam, n, "hipMalloc W.lam")) || (rc = grow_buf(W.tmp, n, "hipMalloc W.tmp")) ||
+      (rc = grow_buf(W.dz, (size_t)B * L.Nz, "hipMalloc W.dz")) || (rc = grow_buf(W.dlam, (size_t)B * std::max<int64_t>(1, L.Nc), "hipMalloc W.dlam")) ||
+      // (lo / hi are grown to [B][Nz] by wide_begin when per-instance bounds are set)
+      (rc = grow_buf(W.lo, L.Nz, "hipMalloc W.lo")) || (rc = grow_buf(W.hi, L.Nz, "hipMalloc W.hi")) ||
+      (rc = grow_buf(W.dw, B, "hipMalloc W.dw")) || (rc = grow_buf(W.stats, (size_t)B * DTO_WIDE_NSTAT, "hipMalloc W.stats")) ||
+      (rc = grow_buf(W.merit, (size_t)B * 2 * DTO_WIDE_TRIALS, "hipMalloc W.merit")) ||
+      (rc = grow_buf(W.alpha, B, "hipMalloc W.alpha")) || (rc = grow_buf(W.gam, B, "hipMalloc W.gam")) ||
+      (rc = grow_buf(W.flags, B, "hipMalloc W.flags")) || (rc = grow_buf(W.active, B, "hipMalloc W.active")) ||
+      (barrier && ((rc = grow_buf(W.zl, n, "hipMalloc W.zl")) || (rc = grow_buf(W.zu, n, "hipMalloc W.zu")) ||
+                   (rc = grow_buf(W.mu, B, "hipMalloc W.mu")) || (rc = grow_buf(W.alphad, B, "hipMalloc W.alphad")))) ||
+      (L.Nw > 0 && (rc = grow_buf(W.params, (size_t)B * L.Nw, "hipMalloc W.params")))) {
+    release_wide(p);
+    return rc;
+  }
+  W.B = B; W.len = len;
   return DTO_OK;
 }
 
@@ -847,12 +772,7 @@ static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bo
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc;
   hipStream_t st = (hipStream_t)b->stream;
   const size_t need_fac = (size_t)B * (size_t)L.T * (size_t)info.fac_stage;
-  if (p->wide_fac_len < need_fac) {
-    if (p->wide_fac) (void)hipFree(p->wide_fac);
-    p->wide_fac = nullptr; p->wide_fac_len = 0;
-    HIP_TRY(hipMalloc((void**)&p->wide_fac, need_fac * sizeof(double)));
-    p->wide_fac_len = need_fac;
-  }
+  HIP_TRY(p->wide_fac.grow(need_fac));
   if ((rc = wide_alloc(p, B, barrier))) return rc;
   WideState& W = *p->wide;
   W.n_bnd = n_bnd; W.barrier = barrier;
@@ -863,13 +783,11 @@ static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bo
   // the bounds this batch runs with: the handle's per-instance ones (copied, so that a later dto_solver_set_bounds leaves the
   // begun state alone) or the problem's shared ones
   W.ldb = p->d_bnd ? Nz : 0;
-  const int64_t lo_len = p->d_bnd ? B * Nz : Nz;
-  if (W.lo_len != lo_len) {
-    (void)hipFree(W.lo); (void)hipFree(W.hi);
-    W.lo = W.hi = nullptr; W.lo_len = 0;
-    HIP_TRY(hipMalloc((void**)&W.lo, (size_t)lo_len * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&W.hi, (size_t)lo_len * sizeof(double)));
-    W.lo_len = lo_len;
+  const size_t lo_len = (size_t)(p->d_bnd ? B * Nz : Nz);
+  if (W.lo.size() != lo_len || W.hi.size() != lo_len) {
+    W.lo.reset(); W.hi.reset();
+    HIP_TRY(W.lo.alloc(lo_len));
+    HIP_TRY(W.hi.alloc(lo_len));
   }
   if (p->d_bnd) {
     HIP_TRY(hipMemcpyAsync(W.lo, p->d_bnd, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -1244,7 +1162,7 @@ static int wide_shift(Problem* p, int knots, hipStream_t st) {
   const int nx = L.nx[0], nu = L.nu[0];
   if (L.Ndyn != (int64_t)(T - 1) * nx || L.Nc != L.Ndyn || L.Nz != (int64_t)(T - 1) * (nx + nu) + nx)
     return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_shift: unexpected variable / dynamics row count");
-  auto shift = [&](double*& buf, int64_t n, int stride, int last_len, const int* keep) -> int {
+  auto shift = [&](DevBuf<double>& buf, int64_t n, int stride, int last_len, const int* keep) -> int {
     const int64_t total = W.B * n;
     if (total == 0) return DTO_OK;
     const int64_t blocks = (total + 255) / 256;
@@ -1262,13 +1180,6 @@ static int wide_shift(Problem* p, int knots, hipStream_t st) {
     if ((rc = shift(W.zl, L.Nz, nx + nu, nx, nullptr))) return rc;
     if ((rc = shift(W.zu, L.Nz, nx + nu, nx, nullptr))) return rc;
   }
-  return DTO_OK;
-}
-
-template <class T>
-static int dev_alloc(T** p, size_t count) {
-  HIP_TRY(hipMalloc((void**)p, std::max<size_t>(1, count) * sizeof(T)));
-  HIP_TRY(hipMemset(*p, 0, std::max<size_t>(1, count) * sizeof(T)));
   return DTO_OK;
 }
 
@@ -1377,9 +1288,8 @@ static int ensure_state(Problem* p, int64_t B, bool allow_general = false) {
     set_partitions_now(S, S.P0);
     return DTO_OK;
   }
-  const int keep_forced = S.forced_P;
-  S.release();
-  S.forced_P = keep_forced;
+  S.release();   // (keeps forced_P)
+  ReleaseOnError<SolverState> guard{&S};
   S.P = S.P0 = P_new;
   S.n_simd = n_simd;
   S.P_cap = P_cap_new;
@@ -1442,35 +1352,35 @@ static int ensure_state(Problem* p, int64_t B, bool allow_general = false) {
       t = e;
     }
     S.n_runs = (int)runs.size();
-    HIP_TRY(hipMalloc((void**)&S.d_runs, runs.size() * sizeof(dto_stage_run)));
+    HIP_TRY(S.d_runs.alloc(runs.size()));
     HIP_TRY(hipMemcpy(S.d_runs, runs.data(), runs.size() * sizeof(dto_stage_run), hipMemcpyHostToDevice));
   }
   const size_t lanes = (size_t)S.G * 64;
-  HIP_TRY(hipMalloc((void**)&S.d_ioff, (L.T + 1) * sizeof(int)));
+  HIP_TRY(S.d_ioff.alloc(L.T + 1));
   HIP_TRY(hipMemcpy(S.d_ioff, S.ioff.data(), (L.T + 1) * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&S.d_recoff, (L.T + 1) * sizeof(int64_t)));
+  HIP_TRY(S.d_recoff.alloc(L.T + 1));
   HIP_TRY(hipMemcpy(S.d_recoff, S.recoff.data(), (L.T + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&S.d_facoff, (L.T + 1) * sizeof(int64_t)));
+  HIP_TRY(S.d_facoff.alloc(L.T + 1));
   HIP_TRY(hipMemcpy(S.d_facoff, S.facoff.data(), (L.T + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&S.d_lo, std::max<size_t>(1, L.Nz) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&S.d_hi, std::max<size_t>(1, L.Nz) * sizeof(double)));
+  HIP_TRY(S.d_lo.alloc(L.Nz));
+  HIP_TRY(S.d_hi.alloc(L.Nz));
   HIP_TRY(hipMemcpy(S.d_lo, L.var_lo.data(), L.Nz * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(S.d_hi, L.var_hi.data(), L.Nz * sizeof(double), hipMemcpyHostToDevice));
-  if ((rc = dev_alloc(&S.z, lanes * L.Nz))) return rc;
-  if ((rc = dev_alloc(&S.lam, lanes * L.Nc))) return rc;
+  HIP_TRY(S.z.alloc_zeroed(lanes * L.Nz));
+  HIP_TRY(S.lam.alloc_zeroed(lanes * L.Nc));
   // bound multipliers exist only where a variable has a finite bound that is not a fixing pair (the acrobot has none: 80 KB
   // per instance, 31 GB at the default bench batch); the kernels test the pointer
   if (S.n_bnd > S.Ni) {
-    if ((rc = dev_alloc(&S.zl, lanes * L.Nz))) return rc;
-    if ((rc = dev_alloc(&S.zu, lanes * L.Nz))) return rc;
+    HIP_TRY(S.zl.alloc_zeroed(lanes * L.Nz));
+    HIP_TRY(S.zu.alloc_zeroed(lanes * L.Nz));
   }
-  if ((rc = dev_alloc(&S.s, lanes * S.Ni))) return rc;
-  if ((rc = dev_alloc(&S.zs, lanes * S.Ni))) return rc;
-  if ((rc = dev_alloc(&S.dz, lanes * L.Nz))) return rc;
-  if ((rc = dev_alloc(&S.dlam, lanes * L.Nc))) return rc;
-  if ((rc = dev_alloc(&S.ds, lanes * S.Ni))) return rc;
-  if ((rc = dev_alloc(&S.rec, lanes * S.rec_total))) return rc;
-  if ((rc = dev_alloc(&S.fac, lanes * S.fac_total))) return rc;
+  HIP_TRY(S.s.alloc_zeroed(lanes * S.Ni));
+  HIP_TRY(S.zs.alloc_zeroed(lanes * S.Ni));
+  HIP_TRY(S.dz.alloc_zeroed(lanes * L.Nz));
+  HIP_TRY(S.dlam.alloc_zeroed(lanes * L.Nc));
+  HIP_TRY(S.ds.alloc_zeroed(lanes * S.Ni));
+  HIP_TRY(S.rec.alloc_zeroed(lanes * S.rec_total));
+  HIP_TRY(S.fac.alloc_zeroed(lanes * S.fac_total));
   // residual / merit partials: one row set per block of DTO_SB stages (k_stage_eval, k_linesearch), not per stage
   // (small batches: fewer stages per wavefront, down to one -- a batch of one then evaluates its T stages on T wavefronts
   //  instead of walking 8 at a time on T / 8: 37 -> ~8 us for the line search of one acrobot T=101 instance; DTO_STAGE_BLOCK sets it)
@@ -1480,13 +1390,13 @@ static int ensure_state(Problem* p, int64_t B, bool allow_general = false) {
     if (const char* e = getenv("DTO_STAGE_BLOCK")) S.sb = std::max(1, std::min((int)DTO_SB, atoi(e)));
   }
   const size_t nblk = ((size_t)L.T + S.sb - 1) / S.sb;
-  if ((rc = dev_alloc(&S.part, lanes * nblk * S.info.npart))) return rc;
-  if ((rc = dev_alloc(&S.lspart, lanes * nblk * 2 * S.info.ls_trials))) return rc;
-  if ((rc = dev_alloc(&S.scal, lanes * S.info.nscal))) return rc;
-  if ((rc = dev_alloc(&S.tile_fwd_tag, (size_t)S.G + 8))) return rc;
-  if ((rc = dev_alloc(&S.tile_bwd_tag, (size_t)S.G + 8))) return rc;
-  if ((rc = dev_alloc(&S.fwd_started, 16))) return rc;
-  if ((rc = dev_alloc(&S.filt, lanes * 2 * S.info.filter_cap))) return rc;
+  HIP_TRY(S.part.alloc_zeroed(lanes * nblk * S.info.npart));
+  HIP_TRY(S.lspart.alloc_zeroed(lanes * nblk * 2 * S.info.ls_trials));
+  HIP_TRY(S.scal.alloc_zeroed(lanes * S.info.nscal));
+  HIP_TRY(S.tile_fwd_tag.alloc_zeroed((size_t)S.G + 8));
+  HIP_TRY(S.tile_bwd_tag.alloc_zeroed((size_t)S.G + 8));
+  HIP_TRY(S.fwd_started.alloc_zeroed(16));
+  HIP_TRY(S.filt.alloc_zeroed(lanes * 2 * S.info.filter_cap));
   {
     // chunk boundaries of every P in [1, P_cap] (or of the one fixed P), back to back: block q holds q + 1 entries
     const int q_lo = (S.P_cap > S.P) ? 1 : S.P, q_hi = S.P_cap;
@@ -1497,20 +1407,21 @@ static int ensure_state(Problem* p, int64_t B, bool allow_general = false) {
       for (int c = 0; c <= q; ++c) all.push_back((int)(((int64_t)c * L.T) / q));
     }
     S.cstart.assign(all.begin() + off_cur, all.begin() + off_cur + S.P + 1);
-    HIP_TRY(hipMalloc((void**)&S.d_cstart_all, all.size() * sizeof(int)));
+    HIP_TRY(S.d_cstart_all.alloc(all.size()));
     HIP_TRY(hipMemcpy(S.d_cstart_all, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
     S.d_cstart = S.d_cstart_all + off_cur;
   }
-  if ((rc = dev_alloc(&S.csum, lanes * (size_t)S.P_cap * S.info.chunk_sum_size))) return rc;
-  if ((rc = dev_alloc(&S.sfac, lanes * (size_t)S.P_cap * S.info.sep_fac_size))) return rc;
-  if ((rc = dev_alloc(&S.xsep, lanes * (size_t)S.P_cap * S.info.nx))) return rc;
-  if ((rc = dev_alloc(&S.cacc, lanes * (size_t)S.P_cap * 4))) return rc;
-  if ((rc = dev_alloc(&S.cpart, lanes * (size_t)S.P_cap * 16))) return rc;
-  if ((rc = dev_alloc(&S.csync, (size_t)S.G * 4))) return rc;
+  HIP_TRY(S.csum.alloc_zeroed(lanes * (size_t)S.P_cap * S.info.chunk_sum_size));
+  HIP_TRY(S.sfac.alloc_zeroed(lanes * (size_t)S.P_cap * S.info.sep_fac_size));
+  HIP_TRY(S.xsep.alloc_zeroed(lanes * (size_t)S.P_cap * S.info.nx));
+  HIP_TRY(S.cacc.alloc_zeroed(lanes * (size_t)S.P_cap * 4));
+  HIP_TRY(S.cpart.alloc_zeroed(lanes * (size_t)S.P_cap * 16));
+  HIP_TRY(S.csync.alloc_zeroed((size_t)S.G * 4));
   S.h_scal.assign(lanes * S.info.nscal, 0.0);
   // the zero fills and table copies above ran on the null stream; the kernels run on the caller's stream, which may be a
   // non-blocking one: order them once here (allocation time only)
   HIP_TRY(hipDeviceSynchronize());
+  guard.s = nullptr;
   return DTO_OK;
 }
 
@@ -1581,10 +1492,8 @@ static bool fused_update_available(Problem* p) {
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
   const size_t reserve = reserve_gb >= 0.0 ? (size_t)(reserve_gb * 1073741824.0) : total_b / 8;
   if (free_b < need + reserve) return false;
-  if (hipMalloc((void**)&S.z_alt, std::max<size_t>(8, lanes * p->L.Nz * sizeof(double))) != hipSuccess) { S.z_alt = nullptr; return false; }
-  if (hipMalloc((void**)&S.lam_alt, std::max<size_t>(8, lanes * p->L.Nc * sizeof(double))) != hipSuccess) {
-    (void)hipFree(S.z_alt); S.z_alt = nullptr; S.lam_alt = nullptr; return false;
-  }
+  if (S.z_alt.alloc(lanes * p->L.Nz) != hipSuccess) return false;
+  if (S.lam_alt.alloc(lanes * p->L.Nc) != hipSuccess) { S.z_alt.reset(); return false; }
   S.fuse_state = 1;
   return true;
 }
@@ -1612,11 +1521,10 @@ static int kkt_launch(Problem* p, int op, const dto_kkt_args& a, hipStream_t st)
 static int ensure_refine_buffers(Problem* p, dto_kkt_args& a) {
   SolverState& S = *p->solver;
   const size_t lanes = (size_t)S.G * 64;
-  int rc;
-  if (!S.refq && (rc = dev_alloc(&S.refq, lanes * (size_t)p->L.T * (size_t)S.info.nx))) return rc;
-  if (!S.refvz && (rc = dev_alloc(&S.refvz, lanes * (size_t)p->L.Nz))) return rc;
-  if (!S.refvl && (rc = dev_alloc(&S.refvl, lanes * (size_t)std::max<int64_t>(1, p->L.Nc)))) return rc;
-  if (!S.rec_bak && (rc = dev_alloc(&S.rec_bak, lanes * (size_t)S.rec_total))) return rc;
+  if (!S.refq) HIP_TRY(S.refq.alloc_zeroed(lanes * (size_t)p->L.T * (size_t)S.info.nx));
+  if (!S.refvz) HIP_TRY(S.refvz.alloc_zeroed(lanes * (size_t)p->L.Nz));
+  if (!S.refvl) HIP_TRY(S.refvl.alloc_zeroed(lanes * (size_t)std::max<int64_t>(1, p->L.Nc)));
+  if (!S.rec_bak) HIP_TRY(S.rec_bak.alloc_zeroed(lanes * (size_t)S.rec_total));
   a.refq = S.refq; a.refvz = S.refvz; a.refvl = S.refvl;
   return DTO_OK;
 }
@@ -1647,10 +1555,7 @@ static int set_batch_params(Problem* p, const dto_batch* b, hipStream_t st) {
   S.use_wtile = false;
   if (!b->params || p->L.Nw == 0) return DTO_OK;
   if (b->ldp < p->L.Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
-  if (!S.wtile) {
-    int rc = dev_alloc(&S.wtile, (size_t)S.G * 64 * (size_t)p->L.Nw);
-    if (rc) return rc;
-  }
+  if (!S.wtile) HIP_TRY(S.wtile.alloc_zeroed((size_t)S.G * 64 * (size_t)p->L.Nw));
   S.use_wtile = true;
   dto_kkt_args a;
   fill_kkt_args(p, a);
@@ -1671,7 +1576,7 @@ static inline double hscal(const SolverState& S, int64_t inst, int slot) {
 
 // identity slot <-> instance map (every entry point that loads a fresh batch)
 static void reset_slot_map(SolverState& S) {
-  if (S.d_inst_of_slot) { (void)hipFree(S.d_inst_of_slot); S.d_inst_of_slot = nullptr; }
+  S.d_inst_of_slot.reset();
   S.inst_of_slot.clear(); S.slot_of_inst.clear();
   S.G_active = S.G;
 }
@@ -1725,20 +1630,15 @@ static int repack(Problem* p, hipStream_t st, int* n_running_out) {
   if (n_running_out) *n_running_out = nrun;
   const int g_new = std::max(1, (nrun + 63) / 64);
   if (g_new >= S.G_active) return DTO_OK;            // nothing to gain
-  if (!S.d_src_slot) HIP_TRY(hipMalloc((void**)&S.d_src_slot, lanes * sizeof(int)));
-  if (!S.d_inst_of_slot) HIP_TRY(hipMalloc((void**)&S.d_inst_of_slot, lanes * sizeof(int)));
+  if (!S.d_src_slot) HIP_TRY(S.d_src_slot.alloc(lanes));
+  if (!S.d_inst_of_slot) HIP_TRY(S.d_inst_of_slot.alloc(lanes));
   HIP_TRY(hipMemcpyAsync(S.d_src_slot, src.data(), lanes * sizeof(int), hipMemcpyHostToDevice, st));
   // the staging buffer must hold the widest vector that moves: iterates, multipliers, slacks, filter (2 * filter_cap
   // rows), scalars, per-instance parameters (the filter rows were missing from the maximum)
   int64_t widest = std::max<int64_t>(std::max<int64_t>(L.Nz, L.Nc), std::max<int64_t>(S.info.nscal, L.Nw));
   widest = std::max<int64_t>(widest, std::max<int64_t>(S.Ni, 2 * (int64_t)S.info.filter_cap));
   const size_t need = (size_t)lanes * (size_t)widest;
-  if (S.repack_tmp_len < need) {
-    if (S.repack_tmp) (void)hipFree(S.repack_tmp);
-    S.repack_tmp = nullptr; S.repack_tmp_len = 0;
-    HIP_TRY(hipMalloc((void**)&S.repack_tmp, need * sizeof(double)));
-    S.repack_tmp_len = need;
-  }
+  HIP_TRY(S.repack_tmp.grow(need));
   auto move = [&](double* buf, int64_t n) -> int {
     if (!buf || n <= 0) return DTO_OK;
     const unsigned nrb = (unsigned)((n + 3) / 4);
@@ -1829,6 +1729,7 @@ static int ensure_im_state(Problem* p, int64_t B) {
   const Layout& L = p->L;
   if (S.B == B && S.A) return DTO_OK;
   S.release();
+  ReleaseOnError<ImState> guard{&S};
   p->vt->im_info(&S.info);
   if (!S.info.supported) return set_error(DTO_ERR_UNSUPPORTED, "the instance-major engine needs an exact-Hessian model without GeneralConstraint");
   S.B = B;
@@ -1851,35 +1752,36 @@ static int ensure_im_state(Problem* p, int64_t B) {
   }
   S.nwin_e = (T + S.info.own_eval - 1) / S.info.own_eval;
   S.nwin_l = (T + S.info.own_ls - 1) / S.info.own_ls;
-  auto table = [&](int** d, const std::vector<int>& h) -> int {
-    HIP_TRY(hipMalloc((void**)d, h.size() * sizeof(int)));
-    HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+  auto table = [&](DevBuf<int>& d, const std::vector<int>& h) -> int {
+    HIP_TRY(d.alloc(h.size()));
+    HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
     return DTO_OK;
   };
-  if ((rc = table(&S.d_aoff, S.aoff)) || (rc = table(&S.d_doff, S.doff)) || (rc = table(&S.d_coff, S.coff)) ||
-      (rc = table(&S.d_boff, S.boff)) || (rc = table(&S.d_ioff, S.ioff)))
+  if ((rc = table(S.d_aoff, S.aoff)) || (rc = table(S.d_doff, S.doff)) || (rc = table(S.d_coff, S.coff)) ||
+      (rc = table(S.d_boff, S.boff)) || (rc = table(S.d_ioff, S.ioff)))
     return rc;
-  HIP_TRY(hipMalloc((void**)&S.d_lo, std::max<size_t>(1, L.Nz) * sizeof(double)));
-  HIP_TRY(hipMalloc((void**)&S.d_hi, std::max<size_t>(1, L.Nz) * sizeof(double)));
+  HIP_TRY(S.d_lo.alloc(L.Nz));
+  HIP_TRY(S.d_hi.alloc(L.Nz));
   HIP_TRY(hipMemcpy(S.d_lo, L.var_lo.data(), L.Nz * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(S.d_hi, L.var_hi.data(), L.Nz * sizeof(double), hipMemcpyHostToDevice));
   const size_t nb = (size_t)B;
   // + one record of slack at the end: the sweeps form (never read) the address of the record after the last stage
-  if ((rc = dev_alloc(&S.A, nb * (size_t)S.a_total + 16))) return rc;
-  if ((rc = dev_alloc(&S.R, nb * (size_t)S.a_total + 16))) return rc;
-  if ((rc = dev_alloc(&S.D, nb * (size_t)S.d_total + 16))) return rc;
-  if ((rc = dev_alloc(&S.C, nb * (size_t)S.c_total + 16))) return rc;
-  if (S.n_bnd > 0 && (rc = dev_alloc(&S.Bd, nb * (size_t)S.b_total + 16))) return rc;
-  if ((rc = dev_alloc(&S.part, nb * (size_t)S.nwin_e * S.info.npart))) return rc;
-  if ((rc = dev_alloc(&S.lspart, nb * (size_t)S.nwin_l * 2 * S.info.ls_trials))) return rc;
-  if ((rc = dev_alloc(&S.scal, nb * (size_t)S.info.nscal))) return rc;
-  if ((rc = dev_alloc(&S.filt, nb * 2 * (size_t)S.info.filter_cap))) return rc;
-  if ((rc = dev_alloc(&S.phase, nb))) return rc;
-  if ((rc = dev_alloc(&S.lists, 3 * nb))) return rc;
-  if ((rc = dev_alloc(&S.ctr, (size_t)8))) return rc;
+  HIP_TRY(S.A.alloc_zeroed(nb * (size_t)S.a_total + 16));
+  HIP_TRY(S.R.alloc_zeroed(nb * (size_t)S.a_total + 16));
+  HIP_TRY(S.D.alloc_zeroed(nb * (size_t)S.d_total + 16));
+  HIP_TRY(S.C.alloc_zeroed(nb * (size_t)S.c_total + 16));
+  if (S.n_bnd > 0) HIP_TRY(S.Bd.alloc_zeroed(nb * (size_t)S.b_total + 16));
+  HIP_TRY(S.part.alloc_zeroed(nb * (size_t)S.nwin_e * S.info.npart));
+  HIP_TRY(S.lspart.alloc_zeroed(nb * (size_t)S.nwin_l * 2 * S.info.ls_trials));
+  HIP_TRY(S.scal.alloc_zeroed(nb * (size_t)S.info.nscal));
+  HIP_TRY(S.filt.alloc_zeroed(nb * 2 * (size_t)S.info.filter_cap));
+  HIP_TRY(S.phase.alloc_zeroed(nb));
+  HIP_TRY(S.lists.alloc_zeroed(3 * nb));
+  HIP_TRY(S.ctr.alloc_zeroed((size_t)8));
   HIP_TRY(hipHostMalloc((void**)&S.h_ctr, 8 * sizeof(int)));
   S.h_scal.assign(nb * S.info.nscal, 0.0);
   HIP_TRY(hipDeviceSynchronize());
+  guard.s = nullptr;
   return DTO_OK;
 }
 
@@ -1917,10 +1819,7 @@ static int im_set_params(Problem* p, const dto_batch* b, hipStream_t st) {
   S.use_w = false;
   if (!b->params || p->L.Nw == 0) return DTO_OK;
   if (b->ldp < p->L.Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
-  if (!S.wbuf) {
-    int rc = dev_alloc(&S.wbuf, (size_t)S.B * (size_t)p->L.Nw);
-    if (rc) return rc;
-  }
+  if (!S.wbuf) HIP_TRY(S.wbuf.alloc_zeroed((size_t)S.B * (size_t)p->L.Nw));
   HIP_TRY(hipMemcpy2DAsync(S.wbuf, p->L.Nw * sizeof(double), b->params, b->ldp * sizeof(double), p->L.Nw * sizeof(double),
                            (size_t)S.B, hipMemcpyDeviceToDevice, st));
   S.use_w = true;
@@ -2236,15 +2135,15 @@ static int ensure_border_csc(Problem* p) {
     ck[(size_t)e] = (int)k;
     crow[(size_t)e] = (int)(L.jac_rows[(size_t)k] - 1);
   }
-  HIP_TRY(hipMalloc((void**)&p->d_csc_ptr, ptr.size() * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&p->d_csc_k, std::max<size_t>(1, ck.size()) * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&p->d_csc_row, std::max<size_t>(1, crow.size()) * sizeof(int)));
+  HIP_TRY(p->d_csc_ptr.alloc(ptr.size()));
+  HIP_TRY(p->d_csc_k.alloc(ck.size()));
+  HIP_TRY(p->d_csc_row.alloc(crow.size()));
   HIP_TRY(hipMemcpy(p->d_csc_ptr, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_csc_k, ck.data(), ck.size() * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(p->d_csc_row, crow.data(), crow.size() * sizeof(int), hipMemcpyHostToDevice));
   std::vector<int> fx((size_t)L.Nz);
   for (int64_t k = 0; k < L.Nz; ++k) fx[(size_t)k] = (L.var_lo[(size_t)k] == L.var_hi[(size_t)k]) ? 1 : 0;
-  HIP_TRY(hipMalloc((void**)&p->d_var_fixed, std::max<size_t>(1, fx.size()) * sizeof(int)));
+  HIP_TRY(p->d_var_fixed.alloc(fx.size()));
   HIP_TRY(hipMemcpy(p->d_var_fixed, fx.data(), fx.size() * sizeof(int), hipMemcpyHostToDevice));
   return DTO_OK;
 }
@@ -2261,12 +2160,7 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
   // workspace: J | c | g | sig | rx | rhsx | rhsc | zero_c | v0x | v0c | Grow[ng] | Yx[ng] | Yc[ng] | hdx | hdm | rho | flags
   const size_t nBz = (size_t)B * Nz, nBc = (size_t)B * Nc;
   const size_t ws_need = (size_t)B * nnzJ + nBc + nBz * 6 + nBc * 4 + (size_t)ng * (2 * nBz + nBc) + (size_t)B * ng + 2 * (size_t)B + 8;
-  if (p->border_ws_len < ws_need) {
-    if (p->border_ws) (void)hipFree(p->border_ws);
-    p->border_ws = nullptr; p->border_ws_len = 0;
-    HIP_TRY(hipMalloc((void**)&p->border_ws, ws_need * sizeof(double)));
-    p->border_ws_len = ws_need;
-  }
+  HIP_TRY(p->border_ws.grow(ws_need));
   double* w = p->border_ws;
   auto take = [&](size_t n) { double* q = w; w += n; return q; };
   double *dJ = take((size_t)B * nnzJ), *dC = take(nBc), *dG = take(nBz), *dSig = take(nBz), *dRxv = take(nBz), *dRhsx = take(nBz),
@@ -2329,16 +2223,7 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
   int rc;
   // one workspace kept in the problem (grown when a larger batch comes): J | c | grad | sigma | rhs_x | rhs_c | sol_x | sol_c
-  auto cleanup = [&]() {};
-#define BTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return hip_fail(e_, #expr); } } while (0)
-#define BRC(expr) do { rc = (expr); if (rc) { cleanup(); return rc; } } while (0)
-  const size_t ws_need = (size_t)B * ((size_t)nnzJ + 4 * (size_t)Nz + 3 * (size_t)Nc);
-  if (p->border_ws_len < ws_need) {
-    if (p->border_ws) (void)hipFree(p->border_ws);
-    p->border_ws = nullptr; p->border_ws_len = 0;
-    BTRY(hipMalloc((void**)&p->border_ws, ws_need * sizeof(double)));
-    p->border_ws_len = ws_need;
-  }
+  HIP_TRY(p->border_ws.grow((size_t)B * ((size_t)nnzJ + 4 * (size_t)Nz + 3 * (size_t)Nc)));
   double* dJ = p->border_ws;
   double* dC = dJ + (size_t)B * nnzJ;
   double* dG = dC + (size_t)B * Nc;
@@ -2348,15 +2233,15 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
   double* dSx = dRc + (size_t)B * Nc;
   double* dSc = dSx + (size_t)B * Nz;
   // ---- derivatives at (x, mu): callbacks on the device, the small vectors come to the host
-  BRC(dto_eval_jac_g_batch(h, b, dJ, nnzJ));
-  BRC(dto_eval_g_batch(h, b, dC, Nc));
-  BRC(dto_eval_grad_f_batch(h, b, dG, Nz));
+  if ((rc = dto_eval_jac_g_batch(h, b, dJ, nnzJ))) return rc;
+  if ((rc = dto_eval_g_batch(h, b, dC, Nc))) return rc;
+  if ((rc = dto_eval_grad_f_batch(h, b, dG, Nz))) return rc;
   std::vector<double> J((size_t)B * nnzJ), c((size_t)B * Nc), g((size_t)B * Nz), m((size_t)B * Nc);
-  BTRY(hipMemcpyAsync(J.data(), dJ, J.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  BTRY(hipMemcpyAsync(c.data(), dC, c.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  BTRY(hipMemcpyAsync(g.data(), dG, g.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  BTRY(hipMemcpy2DAsync(m.data(), Nc * sizeof(double), mu, ldmu * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
-  BTRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(J.data(), dJ, J.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(c.data(), dC, c.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(g.data(), dG, g.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpy2DAsync(m.data(), Nc * sizeof(double), mu, ldmu * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   // r_x = grad f + J' mu (all rows, general ones included); the general rows of J as dense vectors
   std::vector<double> rx((size_t)B * Nz), Grow((size_t)ng * B * Nz, 0.0);
   for (int64_t i = 0; i < B; ++i) {
@@ -2374,13 +2259,13 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
   for (int64_t i = 0; i < B; ++i)
     for (int64_t k = 0; k < Nz; ++k)   // pin_fixed: a variable with lo == hi keeps its value (a huge diagonal entry: its step is ~1e-16 r)
       sig[(size_t)i * Nz + k] = (pin_fixed && L.var_lo[(size_t)k] == L.var_hi[(size_t)k]) ? 1e16 : dw[i];
-  BTRY(hipMemcpyAsync(dSig, sig.data(), sig.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dSig, sig.data(), sig.size() * sizeof(double), hipMemcpyHostToDevice, st));
   dto_kkt_system sys;
   sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
   sys.delta_w = 0.0; sys.delta_c = delta_c;
-  BRC(dto_kkt_assemble(h, b, &sys));
+  if ((rc = dto_kkt_assemble(h, b, &sys))) return rc;
   std::vector<int32_t> iok((size_t)B, 1);
-  BRC(dto_kkt_factor(h, iok.data(), nullptr, (void*)st));
+  if ((rc = dto_kkt_factor(h, iok.data(), nullptr, (void*)st))) return rc;
   std::vector<double> rhsx((size_t)B * Nz), rhsc((size_t)B * Nc, 0.0), solx((size_t)B * Nz), solc((size_t)B * Nc);
   std::vector<double> Yx((size_t)ng * B * Nz), Yc((size_t)ng * B * Nc);
   auto solve = [&](const double* hx, const double* hc, double* ox, double* oc) -> int {
@@ -2396,10 +2281,10 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
   for (size_t k = 0; k < rhsx.size(); ++k) rhsx[k] = -rx[k];
   for (int64_t i = 0; i < B; ++i)
     for (int64_t k = 0; k < Ns; ++k) rhsc[(size_t)i * Nc + k] = -c[(size_t)i * Nc + k];
-  BRC(solve(rhsx.data(), rhsc.data(), solx.data(), solc.data()));
+  if ((rc = solve(rhsx.data(), rhsc.data(), solx.data(), solc.data()))) return rc;
   std::vector<double> zero_c((size_t)B * Nc, 0.0);
   for (int64_t j = 0; j < ng; ++j)
-    BRC(solve(&Grow[(size_t)j * B * Nz], zero_c.data(), &Yx[(size_t)j * B * Nz], &Yc[(size_t)j * B * Nc]));
+    if ((rc = solve(&Grow[(size_t)j * B * Nz], zero_c.data(), &Yx[(size_t)j * B * Nz], &Yc[(size_t)j * B * Nc]))) return rc;
   // ---- border: S drho = r_g - G v0_x per instance (dense n_g x n_g, Gaussian elimination with partial pivoting); S must be
   //      negative definite for the inertia of the bordered matrix to be (Nz, Nc)
   std::vector<double> hdx((size_t)B * Nz), hdm((size_t)B * Nc);
@@ -2456,15 +2341,12 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
     }
     for (int64_t q = 0; q < ng; ++q) hdm[(size_t)i * Nc + Ns + q] = x[(size_t)q];
   }
-  BTRY(hipMemcpy2DAsync(dx, lddx * sizeof(double), hdx.data(), Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
-  BTRY(hipMemcpy2DAsync(dmu, lddmu * sizeof(double), hdm.data(), Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
-  BTRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy2DAsync(dx, lddx * sizeof(double), hdx.data(), Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpy2DAsync(dmu, lddmu * sizeof(double), hdm.data(), Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (stats) {
     stats->grad.swap(g); stats->c.swap(c); stats->rx.swap(rx); stats->dz.swap(hdx); stats->dmu.swap(hdm);
   }
-  cleanup();
-#undef BTRY
-#undef BRC
   return DTO_OK;
 }
 
@@ -2513,33 +2395,31 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   default_opts(o, u);
   hipStream_t st = (hipStream_t)b->stream;
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
-  double *z = nullptr, *lam = nullptr, *dz = nullptr, *dlam = nullptr, *zt = nullptr, *df = nullptr, *dc = nullptr, *dal = nullptr, *dth = nullptr;
-  double *dgd = nullptr, *dgs = nullptr, *dst = nullptr, *dnu = nullptr;   // [B][ng]: s / nu, mu / nu, trial slacks, multipliers of the general rows
-  double* d5 = nullptr;                                                     // [B][5] statistics of the point and the step
-  auto cleanup = [&]() { for (double* q : {z, lam, dz, dlam, zt, df, dc, dal, dth, dgd, dgs, dst, dnu, d5}) if (q) (void)hipFree(q); };
-#define GTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return hip_fail(e_, #expr); } } while (0)
-#define GRC(expr) do { rc = (expr); if (rc) { cleanup(); return rc; } } while (0)
-  GTRY(hipMalloc((void**)&z, (size_t)B * Nz * sizeof(double)));
-  GTRY(hipMalloc((void**)&lam, (size_t)B * Nc * sizeof(double)));
-  GTRY(hipMalloc((void**)&dz, (size_t)B * Nz * sizeof(double)));
-  GTRY(hipMalloc((void**)&dlam, (size_t)B * Nc * sizeof(double)));
-  GTRY(hipMalloc((void**)&zt, (size_t)B * Nz * sizeof(double)));
-  GTRY(hipMalloc((void**)&df, (size_t)B * sizeof(double)));
-  GTRY(hipMalloc((void**)&dc, (size_t)B * Nc * sizeof(double)));
-  GTRY(hipMalloc((void**)&dal, (size_t)B * sizeof(double)));
-  GTRY(hipMalloc((void**)&dth, (size_t)B * sizeof(double)));
+  // the temporaries of this call: released on every return
+  DevBuf<double> z, lam, dz, dlam, zt, df, dc, dal, dth;
+  DevBuf<double> dgd, dgs, dst, dnu;   // [B][ng]: s / nu, mu / nu, trial slacks, multipliers of the general rows
+  DevBuf<double> d5;                   // [B][5] statistics of the point and the step
+  HIP_TRY(z.alloc((size_t)B * Nz));
+  HIP_TRY(lam.alloc((size_t)B * Nc));
+  HIP_TRY(dz.alloc((size_t)B * Nz));
+  HIP_TRY(dlam.alloc((size_t)B * Nc));
+  HIP_TRY(zt.alloc((size_t)B * Nz));
+  HIP_TRY(df.alloc((size_t)B));
+  HIP_TRY(dc.alloc((size_t)B * Nc));
+  HIP_TRY(dal.alloc((size_t)B));
+  HIP_TRY(dth.alloc((size_t)B));
   if (ni > 0) {
-    for (double** q : {&dgd, &dgs, &dst, &dnu}) GTRY(hipMalloc((void**)q, (size_t)B * ng * sizeof(double)));
+    for (DevBuf<double>* q : {&dgd, &dgs, &dst, &dnu}) HIP_TRY(q->alloc((size_t)B * ng));
   }
   // the guess, with the fixed variables put on their values
   std::vector<double> hz((size_t)B * Nz);
-  GTRY(hipMemcpy2DAsync(hz.data(), Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
-  GTRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy2DAsync(hz.data(), Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   for (int64_t i = 0; i < B; ++i)
     for (int64_t k = 0; k < Nz; ++k)
       if (L.var_lo[k] == L.var_hi[k]) hz[(size_t)i * Nz + k] = L.var_lo[k];
-  GTRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  GTRY(hipMemsetAsync(lam, 0, (size_t)B * Nc * sizeof(double), st));
+  HIP_TRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(lam, 0, (size_t)B * Nc * sizeof(double), st));
   struct Inst {
     int status = 0, iter = 0, ls_fail = 0, filter_n = 0;
     double dlast = 0.0, theta_max = -1.0, theta_min = -1.0;
@@ -2562,16 +2442,16 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   };
   if (ni > 0) {
     // slacks from the constraint values at the guess, pushed inside (s >= 1e-2), multipliers 1 (Ipopt's bound_mult_init_val), mu_init
-    GRC(dto_eval_g_batch(h, &bz, dc, Nc));
+    if ((rc = dto_eval_g_batch(h, &bz, dc, Nc))) return rc;
     std::vector<double> hg((size_t)B * ng);
-    GTRY(hipMemcpy2DAsync(hg.data(), ng * sizeof(double), dc + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
-    GTRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy2DAsync(hg.data(), ng * sizeof(double), dc + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < B; ++i) {
       I[(size_t)i].mu = o.mu_init;
       for (int64_t q = 0; q < ng; ++q)
         if (ineq[(size_t)q]) { hs[(size_t)(i * ng + q)] = std::max(-hg[(size_t)(i * ng + q)], 1e-2); hnu[(size_t)(i * ng + q)] = 1.0; }
     }
-    GRC(put_nu());
+    if ((rc = put_nu())) return rc;
   }
   const double kappa_sigma = 1e10;
   std::vector<char> mu_moved((size_t)B, 0);
@@ -2585,8 +2465,8 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
           hgd[e] = ineq[(size_t)q] ? hs[e] / hnu[e] : 0.0;
           hgs[e] = ineq[(size_t)q] ? I[(size_t)i].mu / hnu[e] : 0.0;
         }
-      GTRY(hipMemcpyAsync(dgd, hgd.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
-      GTRY(hipMemcpyAsync(dgs, hgs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(dgd, hgd.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(dgs, hgs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
     }
     // ---- step at the current point: delta_w ladder per instance (Algorithm IC), all instances share the sweeps
     for (int64_t i = 0; i < B; ++i) {
@@ -2596,7 +2476,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     BorderStats bs;
     for (int attempt = 0;; ++attempt) {
       bs.reuse_point = attempt > 0;
-      GRC(bordered_step(p, &bz, lam, Nc, dwv.data(), o.delta_c, dz, Nz, dlam, Nc, okv.data(), &bs, true, ni > 0 ? dgd : nullptr, ni > 0 ? dgs : nullptr));
+      if ((rc = bordered_step(p, &bz, lam, Nc, dwv.data(), o.delta_c, dz, Nz, dlam, Nc, okv.data(), &bs, true, ni > 0 ? dgd : nullptr, ni > 0 ? dgs : nullptr))) return rc;
       bool again = false;
       for (int64_t i = 0; i < B; ++i) {
         Inst& s = I[(size_t)i];
@@ -2612,27 +2492,27 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     std::vector<double> hst5, hdnu;
     if (dev_stats) {
       // device border: five numbers per instance (and the steps of the general rows' multipliers) instead of five vectors
-      if (!d5) GTRY(hipMalloc((void**)&d5, (size_t)B * 5 * sizeof(double)));
-      if (ni > 0) GTRY(hipMemcpyAsync(dst, hs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));   // slack shift of theta
+      if (!d5) HIP_TRY(d5.alloc((size_t)B * 5));
+      if (ni > 0) HIP_TRY(hipMemcpyAsync(dst, hs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));   // slack shift of theta
       hipLaunchKernelGGL(k_border_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, Nc, bs.d_c, bs.d_rx, bs.d_grad, (const double*)dz, (const double*)lam,
                          (const int*)p->d_var_fixed, (const double*)(ni > 0 ? dst : nullptr), Ns, ng, d5);
       hst5.resize((size_t)B * 5);
-      GTRY(hipMemcpyAsync(hst5.data(), d5, hst5.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(hst5.data(), d5, hst5.size() * sizeof(double), hipMemcpyDeviceToHost, st));
       if (ng > 0) {
         hdnu.resize((size_t)B * ng);
-        GTRY(hipMemcpy2DAsync(hdnu.data(), ng * sizeof(double), dlam + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpy2DAsync(hdnu.data(), ng * sizeof(double), dlam + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
       }
     }
     auto dnu_of = [&](int64_t i, int64_t q) { return dev_stats ? hdnu[(size_t)(i * ng + q)] : bs.dmu[(size_t)i * Nc + Ns + q]; };
     // ---- convergence test (Ipopt's scaled error, reference Options), at the point the step was computed at
-    GRC(dto_eval_f_batch(h, &bz, df));
-    GTRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = dto_eval_f_batch(h, &bz, df))) return rc;
+    HIP_TRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
     std::vector<double> hm;
     if (!dev_stats) {
       hm.resize((size_t)B * Nc);
-      GTRY(hipMemcpyAsync(hm.data(), lam, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(hm.data(), lam, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    GTRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     hphi0 = hf;   // objective at the current point: the line search's phi_0
     bool any = false;
     std::vector<double> th0((size_t)B), gphid((size_t)B);
@@ -2733,19 +2613,19 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
             const size_t e = (size_t)(i * ng + q);
             hst[e] = ineq[(size_t)q] ? hs[e] + hal[(size_t)i] * hds[e] : 0.0;
           }
-        GTRY(hipMemcpyAsync(dst, hst.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dst, hst.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
       }
-      GTRY(hipMemcpyAsync(zt, z, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToDevice, st));
-      GTRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(zt, z, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, zt, (const double*)dz, (const double*)dal, Nz, Nz, Nz);
       dto_batch bt = bz;
       bt.x = zt;
-      GRC(dto_eval_f_batch(h, &bt, df));
-      GRC(dto_eval_g_batch(h, &bt, dc, Nc));
+      if ((rc = dto_eval_f_batch(h, &bt, df))) return rc;
+      if ((rc = dto_eval_g_batch(h, &bt, dc, Nc))) return rc;
       hipLaunchKernelGGL(k_rows_abs_sum, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, dth, (const double*)(ni > 0 ? dst : nullptr), Ns, ng);
-      GTRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-      GTRY(hipMemcpyAsync(hth.data(), dth, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-      GTRY(hipStreamSynchronize(st));
+      HIP_TRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(hth.data(), dth, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
       k_done = k + 1;
       for (int64_t i = 0; i < B; ++i) {
         Inst& s = I[(size_t)i];
@@ -2800,7 +2680,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       s.iter++;
       hal[(size_t)i] = chosen;
     }
-    GTRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)dal, Nz, Nz, Nz);
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, lam, (const double*)dlam, (const double*)dal, Nc, Nc, Nc);
     if (ni > 0) {
@@ -2820,20 +2700,17 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
           hnu[e] = std::max(std::min(hnu[e], kappa_sigma * mu_i / hs[e]), mu_i / (kappa_sigma * hs[e]));
         }
       }
-      GRC(put_nu());
+      if ((rc = put_nu())) return rc;
     }
     if (u.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > u.max_cpu_time) { timed_out = true; break; }
   }
-  GTRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), z, Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
-  if (mu_out) GTRY(hipMemcpy2DAsync(mu_out, ldmuo * sizeof(double), lam, Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
-  GTRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), z, Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
+  if (mu_out) HIP_TRY(hipMemcpy2DAsync(mu_out, ldmuo * sizeof(double), lam, Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
   for (int64_t i = 0; i < B; ++i) {
     if (status) status[i] = (I[(size_t)i].status == 0 && timed_out) ? DTO_STATUS_CPU_TIME : I[(size_t)i].status;
     if (iterations) iterations[i] = I[(size_t)i].iter;
   }
-  cleanup();
-#undef GTRY
-#undef GRC
   return DTO_OK;
 }
 
@@ -3008,12 +2885,7 @@ int dto_solver_begin(dto_problem* h, const dto_options* opt, const dto_batch* b)
     if (p->L.Ngen != 0)
       return set_error(DTO_ERR_UNSUPPORTED, "hessian_approximation = limited-memory: lane-per-instance solver path without GeneralConstraint rows");
     const size_t need = (size_t)S.G * (size_t)dto::QnRows{p->L.Nz}.total() * 64;
-    if (S.qn_len < need) {
-      if (S.qn) (void)hipFree(S.qn);
-      S.qn = nullptr; S.qn_len = 0;
-      HIP_TRY(hipMalloc((void**)&S.qn, need * sizeof(double)));
-      S.qn_len = need;
-    }
+    HIP_TRY(S.qn.grow(need));
     HIP_TRY(hipMemsetAsync(S.qn, 0, need * sizeof(double), st));
     // small batches: the QN_M2 column solves of an iteration side by side, as the instances of a second state (12 x the memory of
     // the batch; DTO_QN_COLS=0: one after the other as for large batches)
@@ -3032,11 +2904,11 @@ int dto_solver_begin(dto_problem* h, const dto_options* opt, const dto_batch* b)
       C.use_sigx = C.use_sigc = C.assembled = false;
       C.use_wtile = false;
       if (S.use_wtile) {
-        if (!C.wtile && (rc = dto::dev_alloc(&C.wtile, (size_t)C.G * 64 * (size_t)p->L.Nw))) return rc;
+        if (!C.wtile) HIP_TRY(C.wtile.alloc_zeroed((size_t)C.G * 64 * (size_t)p->L.Nw));
         C.use_wtile = true;
       }
     } else if (S.cols) {
-      S.cols->release(); delete S.cols; S.cols = nullptr;
+      delete S.cols; S.cols = nullptr;
     }
   }
   dto_kkt_args a;
@@ -3360,10 +3232,10 @@ int dto_solver_shift(dto_problem* h, int knots, void* stream) {
   if (L.Ndyn != (int64_t)(T - 1) * nx) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_shift: unexpected dynamics row count");
   hipStream_t st = (hipStream_t)stream;
   const int64_t B = S.B, Nz = L.Nz, Nc = L.Nc;
-  double *a = nullptr, *b = nullptr;
+  dto::DevBuf<double> a, b;
   const size_t n = (size_t)B * (size_t)std::max<int64_t>(Nz, Nc);
-  HIP_TRY(hipMalloc((void**)&a, n * sizeof(double)));
-  if (hipMalloc((void**)&b, n * sizeof(double)) != hipSuccess) { (void)hipFree(a); return set_error(DTO_ERR_DEVICE, "hipMalloc"); }
+  HIP_TRY(a.alloc(n));
+  if (b.alloc(n) != hipSuccess) return set_error(DTO_ERR_DEVICE, "hipMalloc");
   dto_kkt_args ka;
   dto::fill_kkt_args(p, ka);
   int rc = DTO_OK;
@@ -3383,8 +3255,7 @@ int dto_solver_shift(dto_problem* h, int knots, void* stream) {
   if (!rc && Nc > 0) rc = shift(1, Nc, T - 1, nx, 0);
   // bound multipliers follow their variables
   if (!rc && S.zl) { rc = shift(5, Nz, T - 1, nx + nu, nx); if (!rc) rc = shift(6, Nz, T - 1, nx + nu, nx); }
-  hipError_t e = hipStreamSynchronize(st);
-  (void)hipFree(a); (void)hipFree(b);
+  const hipError_t e = hipStreamSynchronize(st);   // a and b are dropped at the return: the launches above must have finished
   if (rc) return rc;
   if (e != hipSuccess) return dto::hip_fail(e, "dto_solver_shift");
   return DTO_OK;
@@ -3394,15 +3265,14 @@ int dto_solver_shift_keep_rows(dto_problem* h, const int32_t* keep, int64_t n) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p) return set_error(DTO_ERR_INVALID, "null argument");
   if (!keep) {
-    if (p->d_shift_keep) (void)hipFree(p->d_shift_keep);
-    p->d_shift_keep = nullptr;
+    p->d_shift_keep.reset();
     return DTO_OK;
   }
   if (n != p->L.Nc) return set_error(DTO_ERR_INVALID, "dto_solver_shift_keep_rows: one flag per constraint row");
   if (n == 0) return DTO_OK;
   int rc = p->ensure_device();
   if (rc) return rc;
-  if (!p->d_shift_keep) HIP_TRY(hipMalloc((void**)&p->d_shift_keep, (size_t)n * sizeof(int)));
+  if (!p->d_shift_keep) HIP_TRY(p->d_shift_keep.alloc((size_t)n));
   HIP_TRY(hipMemcpy(p->d_shift_keep, keep, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
   return DTO_OK;
 }
@@ -3415,8 +3285,7 @@ int dto_solver_set_bounds(dto_problem* h, int64_t B, const double* lower, int64_
     return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_set_bounds: per-instance variable bounds are a tile-path (17..64-state) feature; on "
                                           "the lane-per-instance path per-instance values enter through parameters in stage rows");
   if (!lower && !upper) {
-    if (p->d_bnd) (void)hipFree(p->d_bnd);
-    p->d_bnd = nullptr; p->bnd_B = 0;
+    p->d_bnd.reset(); p->bnd_B = 0;
     return DTO_OK;
   }
   const dto::Layout& L = p->L;
@@ -3430,16 +3299,12 @@ int dto_solver_set_bounds(dto_problem* h, int64_t B, const double* lower, int64_
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the new bounds go to a buffer of their own: a violation leaves the previous setting in force
-  double *buf = nullptr, *shared = nullptr;
-  unsigned long long* res = nullptr;
-  auto cleanup = [&]() {
-    if (buf) (void)hipFree(buf);
-    if (shared) (void)hipFree(shared);
-    if (res) (void)hipFree(res);
-  };
-  hipError_t e = hipMalloc((void**)&buf, (size_t)2 * total * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&shared, (size_t)2 * Nz * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&res, 2 * sizeof(unsigned long long));
+  // (the temporaries are dropped at the return: every path that launched something has waited for the stream by then)
+  dto::DevBuf<double> buf, shared;
+  dto::DevBuf<unsigned long long> res;
+  hipError_t e = buf.alloc((size_t)2 * total);
+  if (e == hipSuccess) e = shared.alloc((size_t)2 * Nz);
+  if (e == hipSuccess) e = res.alloc(2);
   const unsigned long long init[2] = {0ull, ~0ull};
   unsigned long long out[2] = {0ull, 0ull};
   if (e == hipSuccess) e = hipMemcpy2DAsync(buf, Nz * sizeof(double), lower, ldl * sizeof(double), Nz * sizeof(double), B, hipMemcpyDeviceToDevice, st);
@@ -3459,9 +3324,7 @@ int dto_solver_set_bounds(dto_problem* h, int64_t B, const double* lower, int64_
     e = hipMemcpy(&lh[0], buf + out[1], sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(&lh[1], buf + total + out[1], sizeof(double), hipMemcpyDeviceToHost);
   }
-  if (e != hipSuccess) { cleanup(); return dto::hip_fail(e, "dto_solver_set_bounds"); }
-  (void)hipFree(shared); shared = nullptr;
-  (void)hipFree(res); res = nullptr;
+  if (e != hipSuccess) return dto::hip_fail(e, "dto_solver_set_bounds");
   if (out[0] > 0) {
     const int64_t b = (int64_t)(out[1] / (unsigned long long)Nz), j = (int64_t)(out[1] % (unsigned long long)Nz);
     const double l = lh[0], u = lh[1], sl = L.var_lo[(size_t)j], su = L.var_hi[(size_t)j];
@@ -3476,11 +3339,9 @@ int dto_solver_set_bounds(dto_problem* h, int64_t B, const double* lower, int64_
     char msg[384];
     snprintf(msg, sizeof(msg), "dto_solver_set_bounds: instance %lld, variable %lld: %s (lower %.17g, upper %.17g; the problem's %.17g, %.17g); "
              "%llu entries break the problem's bound pattern", (long long)b, (long long)j, why, l, u, sl, su, out[0]);
-    cleanup();
     return set_error(DTO_ERR_INVALID, msg);
   }
-  if (p->d_bnd) (void)hipFree(p->d_bnd);
-  p->d_bnd = buf; p->bnd_B = B;
+  p->d_bnd = std::move(buf); p->bnd_B = B;
   return DTO_OK;
 }
 
@@ -3806,8 +3667,8 @@ int dto_kkt_assemble(dto_problem* h, const dto_batch* b, const dto_kkt_system* s
   S.opt.newton_only = 1;
   S.opt.fixed_delta_w = sys->delta_w;
   const size_t lanes = (size_t)S.G * 64;
-  if (sys->sigma_x && !S.sigx && (rc = dto::dev_alloc(&S.sigx, lanes * (size_t)p->L.Nz))) return rc;
-  if (sys->sigma_c && !S.sigc && (rc = dto::dev_alloc(&S.sigc, lanes * (size_t)std::max<int64_t>(1, p->L.Nc)))) return rc;
+  if (sys->sigma_x && !S.sigx) HIP_TRY(S.sigx.alloc_zeroed(lanes * (size_t)p->L.Nz));
+  if (sys->sigma_c && !S.sigc) HIP_TRY(S.sigc.alloc_zeroed(lanes * (size_t)std::max<int64_t>(1, p->L.Nc)));
   S.use_sigx = sys->sigma_x != nullptr;
   S.use_sigc = sys->sigma_c != nullptr;
   dto_kkt_args a;
@@ -3963,25 +3824,20 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
   const int64_t n_c = g_c ? Nc : 0;   // without g_c the constraint part of every border row is zero: the product skips it
   const int chunks = (int)((Nz + n_c + chunk - 1) / chunk);
   const size_t rows = (size_t)B * (size_t)nb;
-  auto grow = [&](double** ptr, size_t* cap, size_t need, const char* name, const std::string& shape) {
-    return dto::wide_kkt_grow(ptr, cap, need, ("dto_kkt_border_factor: hipMalloc of " + std::string(name) + " (" + std::to_string(need * sizeof(double)) +
+  auto grow = [&](dto::DevBuf<double>& buf, size_t need, const char* name, const std::string& shape) {
+    return dto::grow_buf(buf, need, ("dto_kkt_border_factor: hipMalloc of " + std::string(name) + " (" + std::to_string(need * sizeof(double)) +
                                                " bytes: " + shape + ")").c_str());
   };
   const std::string panel = std::to_string(B) + " instances x " + std::to_string(nb) + " rows x " + std::to_string(N) + " doubles";
-  if ((rc = grow(&W.g, &W.cap_g, rows * (size_t)N, "the border panel", panel))) return rc;
-  if ((rc = grow(&W.y, &W.cap_y, rows * (size_t)N, "K^-1 G'", panel))) return rc;
-  if ((rc = grow(&W.part, &W.cap_part, (size_t)B * (size_t)chunks * 256, "the partial products",
+  if ((rc = grow(W.g, rows * (size_t)N, "the border panel", panel))) return rc;
+  if ((rc = grow(W.y, rows * (size_t)N, "K^-1 G'", panel))) return rc;
+  if ((rc = grow(W.part, (size_t)B * (size_t)chunks * 256, "the partial products",
                  std::to_string(B) + " instances x " + std::to_string(chunks) + " chunks x 256 doubles"))) return rc;
-  if ((rc = grow(&W.lu, &W.cap_lu, (size_t)B * 256, "the LU of the Schur complement", std::to_string(B) + " instances x 256 doubles"))) return rc;
-  if ((rc = grow(&W.yw, &W.cap_yw, (size_t)B * 16, "the border unknowns", std::to_string(B) + " instances x 16 doubles"))) return rc;
-  if ((rc = grow(&W.v0, &W.cap_v0, (size_t)B * (size_t)N, "K^-1 r", std::to_string(B) + " instances x " + std::to_string(N) + " doubles"))) return rc;
-  if (W.cap_iw < (size_t)B * 18) {
-    if (W.iw) (void)hipFree(W.iw);
-    W.iw = nullptr; W.cap_iw = 0;
-    hipError_t e = hipMalloc((void**)&W.iw, (size_t)B * 18 * sizeof(int));
-    if (e != hipSuccess) return dto::hip_fail(e, ("dto_kkt_border_factor: hipMalloc of pivots and flags (" + std::to_string((size_t)B * 18 * sizeof(int)) + " bytes)").c_str());
-    W.cap_iw = (size_t)B * 18;
-  }
+  if ((rc = grow(W.lu, (size_t)B * 256, "the LU of the Schur complement", std::to_string(B) + " instances x 256 doubles"))) return rc;
+  if ((rc = grow(W.yw, (size_t)B * 16, "the border unknowns", std::to_string(B) + " instances x 16 doubles"))) return rc;
+  if ((rc = grow(W.v0, (size_t)B * (size_t)N, "K^-1 r", std::to_string(B) + " instances x " + std::to_string(N) + " doubles"))) return rc;
+  if (const hipError_t e = W.iw.grow((size_t)B * 18); e != hipSuccess)
+    return dto::hip_fail(e, ("dto_kkt_border_factor: hipMalloc of pivots and flags (" + std::to_string((size_t)B * 18 * sizeof(int)) + " bytes)").c_str());
   hipStream_t st = (hipStream_t)stream;
   // the panel of right-hand sides: row b * nb + j = [g_x row; g_c row or zeros]
   const size_t pitch = (size_t)N * sizeof(double);
@@ -4053,24 +3909,16 @@ int dto_solve(dto_problem* h, const dto_options* opt, const double* x0, double* 
   int rc = p->ensure_device();
   if (rc) return rc;
   const dto::Layout& L = p->L;
-  double* d_x = nullptr;
-  double* d_mu = nullptr;
-  auto run = [&]() -> int {
-    HIP_TRY(hipMalloc((void**)&d_x, std::max<size_t>(1, L.Nz) * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&d_mu, std::max<size_t>(1, L.Nc) * sizeof(double)));
-    HIP_TRY(hipMemcpy(d_x, x0, L.Nz * sizeof(double), hipMemcpyHostToDevice));
-    dto_batch b;
-    b.B = 1; b.x = d_x; b.ldx = L.Nz; b.params = nullptr; b.ldp = 0; b.stream = (void*)p->stream;
-    const int r = dto_solve_batch(h, opt, &b, d_x, L.Nz, d_mu, L.Nc, status, iterations);
-    if (r != DTO_OK) return r;
-    HIP_TRY(hipMemcpy(x, d_x, L.Nz * sizeof(double), hipMemcpyDeviceToHost));
-    if (mu) HIP_TRY(hipMemcpy(mu, d_mu, L.Nc * sizeof(double), hipMemcpyDeviceToHost));
-    return DTO_OK;
-  };
-  rc = run();  // the buffers are released on every path
-  if (d_x) (void)hipFree(d_x);
-  if (d_mu) (void)hipFree(d_mu);
-  return rc;
+  dto::DevBuf<double> d_x, d_mu;   // released on every path
+  HIP_TRY(d_x.alloc(L.Nz));
+  HIP_TRY(d_mu.alloc(L.Nc));
+  HIP_TRY(hipMemcpy(d_x, x0, L.Nz * sizeof(double), hipMemcpyHostToDevice));
+  dto_batch b;
+  b.B = 1; b.x = d_x; b.ldx = L.Nz; b.params = nullptr; b.ldp = 0; b.stream = (void*)p->stream;
+  if ((rc = dto_solve_batch(h, opt, &b, d_x, L.Nz, d_mu, L.Nc, status, iterations))) return rc;
+  HIP_TRY(hipMemcpy(x, d_x, L.Nz * sizeof(double), hipMemcpyDeviceToHost));
+  if (mu) HIP_TRY(hipMemcpy(mu, d_mu, L.Nc * sizeof(double), hipMemcpyDeviceToHost));
+  return DTO_OK;
 }
 
 }  // extern "C"
