@@ -21,6 +21,7 @@
 #include "dto_wide_kernels.hpp"
 #include "dto_border_kernels.hpp"
 #include "dto_problem.hpp"
+#include "dto_host_globalization.hpp"
 
 #define HIP_TRY(expr)                                       \
   do {                                                      \
@@ -183,32 +184,6 @@ static void default_opts(dto_solver_opts& o, const dto_options& u) {
 }
 
 struct BorderStats;
-// Ipopt's scaled optimality error (Waechter & Biegler 2006, (5)-(6)) and monotone barrier update (7), shared by the two host-driven
-// barrier loops of this file (tile path: wide_outer; bordered path: general_solve_batch) -- the in-kernel iteration has the
-// same expressions in conv_body (the two loops had drifted apart -- the bordered one left the slack multipliers out of
-// s_d and reset theta_max with the filter).  On a decrease of mu the FILTER is reset, theta_max / theta_min stay (Ipopt, step A-3).
-struct ErrScale { double sd, sc; };
-static inline ErrScale ipopt_scaling(const dto_solver_opts& o, double sum_mult, int64_t n_mult, double sum_bound_mult, int64_t n_bound) {
-  ErrScale e;
-  e.sd = std::max(o.s_max, (sum_mult + sum_bound_mult) / (double)std::max<int64_t>(1, n_mult + n_bound)) / o.s_max;
-  e.sc = n_bound > 0 ? std::max(o.s_max, sum_bound_mult / (double)n_bound) / o.s_max : 1.0;
-  return e;
-}
-static inline double barrier_mu_floor(const dto_solver_opts& o) {
-  return std::max(o.mu_target, std::min(o.tol, o.compl_inf_tol) / (o.kappa_eps + 1.0));
-}
-// mu -> the first value of the monotone sequence at which the barrier problem is NOT yet solved to kappa_eps mu (or the floor);
-// err_rest: max(dual infeasibility / s_d, constraint violation); compl_at(mu): complementarity error against mu
-template <class ComplAt>
-static inline double monotone_mu(const dto_solver_opts& o, double mu, double err_rest, double sc, ComplAt&& compl_at) {
-  const double mu_floor = barrier_mu_floor(o);
-  for (;;) {
-    const double emu = std::max(err_rest, compl_at(mu) / sc);
-    if (!(emu <= o.kappa_eps * mu) || mu <= mu_floor) break;
-    mu = std::max(mu_floor, std::min(o.kappa_mu * mu, std::pow(mu, o.theta_mu)));
-  }
-  return mu;
-}
 
 static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                          double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed = false,
@@ -645,13 +620,12 @@ static __global__ void k_wide_check_bounds(const double* lo, const double* hi, c
 }
 
 // ---- the tile-path solver state (dto_solver_begin / iterate / run / end / begin_warm / shift on a wide plugin) ----------------
-// Host record of one instance: filter ring, inertia-ladder memory, barrier parameter, and the measures of the current iterate
-struct WideInst {
-  int status = 0, iter = 0, ls_fail = 0, full_streak = 0, attempt = 0, acc_count = 0;
-  double f_last = 1e300, mu = 0.0;
-  double dw = 0.0, dlast = 0.0, theta_max = -1.0, theta_min = -1.0, alpha = 0.0, gam = 1.0, gamma_acc = 1.0;
-  std::vector<double> filt;  // (theta, phi) pairs, ring of DTO_FILTER_CAP
-  int filter_n = 0;
+// Host record of one instance: the shared globalisation record (filter ring, ladder memory, barrier parameter) plus what only this
+// path has -- acceptable-level counter, Gauss-Newton fallback of the ladder, and the measures of the current iterate
+struct WideInst : GlobInst {
+  int full_streak = 0, attempt = 0, acc_count = 0;
+  double f_last = 1e300;
+  double dw = 0.0, alpha = 0.0, gam = 1.0, gamma_acc = 1.0;
   double f = 0.0, thinf = 0.0, dinf = 0.0;   // at the last convergence test (dto_solver_stats)
 };
 
@@ -847,240 +821,226 @@ static int wide_begin(Problem* p, const dto_options* opt, const dto_batch* b, bo
   return DTO_OK;
 }
 
+// debug (tools/wide_debug.py), DTO_WIDE_DUMP=<prefix>, for the first DTO_WIDE_DUMP_MAX (default 1) of each: <prefix>_L<k>_<what>.bin --
+// everything factorisation launch k produced (factor records, step, statistics, flags) plus its inputs -- or, merit = true,
+// <prefix>_M<k>_merit.bin: the line-search table of iteration k
+static void wide_debug_dump(Problem* p, bool merit) {
+  const char* prefix = getenv("DTO_WIDE_DUMP");
+  if (!prefix) return;
+  WideState& W = *p->wide;
+  int& count = merit ? W.dump_merit : W.dump_launch;
+  if (count >= (getenv("DTO_WIDE_DUMP_MAX") ? atoi(getenv("DTO_WIDE_DUMP_MAX")) : 1)) return;
+  char fn[1024];
+  if (merit) {
+    snprintf(fn, sizeof(fn), "%s_M%d_merit.bin", prefix, count);
+    if (FILE* f = fopen(fn, "wb")) { fwrite(W.h_merit.data(), sizeof(double), W.h_merit.size(), f); fclose(f); }
+  } else {
+    auto wr = [&](const char* what, const void* dptr, size_t bytes) {
+      std::vector<char> hb(bytes);
+      if (hipMemcpy(hb.data(), dptr, bytes, hipMemcpyDeviceToHost) != hipSuccess) return;
+      snprintf(fn, sizeof(fn), "%s_L%d_%s.bin", prefix, count, what);
+      if (FILE* f = fopen(fn, "wb")) { fwrite(hb.data(), 1, bytes, f); fclose(f); }
+    };
+    const Layout& L = p->L;
+    const size_t B = (size_t)W.B, nz = B * L.Nz * sizeof(double), nc = B * std::max<int64_t>(1, L.Nc) * sizeof(double);
+    dto_wide_info info;
+    p->vt->wide_info(&info);
+    wr("fac", p->wide_fac, B * (size_t)L.T * (size_t)info.fac_stage * sizeof(double));
+    wr("dz", W.dz, nz);
+    wr("dlam", W.dlam, nc);
+    wr("z", W.z, nz);
+    wr("lam", W.lam, nc);
+    wr("stats", W.stats, B * DTO_WIDE_NSTAT * sizeof(double));
+    wr("flags", W.flags, B * sizeof(int));
+    wr("dw", W.dw, B * sizeof(double));
+    wr("active", W.active, B * sizeof(int));
+  }
+  ++count;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Solver for wide-stage models (configs[4]): the same filter line-search SQP iteration as the register path, driven from
 // the host -- one iteration costs a dense block factorisation per instance (hundreds of milliseconds at T = 2000), so a
-// few stream synchronisations per iteration are free.  One call = one outer iteration of every running instance.
+// few stream synchronisations per iteration are free.  wide_outer = one outer iteration of every running instance; its host
+// arithmetic is the phases A - E below, the rules they share with the bordered path are in dto_host_globalization.hpp.
 // ------------------------------------------------------------------------------------------------
+// ---- A: delta_w of the first factorisation attempt of every running instance, on the exact Hessian of the Lagrangian
+static void wide_first_delta_w(WideState& W) {
+  const dto_solver_opts& o = W.opt;
+  for (size_t i = 0; i < (size_t)W.B; ++i) {
+    WideInst& s = W.I[i];
+    W.h_active[i] = s.status == 0;
+    if (s.status != 0) continue;
+    s.attempt = 0;
+    if (s.ls_fail) s.dw = ladder_after_ls_fail(o, s.dlast);
+    else if (s.dlast > 1.1 * o.delta_w_min && s.full_streak < 2) s.dw = std::max(o.delta_w_min, o.kappa_w_minus * s.dlast);
+    else s.dw = 0.0;
+    s.gam = 1.0;
+    W.h_dw[i] = s.dw;
+    W.h_gam[i] = 1.0;
+  }
+}
+
+// ---- B: convergence test at the current iterate (Ipopt's scaled error, reference Options tolerances) and monotone barrier update
+//      (Waechter & Biegler (7)) with mu_target as the floor.  Terminated instances leave h_active; true when the barrier parameter
+//      of some instance moved
+static bool wide_convergence(WideState& W, int64_t Nc) {
+  const dto_solver_opts& o = W.opt;
+  bool mu_moved = false;
+  for (size_t i = 0; i < (size_t)W.B; ++i) {
+    if (!W.h_active[i]) continue;
+    WideInst& s = W.I[i];
+    const double* sv = &W.h_stats[i * DTO_WIDE_NSTAT];
+    const double f = sv[DTO_WIDE_F], th1 = sv[DTO_WIDE_TH1], thinf = sv[DTO_WIDE_THINF], dinf = sv[DTO_WIDE_DINF];
+    s.f = f; s.thinf = thinf; s.dinf = dinf;
+    // Ipopt's scaling with the bound multipliers included; complementarity measured against mu_target (as k_conv does)
+    const ErrScale es = ipopt_scaling(o, sv[DTO_WIDE_SUMLAM], Nc, W.barrier ? sv[DTO_WIDE_SUMZ] : 0.0, W.n_bnd);
+    auto compl_at = [&](double m) {
+      if (!W.barrier) return 0.0;
+      const double szmin = sv[DTO_WIDE_ISZMAX] > 0.0 ? 1.0 / sv[DTO_WIDE_ISZMAX] : 1e300;
+      return std::max(sv[DTO_WIDE_SZMAX] - m, m - szmin);
+    };
+    const double c0 = compl_at(o.mu_target);
+    const IterMeasures m{f, th1, thinf, dinf, std::max(std::max(dinf / es.sd, thinf), c0 / es.sc), c0};
+    s.acc_count = acceptable_point(o, m, s.f_last) ? s.acc_count + 1 : 0;
+    s.f_last = f;
+    s.status = terminal_status(o, s.iter, m, s.acc_count);
+    if (s.status == 0 && W.barrier) {
+      const double mu = monotone_mu(o, s.mu, std::max(dinf / es.sd, thinf), es.sc, compl_at);
+      if (mu != s.mu) { s.mu = mu; W.h_mu[i] = mu; s.filter_n = 0; mu_moved = true; }
+    }
+    init_theta_limits(s, th1);
+    if (s.status != 0) W.h_active[i] = 0;
+  }
+  return mu_moved;
+}
+
+// ---- C: inertia of the factorisations just made (Algorithm IC).  Accepted: the instance leaves h_active and its flag becomes 2
+//      ("step available").  Rejected: the next rung -- the ladder of k_kkt_sep, exact Hessian up to delta_w_exact_cap, then the
+//      constraint curvature is dropped (Gauss-Newton) instead of inflating delta_w further: large delta_w only inflates the
+//      multipliers it fights.  True when some instance needs another attempt
+static bool wide_inertia_verdict(WideState& W) {
+  const dto_solver_opts& o = W.opt;
+  bool again = false;
+  for (size_t i = 0; i < (size_t)W.B; ++i) {
+    if (!W.h_active[i]) continue;
+    WideInst& s = W.I[i];
+    if (W.h_flags[i] || s.attempt >= o.max_refactor) {
+      if (s.dw > 0.0 && s.gam != 0.0) s.dlast = s.dw;
+      if (s.dw == 0.0) s.dlast = 0.0;
+      s.gamma_acc = s.gam;
+      if (!W.h_flags[i]) s.ls_fail = 1;
+      W.h_active[i] = 0;
+      W.h_flags[i] = 2;
+      continue;
+    }
+    if (s.gam != 0.0) {
+      const bool skip_ladder = (s.gamma_acc == 0.0) && (s.iter % 4 != 0);
+      if (!skip_ladder) s.dw = ladder_next(o, s.dw, s.dlast);
+      if (skip_ladder || s.dw > o.delta_w_exact_cap) { s.gam = 0.0; s.dw = o.delta_w_init; }
+    } else {
+      s.dw = std::min(s.dw * o.kappa_w_plus, o.delta_w_max);
+    }
+    s.attempt++;
+    W.h_dw[i] = s.dw;
+    W.h_gam[i] = s.gam;
+    again = true;
+  }
+  return again;
+}
+
+// ---- D: filter line search over the merit table of the trial steps alpha_pmax 2^-k: h_alpha, h_alphad.  With finite bounds
+//      phi = f - mu sum log(gaps) (the merit kernel adds the same terms at the trial points), alpha_pmax is the fraction-to-the-
+//      boundary step and the bound multipliers take the dual step alpha_dmax
+static void wide_line_search(WideState& W) {
+  for (size_t i = 0; i < (size_t)W.B; ++i) {
+    W.h_alpha[i] = 0.0;
+    if (!W.h_active[i]) continue;
+    WideInst& s = W.I[i];
+    const double* sv = &W.h_stats[i * DTO_WIDE_NSTAT];
+    const double* mv = &W.h_merit[i * 2 * DTO_WIDE_TRIALS];
+    const double amax = W.barrier ? sv[DTO_WIDE_APMAX] : 1.0;
+    const double th0 = sv[DTO_WIDE_TH1], phi0 = sv[DTO_WIDE_F] - (W.barrier ? s.mu * sv[DTO_WIDE_LOGBAR] : 0.0), dphi = sv[DTO_WIDE_GPHID];
+    double alpha = amax, accepted = -1.0;
+    bool ftype = false;
+    MostFeasible best;
+    for (int k = 0; k < DTO_WIDE_TRIALS; ++k, alpha *= 0.5) {
+      note_most_feasible(best, k, mv[2 * k + 1]);
+      const TrialVerdict v = trial_acceptable(s, th0, phi0, dphi, alpha, mv[2 * k + 1], mv[2 * k]);
+      if (v != TRIAL_REJECTED) { accepted = alpha; ftype = v == TRIAL_ACCEPTED_FTYPE; break; }
+    }
+    const double chosen = finish_line_search(s, accepted, ftype, best, th0, phi0, amax, DTO_WIDE_TRIALS, 0);
+    s.alpha = chosen;
+    s.full_streak = (chosen >= amax) ? s.full_streak + 1 : 0;
+    W.h_alphad[i] = W.barrier ? sv[DTO_WIDE_ADMAX] : 0.0;
+    if (i == 0 && getenv("DTO_WIDE_VERBOSE"))
+      fprintf(stderr, "it %3d f %.6e th1 %.3e thinf %.3e dinf %.3e dphi %.3e dw %.2e att %d alpha %.4g lsfail %d | f(1) %.6e th(1) %.3e f(.5) %.6e th(.5) %.3e\n",
+              s.iter, phi0, th0, sv[DTO_WIDE_THINF], sv[DTO_WIDE_DINF], dphi, s.dw, s.attempt, chosen, s.ls_fail, mv[0], mv[1], mv[2], mv[3]);
+    s.iter++;
+    W.h_alpha[i] = chosen;
+  }
+}
+
+// ---- E: take the steps (bound multipliers first: their update reads the old point)
+static int wide_take_steps(Problem* p, hipStream_t st) {
+  WideState& W = *p->wide;
+  const int64_t B = W.B, Nz = p->L.Nz, Nc = p->L.Nc;
+  const dim3 grid((unsigned)(B * AXPY_BLOCKS_PER_ROW));
+  HIP_TRY(hipMemcpyAsync(W.alpha, W.h_alpha.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+  if (W.barrier) {
+    for (size_t i = 0; i < (size_t)B; ++i) if (W.h_alpha[i] == 0.0) W.h_alphad[i] = 0.0;
+    HIP_TRY(hipMemcpyAsync(W.alphad, W.h_alphad.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_wide_update_bounds, grid, dim3(256), 0, st, (const double*)W.z, (const double*)W.dz, (double*)W.zl, (double*)W.zu,
+                       (const double*)W.lo, (const double*)W.hi, W.ldb, (const double*)W.alpha, (const double*)W.alphad, (const double*)W.mu, Nz);
+  }
+  hipLaunchKernelGGL(k_rows_axpy, grid, dim3(256), 0, st, (double*)W.z, (const double*)W.dz, (const double*)W.alpha, Nz, Nz, Nz);
+  if (Nc > 0) hipLaunchKernelGGL(k_rows_axpy, grid, dim3(256), 0, st, (double*)W.lam, (const double*)W.dlam, (const double*)W.alpha, Nc, Nc, Nc);
+  return DTO_OK;
+}
+
 static int wide_outer(Problem* p, hipStream_t st) {
   WideState& W = *p->wide;
-  const Layout& L = p->L;
-  const dto_solver_opts& o = W.opt;
-  const int64_t B = W.B, Nz = L.Nz, Nc = L.Nc;
-  const bool barrier = W.barrier;
-  const int64_t n_bnd = W.n_bnd;
-  std::vector<WideInst>& I = W.I;
-  std::vector<int>&h_active = W.h_active, &h_flags = W.h_flags;
-  std::vector<double>&h_gam = W.h_gam, &h_dw = W.h_dw, &h_stats = W.h_stats, &h_merit = W.h_merit, &h_alpha = W.h_alpha,
-                     &h_mu = W.h_mu, &h_alphad = W.h_alphad;
-  double *z = W.z, *lam = W.lam, *dz = W.dz, *dlam = W.dlam, *d_lo = W.lo, *d_hi = W.hi, *d_dw = W.dw, *d_stats = W.stats,
-         *d_merit = W.merit, *d_alpha = W.alpha, *d_gam = W.gam, *d_zl = W.zl, *d_zu = W.zu, *d_mu = W.mu, *d_alphad = W.alphad;
-  int *d_flags = W.flags, *d_active = W.active;
+  const int64_t B = W.B;
   dto_wide_args a;
   wide_fill_args(p, a);
   auto launch = [&](int op) -> int {
     if (op == DTO_WIDE_STEP) wide_fac_taken(p);
-    const int lrc = p->vt->launch_wide(op, &a, (void*)st);
-    return lrc;
+    return p->vt->launch_wide(op, &a, (void*)st);
   };
-  constexpr double G_TH = 1e-5, G_PHI = 1e-8, S_TH = 1.1, S_PHI = 2.3, ETA = 1e-8;
-  const char* dump_prefix = getenv("DTO_WIDE_DUMP");   // debug: <prefix>_L<k>_<what>.bin of the first DTO_WIDE_DUMP_MAX launches
-  const int dump_max = getenv("DTO_WIDE_DUMP_MAX") ? atoi(getenv("DTO_WIDE_DUMP_MAX")) : 1;
-  {
-    // ---- A: first factorisation attempt of every running instance
-    for (int64_t i = 0; i < B; ++i) {
-      WideInst& s = I[(size_t)i];
-      h_active[(size_t)i] = s.status == 0;
-      if (s.status != 0) continue;
-      s.attempt = 0;
-      if (s.ls_fail) s.dw = std::min(o.delta_w_exact_cap, std::max(10.0 * s.dlast, o.delta_w_init));
-      else if (s.dlast > 1.1 * o.delta_w_min && s.full_streak < 2) s.dw = std::max(o.delta_w_min, o.kappa_w_minus * s.dlast);
-      else s.dw = 0.0;
-      s.gam = 1.0;  // the exact Hessian of the Lagrangian first
-      h_dw[(size_t)i] = s.dw;
-      h_gam[(size_t)i] = 1.0;
-    }
-    bool first_pass = true;
-    for (;;) {
-      HIP_TRY(hipMemcpyAsync(d_active, h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(d_dw, h_dw.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(d_gam, h_gam.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
-      { const int lrc = launch(DTO_WIDE_STEP); if (lrc) return hip_fail((hipError_t)lrc, "wide step"); }
-      HIP_TRY(hipMemcpyAsync(h_flags.data(), d_flags, B * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(h_stats.data(), d_stats, h_stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (dump_prefix && W.dump_launch < dump_max) {
-        // debug (tools/wide_debug.py): everything the launch produced -- factor records, step, statistics, flags -- plus its inputs
-        auto wr = [&](const char* what, const void* dptr, size_t bytes) {
-          std::vector<char> hb(bytes);
-          if (hipMemcpy(hb.data(), dptr, bytes, hipMemcpyDeviceToHost) != hipSuccess) return;
-          char fn[1024];
-          snprintf(fn, sizeof(fn), "%s_L%d_%s.bin", dump_prefix, W.dump_launch, what);
-          if (FILE* f = fopen(fn, "wb")) { fwrite(hb.data(), 1, bytes, f); fclose(f); }
-        };
-        dto_wide_info info;
-        p->vt->wide_info(&info);
-        wr("fac", p->wide_fac, (size_t)B * (size_t)L.T * (size_t)info.fac_stage * sizeof(double));
-        wr("dz", dz, (size_t)B * Nz * sizeof(double));
-        wr("dlam", dlam, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double));
-        wr("z", z, (size_t)B * Nz * sizeof(double));
-        wr("lam", lam, (size_t)B * std::max<int64_t>(1, Nc) * sizeof(double));
-        wr("stats", d_stats, (size_t)B * DTO_WIDE_NSTAT * sizeof(double));
-        wr("flags", d_flags, (size_t)B * sizeof(int));
-        wr("dw", d_dw, (size_t)B * sizeof(double));
-        wr("active", d_active, (size_t)B * sizeof(int));
-        ++W.dump_launch;
-      }
-      bool again = false, mu_moved = false;
-      for (int64_t i = 0; i < B; ++i) {
-        if (!h_active[(size_t)i]) continue;
-        WideInst& s = I[(size_t)i];
-        const double* sv = &h_stats[(size_t)i * DTO_WIDE_NSTAT];
-        if (first_pass) {
-          // ---- B: convergence test at the current iterate (Ipopt's scaled error, reference Options tolerances)
-          const double f = sv[DTO_WIDE_F], th1 = sv[DTO_WIDE_TH1], thinf = sv[DTO_WIDE_THINF], dinf = sv[DTO_WIDE_DINF];
-          s.f = f; s.thinf = thinf; s.dinf = dinf;
-          // Ipopt's scaling with the bound multipliers included; complementarity measured against mu_target (as k_conv does)
-          const double sumz = barrier ? sv[DTO_WIDE_SUMZ] : 0.0;
-          const ErrScale es = ipopt_scaling(o, sv[DTO_WIDE_SUMLAM], Nc, sumz, n_bnd);
-          const double sd = es.sd, scn = es.sc;
-          auto compl_at = [&](double m) {
-            if (!barrier) return 0.0;
-            const double szmin = sv[DTO_WIDE_ISZMAX] > 0.0 ? 1.0 / sv[DTO_WIDE_ISZMAX] : 1e300;
-            return std::max(sv[DTO_WIDE_SZMAX] - m, m - szmin);
-          };
-          const double c0 = compl_at(o.mu_target);
-          const double e0 = std::max(std::max(dinf / sd, thinf), c0 / scn);
-          const bool acceptable = o.acceptable_iter > 0 && e0 <= o.acceptable_tol && dinf <= o.acceptable_dual_inf_tol &&
-                                  thinf <= o.acceptable_constr_viol_tol && c0 <= o.acceptable_compl_inf_tol &&
-                                  std::fabs(f - s.f_last) / std::max(1.0, std::fabs(f)) <= o.acceptable_obj_change_tol;
-          s.acc_count = acceptable ? s.acc_count + 1 : 0;
-          s.f_last = f;
-          if (!(f == f) || !(th1 == th1) || !(dinf == dinf)) s.status = 3;
-          else if (e0 <= o.tol && dinf <= o.dual_inf_tol && thinf <= o.constr_viol_tol && c0 <= o.compl_inf_tol) s.status = 1;
-          else if (o.acceptable_iter > 0 && s.acc_count >= o.acceptable_iter) s.status = 4;
-          else if (s.iter >= o.max_iter) s.status = 2;
-          else if (barrier) {
-            // monotone barrier update (Waechter & Biegler (7)) with mu_target as the floor; the step just computed belongs to
-            // the old mu: instances whose mu moved are evaluated again before anything is decided about their factorisation
-            const double m = monotone_mu(o, s.mu, std::max(dinf / sd, thinf), scn, compl_at);
-            if (m != s.mu) { s.mu = m; h_mu[(size_t)i] = m; s.filter_n = 0; mu_moved = true; }
-          }
-          if (s.theta_max < 0.0) { s.theta_max = 1e4 * std::max(1.0, th1); s.theta_min = 1e-4 * std::max(1.0, th1); }
-          if (s.status != 0) { h_active[(size_t)i] = 0; continue; }
-        }
-      }
-      if (first_pass && mu_moved) {
-        // the barrier parameter of some instance moved: its step (and statistics) are re-evaluated with the new mu before the
-        // inertia of that factorisation is judged; nothing of the ladder advances in this pass
-        HIP_TRY(hipMemcpyAsync(d_mu, h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
-        first_pass = false;
-        continue;
-      }
-      for (int64_t i = 0; i < B; ++i) {
-        if (!h_active[(size_t)i]) continue;
-        WideInst& s = I[(size_t)i];
-        // ---- C: inertia (Algorithm IC, ladder on the exact Hessian)
-        if (h_flags[(size_t)i] || s.attempt >= o.max_refactor) {
-          if (s.dw > 0.0 && s.gam != 0.0) s.dlast = s.dw;
-          if (s.dw == 0.0) s.dlast = 0.0;
-          s.gamma_acc = s.gam;
-          if (!h_flags[(size_t)i]) s.ls_fail = 1;
-          h_active[(size_t)i] = 0;   // factorisation accepted: no further attempt
-          h_flags[(size_t)i] = 2;    // marks "step available" for the line search below
-        } else {
-          // same ladder as k_kkt_sep: exact Hessian up to delta_w_exact_cap, then the constraint curvature is dropped
-          // (Gauss-Newton) instead of inflating delta_w further -- large delta_w only inflates the multipliers it fights
-          if (s.gam != 0.0) {
-            const bool skip_ladder = (s.gamma_acc == 0.0) && (s.iter % 4 != 0);
-            if (s.dw == 0.0 && !skip_ladder) s.dw = (s.dlast == 0.0) ? o.delta_w_init : std::max(o.delta_w_min, o.kappa_w_minus * s.dlast);
-            else if (!skip_ladder) s.dw *= (s.dlast == 0.0) ? o.kappa_w_plus_first : o.kappa_w_plus;
-            if (skip_ladder || s.dw > o.delta_w_exact_cap) { s.gam = 0.0; s.dw = o.delta_w_init; }
-          } else {
-            s.dw = std::min(s.dw * o.kappa_w_plus, o.delta_w_max);
-          }
-          s.attempt++;
-          h_dw[(size_t)i] = s.dw;
-          h_gam[(size_t)i] = s.gam;
-          again = true;
-        }
-      }
-      first_pass = false;
-      if (!again) break;
-    }
-    // ---- D: filter line search over the trial steps 2^-k
-    for (int64_t i = 0; i < B; ++i) h_active[(size_t)i] = (I[(size_t)i].status == 0);
-    W.any_running = false;
-    for (int64_t i = 0; i < B; ++i) W.any_running = W.any_running || h_active[(size_t)i];
-    if (!W.any_running) return DTO_OK;
-    HIP_TRY(hipMemcpyAsync(d_active, h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-    { const int lrc = launch(DTO_WIDE_MERIT); if (lrc) return hip_fail((hipError_t)lrc, "wide merit"); }
-    HIP_TRY(hipMemcpyAsync(h_merit.data(), d_merit, h_merit.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  wide_first_delta_w(W);
+  for (bool first_pass = true;; first_pass = false) {
+    HIP_TRY(hipMemcpyAsync(W.active, W.h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.dw, W.h_dw.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(W.gam, W.h_gam.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+    { const int lrc = launch(DTO_WIDE_STEP); if (lrc) return hip_fail((hipError_t)lrc, "wide step"); }
+    HIP_TRY(hipMemcpyAsync(W.h_flags.data(), W.flags, B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(W.h_stats.data(), W.stats, W.h_stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (dump_prefix && W.dump_merit < dump_max) {   // debug: the line-search table of this iteration
-      char fn[1024];
-      snprintf(fn, sizeof(fn), "%s_M%d_merit.bin", dump_prefix, W.dump_merit++);
-      if (FILE* f = fopen(fn, "wb")) { fwrite(h_merit.data(), sizeof(double), h_merit.size(), f); fclose(f); }
+    wide_debug_dump(p, false);
+    if (first_pass && wide_convergence(W, p->L.Nc)) {
+      // the step just computed belongs to the old mu: it (and the statistics) are evaluated again with the new one before the
+      // inertia of that factorisation is judged; nothing of the ladder advances in this pass
+      HIP_TRY(hipMemcpyAsync(W.mu, W.h_mu.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
+      continue;
     }
-    for (int64_t i = 0; i < B; ++i) {
-      h_alpha[(size_t)i] = 0.0;
-      if (!h_active[(size_t)i]) continue;
-      WideInst& s = I[(size_t)i];
-      const double* sv = &h_stats[(size_t)i * DTO_WIDE_NSTAT];
-      const double* mv = &h_merit[(size_t)i * 2 * DTO_WIDE_TRIALS];
-      // with finite bounds: phi = f - mu sum log(gaps) (the merit kernel adds the same terms at the trial points), trial steps
-      // alpha_pmax 2^-k (fraction to the boundary), dual step alpha_dmax for the bound multipliers
-      const double amax = barrier ? sv[DTO_WIDE_APMAX] : 1.0;
-      const double th0 = sv[DTO_WIDE_TH1], phi0 = sv[DTO_WIDE_F] - (barrier ? s.mu * sv[DTO_WIDE_LOGBAR] : 0.0), dphi = sv[DTO_WIDE_GPHID];
-      const int nf = std::min(s.filter_n, DTO_FILTER_CAP);
-      double alpha = amax, chosen = -1.0;
-      bool ftype = false;
-      int best = 0;
-      for (int k = 0; k < DTO_WIDE_TRIALS; ++k) {
-        const double pk = mv[2 * k], tk = mv[2 * k + 1];
-        if (tk < mv[2 * best + 1] || !(mv[2 * best + 1] == mv[2 * best + 1])) best = k;
-        bool ok = (tk == tk) && (pk == pk) && tk <= s.theta_max;
-        const bool sw = dphi < 0.0 && alpha * std::pow(-dphi, S_PHI) > std::pow(th0, S_TH);
-        if (ok) {
-          if (sw && th0 <= s.theta_min) ok = pk <= phi0 + ETA * alpha * dphi + 1e-13 * std::fabs(phi0);
-          else ok = (tk <= (1.0 - G_TH) * th0) || (pk <= phi0 - G_PHI * th0);
-        }
-        if (ok)
-          for (int q = 0; q < nf; ++q) {
-            const double tf = s.filt[2 * q], pf = s.filt[2 * q + 1];
-            if (!(tk <= (1.0 - G_TH) * tf || pk <= pf - G_PHI * tf)) { ok = false; break; }
-          }
-        if (ok) { chosen = alpha; ftype = sw && (pk <= phi0 + ETA * alpha * dphi + 1e-13 * std::fabs(phi0)); break; }
-        alpha *= 0.5;
-      }
-      bool augment;
-      if (chosen < 0.0) {
-        double ab = amax;
-        for (int k = 0; k < best; ++k) ab *= 0.5;
-        chosen = (mv[2 * best + 1] == mv[2 * best + 1] && mv[2 * best + 1] < th0) ? ab : alpha * 2.0;
-        s.ls_fail = 1; augment = true;
-      } else { s.ls_fail = 0; augment = !ftype; }
-      if (augment) {
-        if ((int)s.filt.size() < 2 * DTO_FILTER_CAP) s.filt.resize(2 * DTO_FILTER_CAP, 0.0);
-        const int slot = s.filter_n % DTO_FILTER_CAP;
-        s.filt[2 * slot] = (1.0 - G_TH) * th0;
-        s.filt[2 * slot + 1] = phi0 - G_PHI * th0;
-        s.filter_n++;
-      }
-      s.alpha = chosen;
-      s.full_streak = (chosen >= amax) ? s.full_streak + 1 : 0;
-      h_alphad[(size_t)i] = barrier ? sv[DTO_WIDE_ADMAX] : 0.0;
-      if (i == 0 && getenv("DTO_WIDE_VERBOSE"))
-        fprintf(stderr, "it %3d f %.6e th1 %.3e thinf %.3e dinf %.3e dphi %.3e dw %.2e att %d alpha %.4g lsfail %d | f(1) %.6e th(1) %.3e f(.5) %.6e th(.5) %.3e\n",
-                s.iter, phi0, th0, sv[DTO_WIDE_THINF], sv[DTO_WIDE_DINF], dphi, s.dw, s.attempt, chosen, s.ls_fail, mv[0], mv[1], mv[2], mv[3]);
-      s.iter++;
-      h_alpha[(size_t)i] = chosen;
-    }
-    // ---- E: take the steps (bound multipliers first: their update reads the old point)
-    HIP_TRY(hipMemcpyAsync(d_alpha, h_alpha.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
-    if (barrier) {
-      for (int64_t i = 0; i < B; ++i) if (h_alpha[(size_t)i] == 0.0) h_alphad[(size_t)i] = 0.0;
-      HIP_TRY(hipMemcpyAsync(d_alphad, h_alphad.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_wide_update_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (const double*)z, (const double*)dz,
-                         d_zl, d_zu, (const double*)d_lo, (const double*)d_hi, W.ldb, (const double*)d_alpha, (const double*)d_alphad,
-                         (const double*)d_mu, Nz);
-    }
-    hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)d_alpha, Nz, Nz, Nz);
-    if (Nc > 0)
-      hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, lam, (const double*)dlam, (const double*)d_alpha, Nc, Nc, Nc);
-    if (W.user.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - W.t_start).count() > W.user.max_cpu_time)
-      W.timed_out = true;
+    if (!wide_inertia_verdict(W)) break;
   }
+  W.any_running = false;
+  for (size_t i = 0; i < (size_t)B; ++i) {
+    W.h_active[i] = W.I[i].status == 0;
+    W.any_running = W.any_running || W.h_active[i];
+  }
+  if (!W.any_running) return DTO_OK;
+  HIP_TRY(hipMemcpyAsync(W.active, W.h_active.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  { const int lrc = launch(DTO_WIDE_MERIT); if (lrc) return hip_fail((hipError_t)lrc, "wide merit"); }
+  HIP_TRY(hipMemcpyAsync(W.h_merit.data(), W.merit, W.h_merit.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  wide_debug_dump(p, true);
+  wide_line_search(W);
+  const int rc = wide_take_steps(p, st);
+  if (rc) return rc;
+  if (W.user.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - W.t_start).count() > W.user.max_cpu_time)
+    W.timed_out = true;
   return DTO_OK;
 }
 
@@ -2420,19 +2380,13 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       if (L.var_lo[k] == L.var_hi[k]) hz[(size_t)i * Nz + k] = L.var_lo[k];
   HIP_TRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(lam, 0, (size_t)B * Nc * sizeof(double), st));
-  struct Inst {
-    int status = 0, iter = 0, ls_fail = 0, filter_n = 0;
-    double dlast = 0.0, theta_max = -1.0, theta_min = -1.0;
-    double mu = 0.0;   // barrier parameter (inequality general rows only)
-    std::vector<double> filt;
-  };
+  using Inst = GlobInst;   // (mu: inequality general rows only)
   std::vector<Inst> I((size_t)B);
   // slacks and multipliers of the general rows on the host (the multipliers are mirrored into lam after every update)
   std::vector<double> hs((size_t)B * std::max<int64_t>(1, ng), 0.0), hnu((size_t)B * std::max<int64_t>(1, ng), 0.0), hds((size_t)B * std::max<int64_t>(1, ng), 0.0);
   std::vector<double> hgd((size_t)B * std::max<int64_t>(1, ng), 0.0), hgs((size_t)B * std::max<int64_t>(1, ng), 0.0), hst((size_t)B * std::max<int64_t>(1, ng), 0.0);
   std::vector<double> dwv((size_t)B), hf((size_t)B), hth((size_t)B), hal((size_t)B), hphi0((size_t)B);
   std::vector<int> okv((size_t)B);
-  constexpr double G_TH = 1e-5, G_PHI = 1e-8, S_TH = 1.1, S_PHI = 2.3, ETA = 1e-8;
   constexpr int TRIALS = DTO_LS_TRIALS;
   dto_batch bz = *b;
   bz.x = z; bz.ldx = Nz; bz.params = nullptr; bz.ldp = 0;
@@ -2469,10 +2423,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       HIP_TRY(hipMemcpyAsync(dgs, hgs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
     }
     // ---- step at the current point: delta_w ladder per instance (Algorithm IC), all instances share the sweeps
-    for (int64_t i = 0; i < B; ++i) {
-      Inst& s = I[(size_t)i];
-      dwv[(size_t)i] = s.ls_fail ? std::min(o.delta_w_exact_cap, std::max(10.0 * s.dlast, o.delta_w_init)) : 0.0;
-    }
+    for (int64_t i = 0; i < B; ++i) dwv[(size_t)i] = I[(size_t)i].ls_fail ? ladder_after_ls_fail(o, I[(size_t)i].dlast) : 0.0;
     BorderStats bs;
     for (int attempt = 0;; ++attempt) {
       bs.reuse_point = attempt > 0;
@@ -2481,9 +2432,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       for (int64_t i = 0; i < B; ++i) {
         Inst& s = I[(size_t)i];
         if (s.status != 0 || okv[(size_t)i] || attempt >= o.max_refactor) continue;
-        double& dw = dwv[(size_t)i];
-        dw = (dw == 0.0) ? ((s.dlast == 0.0) ? o.delta_w_init : std::max(o.delta_w_min, o.kappa_w_minus * s.dlast))
-                         : dw * ((s.dlast == 0.0) ? o.kappa_w_plus_first : o.kappa_w_plus);
+        dwv[(size_t)i] = ladder_next(o, dwv[(size_t)i], s.dlast);
         again = true;
       }
       if (!again) break;
@@ -2533,40 +2482,35 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
           gd += bs.grad[(size_t)i * Nz + k] * bs.dz[(size_t)i * Nz + k];
         }
       }
-      // complementarity of the slack / multiplier pairs against mu_target (termination) and against mu (barrier update); the
+      // complementarity of the slack / multiplier pairs against mu_target (termination; against mu: the barrier update below); the
       // step of the inequality rows: ds = (mu - s nu) / nu - (s / nu) dnu, barrier term of the merit's directional derivative
-      double c0 = 0.0, cmu = 0.0, snu = 0.0, bar_d = 0.0;
+      double c0 = 0.0, snu = 0.0, bar_d = 0.0;
       for (int64_t q = 0; q < ng; ++q) {
         if (!ineq[(size_t)q]) continue;
         const size_t e = (size_t)(i * ng + q);
         const double sv = hs[e], nv = hnu[e], dnu = dnu_of(i, q);
-        c0 = std::max(c0, std::fabs(sv * nv - o.mu_target)); cmu = std::max(cmu, std::fabs(sv * nv - s.mu)); snu += std::fabs(nv);
+        c0 = std::max(c0, std::fabs(sv * nv - o.mu_target)); snu += std::fabs(nv);
         hds[e] = (s.mu - sv * nv) / nv - (sv / nv) * dnu;
         bar_d += hds[e] / sv;
       }
       // (the slack's bound multiplier of a slack-eliminated row IS its nu: it counts among the bound multipliers, as the slack
       //  multipliers do in conv_body)
       const ErrScale es = ipopt_scaling(o, slam, Nc, snu, ni);
-      const double sd = es.sd, scn = es.sc;
-      const double e0 = std::max(std::max(dinf / sd, thinf), c0 / scn);
-      const double f = hf[(size_t)i];
+      const IterMeasures m{hf[(size_t)i], th1, thinf, dinf, std::max(std::max(dinf / es.sd, thinf), c0 / es.sc), c0};
       mu_moved[(size_t)i] = 0;
-      if (!(f == f) || !(th1 == th1) || !(dinf == dinf)) s.status = 3;
-      else if (e0 <= o.tol && dinf <= o.dual_inf_tol && thinf <= o.constr_viol_tol && c0 <= o.compl_inf_tol) s.status = 1;
-      else if (s.iter >= o.max_iter) s.status = 2;
-      else if (ni > 0) {
+      s.status = terminal_status(o, s.iter, m, 0);   // acc_count = 0: no acceptable-level termination on this path
+      if (s.status == 0 && ni > 0) {
         // Ipopt's monotone rule: once the barrier problem is solved to kappa_eps mu the parameter drops (and the filter is reset);
         // the step computed above belongs to the old mu: this instance waits one round (alpha = 0) for the step of the new one
-        const double mu = monotone_mu(o, s.mu, std::max(dinf / sd, thinf), scn, [&](double m) {
+        const double mu = monotone_mu(o, s.mu, std::max(dinf / es.sd, thinf), es.sc, [&](double mu_at) {
           double c = 0.0;
           for (int64_t q = 0; q < ng; ++q)
-            if (ineq[(size_t)q]) c = std::max(c, std::fabs(hs[(size_t)(i * ng + q)] * hnu[(size_t)(i * ng + q)] - m));
+            if (ineq[(size_t)q]) c = std::max(c, std::fabs(hs[(size_t)(i * ng + q)] * hnu[(size_t)(i * ng + q)] - mu_at));
           return c;
         });
-        (void)cmu;
         if (mu != s.mu) { s.mu = mu; s.filter_n = 0; mu_moved[(size_t)i] = 1; }
       }
-      if (s.theta_max < 0.0) { s.theta_max = 1e4 * std::max(1.0, th1); s.theta_min = 1e-4 * std::max(1.0, th1); }
+      init_theta_limits(s, th1);
       th0[(size_t)i] = th1; gphid[(size_t)i] = gd - s.mu * bar_d;
       if (s.status == 0) {
         any = true;
@@ -2579,9 +2523,9 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     //      summed on the device).  Trial k is evaluated only while some running instance has not accepted a shorter-numbered
     //      one (round 4: all eight trials of every iteration, each with its constraint vector over PCIe, were most of the
     //      8.7 ms an iteration of a 512-instance batch took; a Newton step near the solution is accepted at alpha = 1)
-    std::vector<double> phi((size_t)B * TRIALS, 0.0), th((size_t)B * TRIALS, 0.0), chosen_a((size_t)B, -1.0);
+    std::vector<double> chosen_a((size_t)B, -1.0);
     std::vector<char> ftype_a((size_t)B, 0);
-    std::vector<int> best_a((size_t)B, 0);
+    std::vector<MostFeasible> best_a((size_t)B);
     // inequality rows: the trials start from the fraction-to-the-boundary step of the slacks, the merit is the barrier function
     std::vector<double> apmax((size_t)B, 1.0), admax((size_t)B, 1.0);
     for (int64_t i = 0; i < B && ni > 0; ++i) {
@@ -2600,7 +2544,6 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       }
       hphi0[(size_t)i] -= s.mu * lb;
     }
-    int k_done = 0;
     for (int k = 0; k < TRIALS; ++k) {
       bool undecided = false;
       for (int64_t i = 0; i < B; ++i) undecided = undecided || (I[(size_t)i].status == 0 && chosen_a[(size_t)i] < 0.0);
@@ -2626,59 +2569,27 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       HIP_TRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipMemcpyAsync(hth.data(), dth, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
-      k_done = k + 1;
       for (int64_t i = 0; i < B; ++i) {
         Inst& s = I[(size_t)i];
         if (s.status != 0 || chosen_a[(size_t)i] >= 0.0) continue;
-        const double alpha = hal[(size_t)i];
         double pk = hf[(size_t)i];
         const double tk = hth[(size_t)i];
         for (int64_t q = 0; q < ng && ni > 0; ++q)
           if (ineq[(size_t)q]) pk -= s.mu * std::log(hst[(size_t)(i * ng + q)]);
-        phi[(size_t)i * TRIALS + k] = pk;
-        th[(size_t)i * TRIALS + k] = tk;
-        int& best = best_a[(size_t)i];
-        if (tk < th[(size_t)i * TRIALS + best] || !(th[(size_t)i * TRIALS + best] == th[(size_t)i * TRIALS + best])) best = k;
-        const double t0 = th0[(size_t)i], phi0 = hphi0[(size_t)i], dphi = gphid[(size_t)i];
-        const int nf = std::min(s.filter_n, DTO_FILTER_CAP);
-        bool ok = (tk == tk) && (pk == pk) && tk <= s.theta_max;
-        const bool sw = dphi < 0.0 && alpha * std::pow(-dphi, S_PHI) > std::pow(t0, S_TH);
-        if (ok) {
-          if (sw && t0 <= s.theta_min) ok = pk <= phi0 + ETA * alpha * dphi + 1e-13 * std::fabs(phi0);
-          else ok = (tk <= (1.0 - G_TH) * t0) || (pk <= phi0 - G_PHI * t0);
-        }
-        if (ok)
-          for (int q = 0; q < nf; ++q) {
-            const double tf = s.filt[2 * q], pf = s.filt[2 * q + 1];
-            if (!(tk <= (1.0 - G_TH) * tf || pk <= pf - G_PHI * tf)) { ok = false; break; }
-          }
-        if (ok) { chosen_a[(size_t)i] = alpha; ftype_a[(size_t)i] = (sw && (pk <= phi0 + ETA * alpha * dphi + 1e-13 * std::fabs(phi0))) ? 1 : 0; }
+        note_most_feasible(best_a[(size_t)i], k, tk);
+        const TrialVerdict v = trial_acceptable(s, th0[(size_t)i], hphi0[(size_t)i], gphid[(size_t)i], hal[(size_t)i], tk, pk);
+        if (v != TRIAL_REJECTED) { chosen_a[(size_t)i] = hal[(size_t)i]; ftype_a[(size_t)i] = v == TRIAL_ACCEPTED_FTYPE; }
       }
     }
-    (void)k_done;
     for (int64_t i = 0; i < B; ++i) {
       hal[(size_t)i] = 0.0;
       Inst& s = I[(size_t)i];
       if (s.status != 0) continue;
-      const double t0 = th0[(size_t)i], phi0 = hphi0[(size_t)i];
-      double chosen = chosen_a[(size_t)i];
-      const bool ftype = ftype_a[(size_t)i] != 0;
-      const int best = best_a[(size_t)i];
-      bool augment;
-      if (ni > 0 && mu_moved[(size_t)i]) { hal[(size_t)i] = 0.0; continue; }   // no step, no iteration: its barrier parameter just moved
-      if (chosen < 0.0) {   // every trial rejected (all TRIALS were evaluated for this instance): the most feasible one, or the shortest
-        chosen = apmax[(size_t)i] * ((th[(size_t)i * TRIALS + best] < t0) ? std::ldexp(1.0, -best) : std::ldexp(1.0, -(TRIALS - 1)));
-        s.ls_fail = 1; augment = true;
-      } else { s.ls_fail = okv[(size_t)i] ? 0 : 1; augment = !ftype; }
-      if (augment) {
-        if ((int)s.filt.size() < 2 * DTO_FILTER_CAP) s.filt.resize(2 * DTO_FILTER_CAP, 0.0);
-        const int slot = s.filter_n % DTO_FILTER_CAP;
-        s.filt[2 * slot] = (1.0 - G_TH) * t0;
-        s.filt[2 * slot + 1] = phi0 - G_PHI * t0;
-        s.filter_n++;
-      }
+      if (ni > 0 && mu_moved[(size_t)i]) continue;   // no step, no iteration: its barrier parameter just moved
+      // (an instance whose trials were all rejected had all TRIALS of them evaluated)
+      hal[(size_t)i] = finish_line_search(s, chosen_a[(size_t)i], ftype_a[(size_t)i] != 0, best_a[(size_t)i], th0[(size_t)i], hphi0[(size_t)i],
+                                          apmax[(size_t)i], TRIALS, okv[(size_t)i] ? 0 : 1);
       s.iter++;
-      hal[(size_t)i] = chosen;
     }
     HIP_TRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)dal, Nz, Nz, Nz);
