@@ -133,6 +133,9 @@ def lib() -> C.CDLL:
         "dto_kkt_solve_refined": [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp],
         "dto_kkt_border_factor": [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, c_int32_p, c_int32_p, vp],
         "dto_kkt_border_solve": [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp],
+        "dto_kkt_border_multiply": [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp],
+        "dto_kkt_border_solve_refined": [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp,
+                                         C.c_int64, vp, vp],
         "dto_shard_range": [C.c_int64, C.c_int, C.c_int, c_int64_p, c_int64_p],
         "dto_solver_iterate": [vp, C.c_int, vp],
         "dto_solver_stats": [vp, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],

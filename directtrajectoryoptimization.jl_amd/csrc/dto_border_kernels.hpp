@@ -8,6 +8,8 @@
 //     k_border_schur  S = sym(C) - sym(P)   Cholesky of -S (flag), LU with partial pivoting (kept), zero-pivot flag
 //     k_border_rhs    y = S^-1 (s - Y r)    (G K^-1 r = Y r: K is symmetric)
 //     k_border_sub    v = v0 - Y' y
+// dto_kkt_border_multiply adds the border part of [K G'; G sym(C)] [v; y] to K v in one pass over the kept panel G (k_border_mul,
+// k_border_mul_fin); dto_kkt_border_solve_refined is built on that product and the solve above.
 // A vector of length N lives in two arrays (the variables' part and the constraint rows' part) with a leading dimension each,
 // so every k range below is two segments.  Nothing is read beyond the row lengths: the callers' padding may hold anything.
 #pragma once
@@ -94,9 +96,10 @@ static_assert(4 * 256 <= KB_MAX * KB_LD, "the reduction of k_border_gram reuses 
 // One wavefront per instance: P = sum of the partials in chunk order, S = (C + C')/2 - (P + P')/2, then lane 0: is -S positive
 // definite (Cholesky attempt), LU of S with partial pivoting into lu [B][256] (row-major, stride 16: unit-lower multipliers
 // below the diagonal, U on and above) and piv [B][16] (row exchanged with row k at step k); flags [2][B]: negdef, singular
-// (a pivot that is zero -- or not a number -- was met; the elimination of that column is skipped).
+// (a pivot that is zero -- or not a number -- was met; the elimination of that column is skipped).  csym [B][256], stride 16, keeps
+// (C + C')/2 (zeros without c and beyond nb) for k_border_mul_fin.
 static __global__ __launch_bounds__(64) void k_border_schur(int64_t B, int nb, int chunks, const double* part, const double* c, int64_t ldc,
-                                                            double* lu, int* piv, int* flags) {
+                                                            double* lu, int* piv, int* flags, double* csym) {
   __shared__ double P[256], S[256], L[256];
   const int64_t b = blockIdx.x;
   const int l = threadIdx.x;
@@ -110,12 +113,13 @@ static __global__ __launch_bounds__(64) void k_border_schur(int64_t B, int nb, i
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int i = l + 64 * e, a = i >> 4, q = i & 15;
-    double v = 0.0;
+    double v = 0.0, cs = 0.0;
     if (a < nb && q < nb) {
-      const double cs = c ? 0.5 * (c[b * ldc + a * nb + q] + c[b * ldc + q * nb + a]) : 0.0;
+      if (c) cs = 0.5 * (c[b * ldc + a * nb + q] + c[b * ldc + q * nb + a]);
       v = cs - 0.5 * (P[a * 16 + q] + P[q * 16 + a]);
     }
     S[i] = v;
+    csym[b * 256 + i] = cs;
   }
   __syncthreads();
   if (l != 0) return;
@@ -222,6 +226,79 @@ static __global__ __launch_bounds__(KB_THREADS) void k_border_sub(int nb, int64_
     if (k < n_x) sol_x[b * ldsx + k] = v;
     else sol_c[b * ldsc + (k - n_x)] = v;
   }
+}
+
+// ---- dto_kkt_border_multiply: [out; out_b] = [K G'; G sym(C)] [v; v_b].  out arrives holding K v (k_wide_kmul); the border part is
+//      ONE pass over the kept panel G, every entry loaded once and used twice:
+//          out[k] += sum_j v_b[j] G[j][k]   (j ascending, the sum formed first)       t_j += G[j][k] v[k]
+// grid.x = B * chunks with the chunks of dto_kkt_border_factor (k_border_gram), workgroup (b, ch) covers k in
+// [ch * chunk, min(N, (ch + 1) * chunk)); n_c = 0 (no g_c at factor time) skips the constraint segment of G, v and out.  Thread t
+// takes k_lo + t, k_lo + t + 256, ...: a wavefront reads 64 consecutive doubles of one row per instruction, the nb loads of one k
+// are independent.  The partial t_j: thread sums in k order, a shuffle tree inside the wavefront, the four wavefront sums in
+// wavefront order through LDS -> tpart[(b * chunks + ch) * 16 + j].  No atomics.  Nothing is read or written beyond the row lengths.
+static __global__ __launch_bounds__(KB_THREADS) void k_border_mul(int nb, int64_t n_x, int64_t n_c, int64_t chunk, int chunks,
+                                                                  const double* g_x, int64_t ldgx, const double* g_c, int64_t ldgc,
+                                                                  const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc,
+                                                                  const double* v_b, int64_t ldvb, double* out_x, int64_t ldox,
+                                                                  double* out_c, int64_t ldoc, double* tpart) {
+  __shared__ double red[KB_MAX][KB_THREADS / 64];
+  const int64_t b = blockIdx.x / chunks;
+  const int ch = (int)(blockIdx.x % chunks);
+  const int64_t N = n_x + n_c;
+  const int64_t k_lo = (int64_t)ch * chunk, k_hi = k_lo + chunk < N ? k_lo + chunk : N;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  double y[KB_MAX], acc[KB_MAX];
+#pragma unroll
+  for (int j = 0; j < KB_MAX; ++j) {
+    y[j] = j < nb ? v_b[b * ldvb + j] : 0.0;
+    acc[j] = 0.0;
+  }
+  for (int64_t k = k_lo + t; k < k_hi; k += KB_THREADS) {
+    const double vk = kb_seg(v_x, ldvx, v_c, ldvc, b, k, n_x);
+    const double ok = kb_seg(out_x, ldox, out_c, ldoc, b, k, n_x);   // (K v)[k]: requested with the row loads, not after them
+    double g[KB_MAX];
+#pragma unroll
+    for (int j = 0; j < KB_MAX; ++j) g[j] = j < nb ? kb_seg(g_x, ldgx, g_c, ldgc, b * nb + j, k, n_x) : 0.0;
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < KB_MAX; ++j)
+      if (j < nb) {
+        s += y[j] * g[j];
+        acc[j] += g[j] * vk;
+      }
+    if (k < n_x) out_x[b * ldox + k] = ok + s;
+    else out_c[b * ldoc + (k - n_x)] = ok + s;
+  }
+#pragma unroll
+  for (int j = 0; j < KB_MAX; ++j) {
+    double v = acc[j];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) red[j][wave] = v;
+  }
+  __syncthreads();   // the wavefront sums are in LDS before the first nb threads read them
+  if (t < nb) tpart[((int64_t)b * chunks + ch) * KB_MAX + t] = ((red[t][0] + red[t][1]) + red[t][2]) + red[t][3];
+}
+static_assert(KB_THREADS / 64 == 4, "k_border_mul adds four wavefront sums");
+
+// One wavefront per instance, lane j < nb: out_b[j] = sum of the partials t_j in chunk order, then + sym(C)[j][q] v_b[q], q ascending
+// (csym [B][256], stride 16, as dto_kkt_border_factor kept it).
+static __global__ __launch_bounds__(64) void k_border_mul_fin(int nb, int chunks, const double* tpart, const double* csym, const double* v_b,
+                                                              int64_t ldvb, double* out_b, int64_t ldob) {
+  const int64_t b = blockIdx.x;
+  const int j = threadIdx.x;
+  if (j >= nb) return;
+  double acc = 0.0;
+  for (int ch = 0; ch < chunks; ++ch) acc += tpart[(b * chunks + ch) * KB_MAX + j];
+  for (int q = 0; q < nb; ++q) acc += csym[b * 256 + j * 16 + q] * v_b[b * ldvb + q];
+  out_b[b * ldob + j] = acc;
+}
+
+// resid[b] = NaN for the instances whose Schur complement is singular (their solution is NaN in every entry; the maximum of
+// k_rows_maxabs ignores NaN)
+static __global__ void k_border_resid_singular(int64_t B, const int* singular, double* resid) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B && singular[b]) resid[b] = __builtin_nan("");
 }
 
 }  // namespace dto

@@ -215,6 +215,13 @@ struct KktBorder {
   DevBuf<double> lu, yw;   // [B][256] LU of S, [B][16] border unknowns of the last solve
   DevBuf<double> v0;       // [B][Nz + Nc]: K^-1 r of the last solve
   DevBuf<int> iw;          // [B][16] pivots, then [2][B] flags (negdef, singular)
+  // ---- for dto_kkt_border_multiply / dto_kkt_border_solve_refined (tile path)
+  int64_t chunk = 0, n_c = 0;   // doubles of k per workgroup and the length of the constraint segment (0: no g_c) the factor call used
+  int chunks = 0;
+  DevBuf<double> csym;     // [B][256], stride 16: (C + C')/2
+  DevBuf<double> tpart;    // [B][chunks][16]: partial G v of k_border_mul
+  DevBuf<double> ref_r, ref_d;   // [B][Nz + Nc + 16] each: residual and correction (or M sol) of dto_kkt_border_solve_refined, allocated
+                                 // by its first call with passes > 0 or a residual norm to report
 };
 static inline void kkt_border_taken(Problem* p) {
   if (p->kkt_border) p->kkt_border->valid = false;
@@ -3747,6 +3754,9 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
   if ((rc = grow(W.lu, (size_t)B * 256, "the LU of the Schur complement", std::to_string(B) + " instances x 256 doubles"))) return rc;
   if ((rc = grow(W.yw, (size_t)B * 16, "the border unknowns", std::to_string(B) + " instances x 16 doubles"))) return rc;
   if ((rc = grow(W.v0, (size_t)B * (size_t)N, "K^-1 r", std::to_string(B) + " instances x " + std::to_string(N) + " doubles"))) return rc;
+  if ((rc = grow(W.csym, (size_t)B * 256, "the symmetric part of C", std::to_string(B) + " instances x 256 doubles"))) return rc;
+  if ((rc = grow(W.tpart, (size_t)B * (size_t)chunks * 16, "the partial products of G v",
+                 std::to_string(B) + " instances x " + std::to_string(chunks) + " chunks x 16 doubles"))) return rc;
   if (const hipError_t e = W.iw.grow((size_t)B * 18); e != hipSuccess)
     return dto::hip_fail(e, ("dto_kkt_border_factor: hipMalloc of pivots and flags (" + std::to_string((size_t)B * 18 * sizeof(int)) + " bytes)").c_str());
   hipStream_t st = (hipStream_t)stream;
@@ -3763,7 +3773,8 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
   hipLaunchKernelGGL(dto::k_border_gram, dim3((unsigned)(B * chunks)), dim3(dto::KB_THREADS), 0, st, (int)nb, Nz, n_c, chunk, chunks,
                      (const double*)W.g, N, (const double*)(W.g + Nz), N, (const double*)W.y, N, (const double*)(W.y + Nz), N, W.part);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dto::k_border_schur, dim3((unsigned)B), dim3(64), 0, st, B, (int)nb, chunks, (const double*)W.part, c, ldc, W.lu, piv, flags);
+  hipLaunchKernelGGL(dto::k_border_schur, dim3((unsigned)B), dim3(64), 0, st, B, (int)nb, chunks, (const double*)W.part, c, ldc, W.lu, piv, flags,
+                     (double*)W.csym);
   HIP_TRY(hipGetLastError());
   // g_x / g_c / c have been consumed when this returns (and the flags are there)
   std::vector<int> fl(2 * (size_t)B);
@@ -3774,6 +3785,7 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
     if (schur_singular) schur_singular[i] = fl[(size_t)(B + i)];
   }
   W.nb = (int)nb; W.B = B;
+  W.chunk = chunk; W.chunks = chunks; W.n_c = n_c;
   W.valid = true;
   return DTO_OK;
 }
@@ -3802,6 +3814,103 @@ int dto_kkt_border_solve(dto_problem* h, const double* rhs_x, int64_t ldrx, cons
   hipLaunchKernelGGL(dto::k_border_sub, dim3((unsigned)(B * dto::KB_ROW_BLOCKS)), dim3(dto::KB_THREADS), 0, st, W.nb, Nz, Nc, (const double*)W.v0,
                      (const double*)W.y, N, (const double*)(W.y + Nz), N, (const double*)W.yw, sol_x, ldsx, sol_c, ldsc);
   HIP_TRY(hipGetLastError());
+  return DTO_OK;
+}
+
+// ---- the bordered matrix as an operator and refined bordered solves (tile path): K v from k_wide_kmul, the border part from one
+//      pass over the kept panel (k_border_mul, with the chunks of the factor call) and sym(C) v_b from what k_border_schur kept.
+// The checks both entry points share, in the order of dto_kkt_border_solve: path, border in place, `bad`, the vectors.
+static int check_border_vectors(Problem* p, const char* who, const char* bad, const double* in_x, int64_t ldix, const double* in_c,
+                                int64_t ldic, const double* in_b, int64_t ldib, const double* out_x, int64_t ldox, const double* out_c,
+                                int64_t ldoc, const double* out_b, int64_t ldob) {
+  if (!p->vt->launch_wide)
+    return set_error(DTO_ERR_UNSUPPORTED, (std::string(who) + ": tile path only (the lane-per-instance path keeps no assembled system to "
+                                           "multiply with: dto_kkt_multiply is unsupported there)").c_str());
+  if (!p->kkt_border || !p->kkt_border->valid)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_border_factor has not been called (or dto_kkt_assemble, dto_kkt_factor, dto_kkt_step_batch or the "
+                                      "solver has run since)");
+  if (int rc = check_kkt_vectors(p, bad, in_x, ldix, in_c, ldic, out_x, ldox, out_c, ldoc)) return rc;
+  if (!in_b || !out_b) return set_error(DTO_ERR_INVALID, "null argument");
+  if (ldib < p->kkt_border->nb || ldob < p->kkt_border->nb) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  return DTO_OK;
+}
+static int border_multiply(Problem* p, const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc, const double* v_b, int64_t ldvb,
+                           double* out_x, int64_t ldox, double* out_c, int64_t ldoc, double* out_b, int64_t ldob, hipStream_t st) {
+  dto::KktBorder& W = *p->kkt_border;
+  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc, B = W.B;
+  if (int rc = dto::wide_kkt_multiply(p, v_x, ldvx, v_c, ldvc, out_x, ldox, out_c, ldoc, st)) return rc;
+  hipLaunchKernelGGL(dto::k_border_mul, dim3((unsigned)(B * W.chunks)), dim3(dto::KB_THREADS), 0, st, W.nb, Nz, W.n_c, W.chunk, W.chunks,
+                     (const double*)W.g, N, (const double*)(W.g + Nz), N, v_x, ldvx, v_c, ldvc, v_b, ldvb, out_x, ldox, out_c, ldoc,
+                     (double*)W.tpart);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dto::k_border_mul_fin, dim3((unsigned)B), dim3(64), 0, st, W.nb, W.chunks, (const double*)W.tpart, (const double*)W.csym,
+                     v_b, ldvb, out_b, ldob);
+  HIP_TRY(hipGetLastError());
+  return DTO_OK;
+}
+
+int dto_kkt_border_multiply(dto_problem* h, const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc, const double* v_b, int64_t ldvb,
+                            double* out_x, int64_t ldox, double* out_c, int64_t ldoc, double* out_b, int64_t ldob, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  if ((rc = check_border_vectors(p, "dto_kkt_border_multiply", nullptr, v_x, ldvx, v_c, ldvc, v_b, ldvb, out_x, ldox, out_c, ldoc, out_b, ldob)))
+    return rc;
+  return border_multiply(p, v_x, ldvx, v_c, ldvc, v_b, ldvb, out_x, ldox, out_c, ldoc, out_b, ldob, (hipStream_t)stream);
+}
+
+// dto_kkt_border_solve, then `passes` rounds of (rho, sigma) = (r, s) - M (v, y), (dv, dy) = the bordered solve of it, (v, y) += (dv, dy);
+// with `resid` one more product for max |(r, s) - M (v, y)| of what is returned.  A row of the workspace is [x | c | border]: the
+// border segment is a third short row of the row kernels.  The correction solves write the workspace, never the caller's arrays
+// (v0 and yw of the handle are scratch of every bordered solve).
+int dto_kkt_border_solve_refined(dto_problem* h, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
+                                 const double* rhs_b, int64_t ldrb, double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, double* sol_b,
+                                 int64_t ldsb, double* resid, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  if ((rc = check_border_vectors(p, "dto_kkt_border_solve_refined", passes < 0 || passes > 4 ? "passes outside 0..4" : nullptr, rhs_x, ldrx,
+                                 rhs_c, ldrc, rhs_b, ldrb, sol_x, ldsx, sol_c, ldsc, sol_b, ldsb)))
+    return rc;
+  if ((rc = dto_kkt_border_solve(h, rhs_x, ldrx, rhs_c, ldrc, rhs_b, ldrb, sol_x, ldsx, sol_c, ldsc, sol_b, ldsb, stream))) return rc;
+  if (passes == 0 && !resid) return DTO_OK;
+  dto::KktBorder& W = *p->kkt_border;
+  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc, ld = N + dto::KB_MAX, B = W.B;
+  const int nb = W.nb;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t need = (size_t)B * (size_t)ld;
+  const std::string what = "dto_kkt_border_solve_refined: hipMalloc of a workspace array (" + std::to_string(need * sizeof(double)) +
+                           " bytes: " + std::to_string(B) + " instances x " + std::to_string(ld) + " doubles)";
+  if ((rc = dto::grow_buf(W.ref_r, need, what.c_str()))) return rc;
+  if ((rc = dto::grow_buf(W.ref_d, need, what.c_str()))) return rc;
+  double *r_x = W.ref_r, *r_c = r_x + Nz, *r_b = r_x + N, *d_x = W.ref_d, *d_c = d_x + Nz, *d_b = d_x + N;
+  const dim3 grid((unsigned)(B * dto::AXPY_BLOCKS_PER_ROW)), block(256);
+  auto residual = [&]() -> int {   // ref_r = rhs - M sol (M sol passes through ref_d)
+    if (int e = border_multiply(p, sol_x, ldsx, sol_c, ldsc, sol_b, ldsb, d_x, ld, d_c, ld, d_b, ld, st)) return e;
+    hipLaunchKernelGGL(dto::k_rows_residual, grid, block, 0, st, r_x, rhs_x, (const double*)d_x, Nz, ld, ldrx, ld);
+    if (Nc > 0) hipLaunchKernelGGL(dto::k_rows_residual, grid, block, 0, st, r_c, rhs_c, (const double*)d_c, Nc, ld, ldrc, ld);
+    hipLaunchKernelGGL(dto::k_rows_residual, grid, block, 0, st, r_b, rhs_b, (const double*)d_b, (int64_t)nb, ld, ldrb, ld);
+    HIP_TRY(hipGetLastError());
+    return DTO_OK;
+  };
+  for (int it = 0; it < passes; ++it) {
+    if ((rc = residual())) return rc;
+    if ((rc = dto_kkt_border_solve(h, r_x, ld, r_c, ld, r_b, ld, d_x, ld, d_c, ld, d_b, ld, stream))) return rc;
+    hipLaunchKernelGGL(dto::k_rows_add, grid, block, 0, st, sol_x, (const double*)d_x, Nz, ldsx, ld);
+    if (Nc > 0) hipLaunchKernelGGL(dto::k_rows_add, grid, block, 0, st, sol_c, (const double*)d_c, Nc, ldsc, ld);
+    hipLaunchKernelGGL(dto::k_rows_add, grid, block, 0, st, sol_b, (const double*)d_b, (int64_t)nb, ldsb, ld);
+    HIP_TRY(hipGetLastError());
+  }
+  if (resid) {
+    if ((rc = residual())) return rc;
+    // (the x, c and border segments of a workspace row are contiguous: one maximum over Nz + Nc + nb entries)
+    hipLaunchKernelGGL(dto::k_rows_maxabs, dim3((unsigned)B), dim3(256), 0, st, (const double*)W.ref_r, N + nb, ld, resid);
+    hipLaunchKernelGGL(dto::k_border_resid_singular, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, (const int*)(W.iw + (size_t)B * 17),
+                       resid);
+    HIP_TRY(hipGetLastError());
+  }
   return DTO_OK;
 }
 

@@ -843,6 +843,39 @@ class Solver:
         capi.check(self._solve_nlp._lib.dto_kkt_border_solve(self._solve_nlp._h, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, rhs_b_ptr, ldrb,
                                                              sol_x_ptr, ldsx, sol_c_ptr, ldsc, sol_b_ptr, ldsb, stream or None))
 
+    def kkt_border_multiply(self, v_x_ptr, ldvx, v_c_ptr, ldvc, v_b_ptr, ldvb, out_x_ptr, ldox, out_c_ptr, ldoc, out_b_ptr, ldob, stream=0):
+        """[out_x; out_c; out_b] = [[K, G'], [G, sym(C)]] [v_x; v_c; v_b] for the border of kkt_border_factor (include/dto.h:
+        dto_kkt_border_multiply), tile path only: K v as kkt_multiply, then one pass over the kept panel G for G' v_b and G v, and
+        sym(C) v_b.  Arrays as for kkt_border_solve.  Needs a valid border (that is where G and C live), reads no factor record.
+        The product must not overlap v.  Bit-identical from run to run.  The lane-per-instance path raises DTO_ERR_UNSUPPORTED."""
+        ptrs = (v_x_ptr, v_c_ptr, v_b_ptr, out_x_ptr, out_c_ptr, out_b_ptr)
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in ptrs):
+            raise TypeError("kkt_border_multiply takes device pointers as integers (tensor.data_ptr())")
+        if (out_x_ptr and out_x_ptr == v_x_ptr) or (out_c_ptr and out_c_ptr == v_c_ptr) or (out_b_ptr and out_b_ptr == v_b_ptr):
+            raise ValueError("kkt_border_multiply: the product must not overlap v")
+        capi.check(self._solve_nlp._lib.dto_kkt_border_multiply(self._solve_nlp._h, v_x_ptr, ldvx, v_c_ptr, ldvc, v_b_ptr, ldvb,
+                                                                out_x_ptr, ldox, out_c_ptr, ldoc, out_b_ptr, ldob, stream or None))
+
+    def kkt_border_solve_refined(self, rhs_x_ptr, ldrx, rhs_c_ptr, ldrc, rhs_b_ptr, ldrb, sol_x_ptr, ldsx, sol_c_ptr, ldsc, sol_b_ptr, ldsb,
+                                 passes, resid_ptr=0, stream=0):
+        """kkt_border_solve followed by `passes` (0 .. 4) rounds of iterative refinement against the bordered matrix (include/dto.h:
+        dto_kkt_border_solve_refined), tile path only: residual = rhs - kkt_border_multiply(sol), correction = kkt_border_solve of
+        it, sol += correction.  passes = 0 is kkt_border_solve, bit for bit.  resid_ptr: DEVICE [B] doubles or 0 -- when given, one
+        more product writes max |rhs - M sol| of the returned solution per instance (NaN for an instance with a singular Schur
+        complement).  Nothing is factorised again.  The lane-per-instance path raises DTO_ERR_UNSUPPORTED."""
+        ptrs = (rhs_x_ptr, rhs_c_ptr, rhs_b_ptr, sol_x_ptr, sol_c_ptr, sol_b_ptr, resid_ptr)
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in ptrs):
+            raise TypeError("kkt_border_solve_refined takes device pointers as integers (tensor.data_ptr())")
+        if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)):
+            raise TypeError("kkt_border_solve_refined: passes is an integer")
+        if not 0 <= passes <= 4:
+            raise ValueError("kkt_border_solve_refined: passes outside 0..4")
+        if (sol_x_ptr and sol_x_ptr == rhs_x_ptr) or (sol_c_ptr and sol_c_ptr == rhs_c_ptr) or (sol_b_ptr and sol_b_ptr == rhs_b_ptr):
+            raise ValueError("kkt_border_solve_refined: the solutions must not overlap the right-hand sides (they are read again by every pass)")
+        capi.check(self._solve_nlp._lib.dto_kkt_border_solve_refined(self._solve_nlp._h, int(passes), rhs_x_ptr, ldrx, rhs_c_ptr, ldrc,
+                                                                     rhs_b_ptr, ldrb, sol_x_ptr, ldsx, sol_c_ptr, ldsc, sol_b_ptr, ldsb,
+                                                                     resid_ptr or None, stream or None))
+
     def iterate_batch(self, n, stream=0):
         capi.check(self._solve_nlp._lib.dto_solver_iterate(self._solve_nlp._h, int(n), stream or None))
 

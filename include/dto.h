@@ -333,6 +333,42 @@ int dto_kkt_border_solve(dto_problem* p, const double* rhs_x, int64_t ldrx, cons
                          const double* rhs_b, int64_t ldrb, double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc,
                          double* sol_b, int64_t ldsb, void* stream);
 
+/* The bordered matrix as an operator, and bordered solves refined against it (tile path).  M = [K G'; G sym(C)] with the border of
+ * the last dto_kkt_border_factor: K as dto_kkt_multiply applies it, G the kept panel of border rows, sym(C) = (C + C')/2 (zero
+ * without c).  All arrays are DEVICE arrays, [B][ld], laid out as for dto_kkt_border_solve; outputs must not overlap inputs.
+ * dto_kkt_border_multiply -- [out_x; out_c; out_b] = M [v_x; v_c; v_b].  out_x / out_c first receive K v (dto_kkt_multiply's
+ * kernel), then one pass over the panel -- nb x N doubles per instance, every entry read once -- adds G' v_b to them and forms
+ * G v; out_b = G v + sym(C) v_b.  No factor record and no Schur complement is read: the product of an instance whose Schur
+ * complement is singular is finite.
+ * dto_kkt_border_solve_refined -- dto_kkt_border_solve, then `passes` (0 .. 4) rounds of (rho, sigma) = (r, s) - M (v, y),
+ * (dv, dy) = dto_kkt_border_solve of it, (v, y) += (dv, dy): fixed-precision iterative refinement, residuals in working
+ * precision.  It repairs what an inexact K^-1 (a factorisation of wrong inertia, delta_w = 0) leaves in Y, S and v0, as
+ * dto_kkt_solve_refined does for plain solves; nothing is factorised again.  passes = 0 without resid is dto_kkt_border_solve,
+ * bit for bit.  resid: DEVICE [B] or NULL; when given, one further product writes max |(r, s) - M (v, y)| over the N + nb rows of
+ * the returned solution, formed element by element as rhs - product with the product exactly as dto_kkt_border_multiply computes
+ * it.  An instance with a singular Schur complement returns NaN in every solution entry and NaN in resid; the others are not
+ * affected.
+ * State: both need a valid border (dto_kkt_assemble, dto_kkt_factor, dto_kkt_border_factor) -- the product too, that is where G
+ * and C live -- and fail with DTO_ERR_INVALID and the message of dto_kkt_border_solve without one; whatever invalidates the
+ * border (see above) invalidates them.  Errors, in this order: no border; passes outside 0..4; a null vector; a leading dimension
+ * below its row length (nb for v_b / out_b / rhs_b / sol_b) -- all DTO_ERR_INVALID.  A refused call writes nothing.
+ * Results are bit-identical from run to run (no atomic sums) and do not depend on the callers' leading dimensions; padding is
+ * neither read nor written.  The panel is summed in the chunks dto_kkt_border_factor used (DTO_BORDER_GRAM_CHUNK at factor time
+ * sets both).  The calls may be mixed freely with dto_kkt_solve, _solve_multi, _multiply, _solve_refined and _border_solve on one
+ * factorisation; all of those return what they return without them, bit for bit.
+ * Workspace kept with the handle: dto_kkt_border_factor keeps sym(C) (256 doubles per instance) and 16 doubles per chunk and
+ * instance for the partial G v; dto_kkt_border_solve_refined allocates two arrays of B x (N + 16) doubles at its first call with
+ * passes > 0 or resid (the size is reported if that fails); all freed with the handle.  Per path:
+ * - tile path: as above;
+ * - lane-per-instance path: DTO_ERR_UNSUPPORTED ("tile path only": no assembled system is kept there, dto_kkt_multiply is
+ *   unsupported too); nothing is written and the border stays usable. */
+int dto_kkt_border_multiply(dto_problem* p, const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc, const double* v_b,
+                            int64_t ldvb, double* out_x, int64_t ldox, double* out_c, int64_t ldoc, double* out_b, int64_t ldob,
+                            void* stream);
+int dto_kkt_border_solve_refined(dto_problem* p, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
+                                 const double* rhs_b, int64_t ldrb, double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc,
+                                 double* sol_b, int64_t ldsb, double* resid, void* stream);
+
 /* Batched interior-point solve, one independent NLP per instance, same structure, different guesses.
  * x0: DEVICE [B][ldx] initial guesses (what initialize_states!/initialize_controls! set,
  * src/solver.jl:23-39); x_out/mu_out: DEVICE [B][ld*] final accepted iterates (get_trajectory,

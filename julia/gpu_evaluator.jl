@@ -306,6 +306,36 @@ function kkt_border_solve!(ev::GPUEvaluator, nb::Integer, rhs_x::Ptr{Float64}, r
 end
 
 """
+    kkt_border_multiply!(ev, nb, v_x, v_c, v_b, out_x, out_c, out_b)
+    kkt_border_solve_refined!(ev, nb, rhs_x, rhs_c, rhs_b, sol_x, sol_c, sol_b; passes = 2, resid = C_NULL)
+
+The bordered matrix of the last `kkt_border_factor!` as an operator, `[out_x; out_c; out_b] = [K G'; G sym(C)] [v_x; v_c; v_b]`
+(`dto_kkt_border_multiply`), and `dto_kkt_border_solve` followed by `passes` (0..4) rounds of iterative refinement against it
+(`dto_kkt_border_solve_refined`).  Tile path (17..64-state models); DEVICE arrays as for `kkt_border_solve!`, outputs must not
+overlap inputs; `resid` is a DEVICE vector of B doubles that receives max |rhs − M sol| per instance, or `C_NULL`.
+"""
+function kkt_border_multiply!(ev::GPUEvaluator, nb::Integer, v_x::Ptr{Float64}, v_c::Ptr{Float64}, v_b::Ptr{Float64},
+                              out_x::Ptr{Float64}, out_c::Ptr{Float64}, out_b::Ptr{Float64})
+    nz, nc = ev.num_variables, ev.num_constraint
+    dto_check(ccall((:dto_kkt_border_multiply, libdto), Cint,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Int64, Ptr{Cvoid}),
+                    ev.handle, v_x, nz, v_c, nc, v_b, nb, out_x, nz, out_c, nc, out_b, nb, C_NULL))
+    return nothing
+end
+
+function kkt_border_solve_refined!(ev::GPUEvaluator, nb::Integer, rhs_x::Ptr{Float64}, rhs_c::Ptr{Float64}, rhs_b::Ptr{Float64},
+                                   sol_x::Ptr{Float64}, sol_c::Ptr{Float64}, sol_b::Ptr{Float64};
+                                   passes = 2, resid = Ptr{Float64}(C_NULL))
+    nz, nc = ev.num_variables, ev.num_constraint
+    dto_check(ccall((:dto_kkt_border_solve_refined, libdto), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Cvoid}),
+                    ev.handle, passes, rhs_x, nz, rhs_c, nc, rhs_b, nb, sol_x, nz, sol_c, nc, sol_b, nb, resid, C_NULL))
+    return nothing
+end
+
+"""
     set_bounds_batch!(ev, lower, upper)
     set_bounds_batch!(ev, nothing, nothing)
 

@@ -8,7 +8,12 @@ HIP events on the stream, two warm-up rounds, medians of `reps` rounds with the 
     rocprofv3 --kernel-trace --stats, gives the kernels alone);
   * border_solve against a plain dto_kkt_solve on the same right-hand side;
   * parent: nb + 1 dto_kkt_solve calls plus the copy of Y = K^-1 G' to the host (the Schur complement was the host's job), per
-    bordered right-hand side; the border calls amortise the nb solves over every right-hand side that follows."""
+    bordered right-hand side; the border calls amortise the nb solves over every right-hand side that follows;
+  * border_multiply (dto_kkt_border_multiply) against a plain dto_kkt_multiply on the same vector: their difference is k_border_mul
+    + k_border_mul_fin, the one pass over the kept panel -- mul_panel_GBps_at_least = (nb x N doubles per instance) over that
+    difference against the HBM peak;
+  * border_refined1: dto_kkt_border_solve_refined(passes = 1); its excess over border_solve is one refinement pass (product,
+    residual, bordered solve of the residual, update), reported relative to one dto_kkt_border_solve and to one dto_kkt_factor."""
 import json
 import os
 import sys
@@ -44,6 +49,8 @@ RC = torch.randn((B, nc), device="cuda", dtype=torch.float64, generator=g)
 RB = torch.randn((B, nb), device="cuda", dtype=torch.float64, generator=g)
 OX, OC, OB = torch.empty_like(RX), torch.empty_like(RC), torch.empty_like(RB)
 PX, PC = torch.empty_like(RX), torch.empty_like(RC)
+MX, MC, MB = torch.empty_like(RX), torch.empty_like(RC), torch.empty_like(RB)
+KX, KC = torch.empty_like(RX), torch.empty_like(RC)
 
 
 def timed(fn):
@@ -76,7 +83,26 @@ def parent():
     return YX.cpu(), YC.cpu()
 
 
-what = dict(border_factor=border_factor, multi_solve=multi_solve, border_solve=border_solve, plain_solve=plain_solve, parent=parent)
+def border_multiply():
+    s.kkt_border_multiply(RX.data_ptr(), nz, RC.data_ptr(), nc, RB.data_ptr(), nb, MX.data_ptr(), nz, MC.data_ptr(), nc, MB.data_ptr(), nb)
+
+
+def plain_multiply():
+    s.kkt_multiply(RX.data_ptr(), nz, RC.data_ptr(), nc, KX.data_ptr(), nz, KC.data_ptr(), nc)
+
+
+def border_refined1():
+    s.kkt_border_solve_refined(RX.data_ptr(), nz, RC.data_ptr(), nc, RB.data_ptr(), nb, OX.data_ptr(), nz, OC.data_ptr(), nc, OB.data_ptr(), nb, 1)
+
+
+def kkt_factor():
+    s.kkt_factor()
+    border_factor()          # (a new factorisation invalidates the border: put it back, outside the figure -- see factor_s below)
+
+
+what = dict(border_factor=border_factor, multi_solve=multi_solve, border_solve=border_solve, plain_solve=plain_solve, parent=parent,
+            border_multiply=border_multiply, plain_multiply=plain_multiply, border_refined1=border_refined1,
+            factor_and_border_factor=kkt_factor)
 times = {k: [] for k in what}
 for it in range(2 + reps):
     for k, fn in what.items():
@@ -97,4 +123,17 @@ if rest > 0:
     out["gram_fraction_of_hbm_peak_at_least"] = round(gram_bytes / rest / 1e9 / HBM_PEAK_GBPS, 3)
 out["border_solve_over_plain_solve"] = round(out["border_solve_s"] / out["plain_solve_s"], 3)
 out["parent_over_border_solve"] = round(out["parent_s"] / out["border_solve_s"], 2)
+mul_rest = out["border_multiply_s"] - out["plain_multiply_s"]
+panel_bytes = 1.0 * nb * N * 8 * B
+out["mul_minus_plain_mul_s"] = round(mul_rest, 6)
+out["mul_panel_read_GB"] = round(panel_bytes / 1e9, 3)
+if mul_rest > 0:
+    out["mul_panel_GBps_at_least"] = round(panel_bytes / mul_rest / 1e9, 1)
+    out["mul_panel_fraction_of_hbm_peak_at_least"] = round(panel_bytes / mul_rest / 1e9 / HBM_PEAK_GBPS, 3)
+out["factor_s"] = round(out["factor_and_border_factor_s"] - out["border_factor_s"], 6)
+one_pass = out["border_refined1_s"] - out["border_solve_s"]
+out["refine_pass_s"] = round(one_pass, 6)
+out["refine_pass_over_border_solve"] = round(one_pass / out["border_solve_s"], 3)
+if out["factor_s"] > 0:
+    out["refine_pass_over_factor"] = round(one_pass / out["factor_s"], 3)
 print(json.dumps(out), flush=True)
