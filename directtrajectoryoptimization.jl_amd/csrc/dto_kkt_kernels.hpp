@@ -187,6 +187,10 @@ struct dto_kkt_args {
   // slot -> instance map after dto_solver_repack moved the running instances to the front (NULL: identity)
   const int* inst_of_slot;
   int fwd_rounds;  // sequential sweep: inertia-correction rounds per launch (0 = all)
+  // sequential forward sweep: adjacent tiles per wavefront (kkt_fwd_seq_body); 0 or 1: one tile per wavefront.  The launch has
+  // ceil(G / fwd_group) blocks; more than 1 only with fwd_rounds <= 0 and without newton_only (the host's choice, dto_solver.cpp).
+  // (In the four bytes that padded fwd_rounds: no offset and not the size of the block moves.)
+  int fwd_group;
   // time-partitioned form: per tile four arrival counters (chunk sums -> convergence test, chunk sweeps -> separator system, back
   // substitutions -> step partials, merit partials -> step size): the wavefront that arrives LAST does the tile's joining step in
   // the same launch (tile_last_arrival); NULL: one launch per step as in rounds 2-4 (DTO_FUSE_JOIN=0, bit-identical)
@@ -392,6 +396,64 @@ __device__ __forceinline__ SoaBufs::SoaBufs(const dto_kkt_args& a, int64_t g) {
   sigx.bind(a.sigx, g, a.Nz); sigc.bind(a.sigc, g, a.Nc); wt.bind(a.wtile, g, a.Nw);
 }
 
+// The same arrays for a GROUP of adjacent tiles, every lane at a (tile, lane) slot of its own (the sequential forward sweep packs
+// the lanes of its group that still need a factorisation into one wavefront, kkt_fwd_seq_body).  The resource spans the group's
+// tiles; the slot is the vector offset -- source tile x rows of the array x 512 + source lane x 8 (x 16 in the pair-interleaved
+// arrays) -- one VGPR per class of arrays with the same row count instead of the one `8 x lane` of TileBuf.  The hardware's
+// range check covers the vector offset, so the dropped-store offset of TileBuf::st2 works unchanged (the host keeps a group's
+// rows below 2 GiB).
+struct SlotBuf {
+  __amdgpu_buffer_rsrc_t r;
+  unsigned vo;
+  __device__ __forceinline__ void bind(const double* base, int64_t tile0, int64_t rows, int ntiles) {
+    const int64_t bytes = base ? ntiles * rows * 512 : 0;
+    r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base + ((tile0 * rows) << 6)), 0, (int)bytes, 0x00020000);
+    vo = 0;
+  }
+  __device__ __forceinline__ double ld(int row) const {
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo, row << 9, 0));
+  }
+  __device__ __forceinline__ void st(int row, double v) const {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(dto_v2i, v), r, vo, row << 9, 0);
+  }
+  __device__ __forceinline__ void ld2(int row0, int k, double& v0, double& v1) const {
+    const dto_v4i q = __builtin_amdgcn_raw_buffer_load_b128(r, vo, (row0 << 9) + (k << 10), 0);
+    v0 = __builtin_bit_cast(double, dto_v2i{q[0], q[1]});
+    v1 = __builtin_bit_cast(double, dto_v2i{q[2], q[3]});
+  }
+  __device__ __forceinline__ void st2(int row0, int k, double v0, double v1, bool on) const {
+    const dto_v2i a0 = __builtin_bit_cast(dto_v2i, v0), a1 = __builtin_bit_cast(dto_v2i, v1);
+    __builtin_amdgcn_raw_buffer_store_b128(dto_v4i{a0[0], a0[1], a1[0], a1[1]}, r, on ? vo : 0x80000000u, (row0 << 9) + (k << 10), 0);
+  }
+  __device__ __forceinline__ double ld1p(int row0, int i) const {
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo + (i & 1) * 8u, (row0 << 9) + ((i >> 1) << 10), 0));
+  }
+  __device__ __forceinline__ void st1p(int row0, int i, double v, bool on) const {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(dto_v2i, v), r, on ? vo + (i & 1) * 8u : 0x80000000u,
+                                          (row0 << 9) + ((i >> 1) << 10), 0);
+  }
+};
+struct SlotBufs {
+  SlotBuf z, lam, zl, zu, s, zs, dz, dlam, ds, rec, fac, sigx, sigc, wt;
+  __device__ __forceinline__ SlotBufs(const dto_kkt_args& a, int64_t g0, int ntiles) {
+    z.bind(a.z, g0, a.Nz, ntiles); lam.bind(a.lam, g0, a.Nc, ntiles); zl.bind(a.zl, g0, a.Nz, ntiles); zu.bind(a.zu, g0, a.Nz, ntiles);
+    s.bind(a.s, g0, a.Ni, ntiles); zs.bind(a.zs, g0, a.Ni, ntiles); dz.bind(a.dz, g0, a.Nz, ntiles);
+    dlam.bind(a.dlam, g0, a.Nc, ntiles); ds.bind(a.ds, g0, a.Ni, ntiles);
+    rec.bind(a.rec, g0, a.rec_total, ntiles); fac.bind(a.fac, g0, a.fac_total, ntiles);
+    sigx.bind(a.sigx, g0, a.Nz, ntiles); sigc.bind(a.sigc, g0, a.Nc, ntiles); wt.bind(a.wtile, g0, a.Nw, ntiles);
+  }
+  // this lane works on lane `lane` of the group's tile `tig`
+  __device__ __forceinline__ void slot(const dto_kkt_args& a, int tig, int lane) {
+    const unsigned t512 = (unsigned)tig * 512u, l8 = (unsigned)lane * 8u;
+    z.vo = zl.vo = zu.vo = sigx.vo = dz.vo = t512 * (unsigned)a.Nz + l8;
+    lam.vo = sigc.vo = dlam.vo = t512 * (unsigned)a.Nc + l8;
+    s.vo = zs.vo = ds.vo = t512 * (unsigned)a.Ni + l8;
+    wt.vo = t512 * (unsigned)a.Nw + l8;
+    rec.vo = t512 * (unsigned)a.rec_total + 2u * l8;
+    fac.vo = t512 * (unsigned)a.fac_total + 2u * l8;
+  }
+};
+
 // parameters w_t of stage t: shared by all instances (the reference's one `parameters` vector, src/solver.jl:10), or one
 // set per instance (dto_batch.params: MPC rollouts that differ in initial state / target)
 template <int N>
@@ -486,18 +548,84 @@ struct SoaIO {
   }
 };
 
+// What stage_factor / stage_forward read and write through SoaIO, for a lane that works on the slot (tile g, lane `lane`) of
+// its own choice instead of (the block's tile, threadIdx.x): the out-of-line end stages of the sequential forward sweep, whose
+// wavefront serves the packed lanes of a group of tiles (kkt_fwd_seq_body).  Plain pointer arithmetic per lane: cold code.
+template <class M, int K>
+struct SoaSlotIO {
+  using D = KindDims<M, K>;
+  const dto_kkt_args& a;
+  const int64_t g;
+  const int lane, t, z0;
+  const double* recp;
+  double* facp;
+  __device__ __forceinline__ SoaSlotIO(const dto_kkt_args& a_, int64_t g_, int lane_, int t_)
+      : a(a_), g(g_), lane(lane_), t(t_), z0(uload(a_.zoff, t_)),
+        recp(a_.rec + ((g_ * a_.rec_total + uload(a_.recoff, t_)) << 6) + 2 * lane_),
+        facp(a_.fac + ((g_ * a_.fac_total + uload(a_.facoff, t_)) << 6) + 2 * lane_) {}
+  __device__ __forceinline__ const double* at(const double* base, int64_t n, int64_t i) const { return base + ((g * n + i) << 6) + lane; }
+  __device__ __forceinline__ double rec(int e) const { return recp[pair_at(e)]; }
+  __device__ __forceinline__ double p(int i) const { return *at(a.z, a.Nz, z0 + i); }
+  __device__ __forceinline__ double y(int i) const { return *at(a.z, a.Nz, uload(a.zoff, t + 1) + i); }
+  __device__ __forceinline__ double lam(int k) const { return *at(a.lam, a.Nc, uload(a.cdoff, t) + k); }
+  __device__ __forceinline__ double nu(int j) const { return *at(a.lam, a.Nc, uload(a.ccoff, t) + j); }
+  template <int N>
+  __device__ __forceinline__ void params(arr<N>& w) const {
+    const int w0 = uload(a.woff, t);
+    if (a.wtile) {
+#pragma unroll
+      for (int i = 0; i < N; ++i) w[i] = *at(a.wtile, a.Nw, w0 + i);
+    } else {
+#pragma unroll
+      for (int i = 0; i < N; ++i) w[i] = uload(a.params, w0 + i);
+    }
+  }
+  __device__ __forceinline__ void bounds(StageBounds<D::NP>& b) const {
+    const bool duals = a.zl != nullptr;   // as load_stage_bounds
+#pragma unroll
+    for (int i = 0; i < D::NP; ++i) {
+      b.lo[i] = uload(a.lo, z0 + i);
+      b.hi[i] = uload(a.hi, z0 + i);
+      b.p[i] = duals ? *at(a.z, a.Nz, z0 + i) : 0.0;
+      b.zl[i] = duals ? *at(a.zl, a.Nz, z0 + i) : 0.0;
+      b.zu[i] = duals ? *at(a.zu, a.Nz, z0 + i) : 0.0;
+    }
+  }
+  __device__ __forceinline__ bool has_sigx() const { return a.sigx != nullptr; }
+  __device__ __forceinline__ bool has_sigc() const { return a.sigc != nullptr; }
+  __device__ __forceinline__ double sigx(int i) const { return *at(a.sigx, a.Nz, z0 + i); }
+  __device__ __forceinline__ double sigc_con(int j) const { return *at(a.sigc, a.Nc, uload(a.ccoff, t) + j); }
+  __device__ __forceinline__ double sigc_dyn(int k) const { return *at(a.sigc, a.Nc, uload(a.cdoff, t) + k); }
+  __device__ __forceinline__ double slack(int j) const { return *at(a.s, a.Ni, uload(a.ioff, t) + D::slack(j)); }
+  __device__ __forceinline__ double slack_mult(int j) const { return *at(a.zs, a.Ni, uload(a.ioff, t) + D::slack(j)); }
+  static constexpr bool PAIR_CARRY = true;
+  __device__ __forceinline__ void put_carry(int i, double v, bool on = true) const { if (on) facp[((int64_t)(i >> 1) << 7) + (i & 1)] = v; }
+  __device__ __forceinline__ void put_carry2(int i, double v0, double v1, bool on) const {
+    if (on) *reinterpret_cast<double2*>(facp + ((int64_t)(i >> 1) << 7)) = double2{v0, v1};
+  }
+  __device__ __forceinline__ long long* prof() const {
+#if DTO_KKT_PROFILE == 2
+    return a.prof;
+#elif DTO_KKT_PROFILE
+    return (a.prof && blockIdx.x == 1 && threadIdx.x == 0) ? a.prof : nullptr;
+#else
+    return nullptr;   // (see SoaIO::prof)
+#endif
+  }
+};
+
 // SoaIO for a stage inside a run (dto_stage_run): every offset is arithmetic -- offset of the run's first stage + stride x
 // position -- so nothing has to be looked up before the stage's rows can be requested.  Measured background (profiles/r03):
 // with look-ups, a stage of the sweeps began with a chain of dependent memory round trips (kind -> offsets -> rows) that no
 // other instruction of the wavefront could overlap; a wavefront sat in s_waitcnt for 58 % of its cycles.  BOUNDED = false:
 // the run has no fixed variable and no finite bound, the bound tests of the block algebra fold away at compile time.
-template <class M, int K, bool BOUNDED>
+template <class M, int K, bool BOUNDED, class B = SoaBufs>
 struct SoaRunIO {
   using D = KindDims<M, K>;
   const dto_kkt_args& a;
-  const SoaBufs& b;
+  const B& b;
   const int t, z0, cd0, cc0, io0, w0, rec0, fac0;
-  __device__ __forceinline__ SoaRunIO(const dto_kkt_args& a_, const SoaBufs& b_, const dto_stage_run& r, int t_)
+  __device__ __forceinline__ SoaRunIO(const dto_kkt_args& a_, const B& b_, const dto_stage_run& r, int t_)
       : a(a_), b(b_), t(t_), z0(r.z0 + (t_ - r.t0) * r.zs), cd0(r.cd0 + (t_ - r.t0) * r.cds), cc0(r.cc0 + (t_ - r.t0) * r.ccs),
         io0(r.io0 + (t_ - r.t0) * r.ios), w0(r.w0 + (t_ - r.t0) * r.ws), rec0((int)r.rec0 + (t_ - r.t0) * (int)r.recs),
         fac0((int)r.fac0 + (t_ - r.t0) * (int)r.facs) {}
@@ -598,7 +726,8 @@ struct StageIn {
   double rec[D::REC > 0 ? D::REC : 1], p[HAS_P && NP > 0 ? NP : 1], y[D::FUSED && NY > 0 ? NY : 1], lam[NY > 0 ? NY : 1],
       nu[Q > 0 ? Q : 1], zl[BOUNDED && NP > 0 ? NP : 1], zu[BOUNDED && NP > 0 ? NP : 1], s[Q > 0 ? Q : 1], zs[Q > 0 ? Q : 1],
       car[NCAR > 0 ? NCAR : 1];
-  __device__ __forceinline__ void load(const SoaBufs& b, const dto_stage_run& r, int t) {
+  template <class B>
+  __device__ __forceinline__ void load(const B& b, const dto_stage_run& r, int t) {
     const int n = t - r.t0;
     const int z0 = r.z0 + n * r.zs, cd0 = r.cd0 + n * r.cds, cc0 = r.cc0 + n * r.ccs, io0 = r.io0 + n * r.ios;
     const int rec0 = (int)r.rec0 + n * (int)r.recs, fac0 = (int)r.fac0 + n * (int)r.facs;
@@ -637,13 +766,13 @@ struct StageIn {
 };
 
 // SoaRunIO whose reads come out of a StageIn (writes, the linear-solver extras and the parameters stay direct)
-template <class M, int K, bool BOUNDED, bool BWD, bool SPK = false>
-struct SoaPreIO : SoaRunIO<M, K, BOUNDED> {
-  using Base = SoaRunIO<M, K, BOUNDED>;
+template <class M, int K, bool BOUNDED, bool BWD, bool SPK = false, class B = SoaBufs>
+struct SoaPreIO : SoaRunIO<M, K, BOUNDED, B> {
+  using Base = SoaRunIO<M, K, BOUNDED, B>;
   using D = KindDims<M, K>;
   using In = StageIn<M, K, BOUNDED, BWD, SPK>;
   const In& in;
-  __device__ __forceinline__ SoaPreIO(const dto_kkt_args& a_, const SoaBufs& b_, const dto_stage_run& r, int t_, const In& in_)
+  __device__ __forceinline__ SoaPreIO(const dto_kkt_args& a_, const B& b_, const dto_stage_run& r, int t_, const In& in_)
       : Base(a_, b_, r, t_), in(in_) {}
   __device__ __forceinline__ double rec(int e) const { return in.rec[e]; }
   __device__ __forceinline__ double p(int i) const { return in.p[i]; }
@@ -2096,12 +2225,12 @@ constexpr bool heavy_kind() {
   return D::BD * (D::BD + 1) / 2 + D::BD * D::NY > 100;
 }
 template <class M, int K, bool SPK>
-__device__ __attribute__((noinline)) void stage_forward_cold(const dto_kkt_args& a, int64_t g, int t, double mu, double dw, double gam,
-                                                            bool first, bool need, Carry<M>* cy, Spike<M>* sp, int* okneg) {
+__device__ __attribute__((noinline)) void stage_forward_cold(const dto_kkt_args& a, int64_t g, int lane, int t, double mu, double dw,
+                                                            double gam, bool first, bool need, Carry<M>* cy, Spike<M>* sp, int* okneg) {
   bool ok = okneg[0] != 0;
   int nneg = okneg[1];
   const bool keep_lost = okneg[2] != 0;
-  stage_forward<M, K, SPK>(a.opt, SoaIO<M, K>(a, g, t), mu, dw, gam, first, need, *cy, *sp, ok, nneg, keep_lost);
+  stage_forward<M, K, SPK>(a.opt, SoaSlotIO<M, K>(a, g, lane, t), mu, dw, gam, first, need, *cy, *sp, ok, nneg, keep_lost);
   okneg[0] = ok ? 1 : 0;
   okneg[1] = nneg;
 }
@@ -2155,17 +2284,145 @@ __device__ __forceinline__ void retry_update(const dto_kkt_args& a, double* sc, 
   retry_update_t<6>(a.opt, (int)a.Nc, sc, ok, nneg);
 }
 
-// CHUNKED = false: the plain sequential sweep (P = 1) without any spike code -- a separate instantiation because the
-// spike blocks are what pushes the register count of the chunked form beyond one wavefront per SIMD
+// position of the n-th set bit of m (n < popcount(m))
+__device__ __forceinline__ int nth_set_bit(unsigned long long m, int n) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) {
+    const int c = __popcll((m >> pos) & ((1ull << w) - 1ull));
+    if (n >= c) { n -= c; pos += w; }
+  }
+  return pos;
+}
+
+// The plain sequential sweep (P = 1) without any spike code -- its own body because the spike blocks are what pushes the
+// register count of the chunked form beyond one wavefront per SIMD.
+// The wavefront owns its tiles for the whole inertia-correction loop: sweep, judge the inertia, pick the next (delta_w, gamma)
+// and sweep again until every lane has a factorisation -- no launch per round.  Block b owns the a.fwd_group adjacent tiles
+// from b * fwd_group on.  With one tile every round runs on the tile as it lies.  With more, the first round of every tile runs
+// in turn with the lanes where they are; the retry rounds then run ONCE FOR THE GROUP: the lanes of all its tiles that still
+// need a factorisation, in (tile, lane) order, are handed to the 64 physical lanes (ballot / popcount / n-th set bit: no LDS,
+// no barrier, no other wavefront involved), those beyond 64 in the next pass.  A retry round of a tile occupies a wavefront for a
+// whole sweep with about a fifth of its lanes doing anything; packed, the group pays one such round per 64 needing lanes.
+// Every quantity of an attempt is per lane (SC_TRY_*, SC_ATTEMPT, ok, nneg, keep_lost, the carries), so what an instance
+// computes does not depend on the physical lane that runs it: results are bit for bit those of one tile per wavefront.
+// ONE stage loop serves all of it: the lane's slot is a vector offset into resources that span the group (SlotBufs).
+template <class M>
+__device__ __forceinline__ void kkt_fwd_seq_body(const dto_kkt_args& a) {
+  const int k = a.fwd_group > 1 ? a.fwd_group : 1;
+  const int g0 = (int)blockIdx.x * k;
+  const int kt = min(k, a.G - g0);
+  if (kt <= 0) return;
+  SlotBufs bufs(a, g0, kt);
+  for (int pass = 0; a.fwd_rounds <= 0 || pass < a.fwd_rounds; ++pass) {
+    int tig = 0, lane = threadIdx.x;   // this lane's slot of the pass: tile inside the group, lane of that tile
+    bool mine = true;
+    if (k > 1) {
+      if (pass < kt) {
+        tig = pass;
+      } else {
+        mine = false;   // (a lane without a needing slot sweeps its own slot of the first tile with need = false)
+        int base = 0;
+        for (int j = 0; j < kt && base < WAVE; ++j) {
+          const double* scj = a.scal + (((int64_t)(g0 + j) * SC_COUNT) << 6) + threadIdx.x;
+          const unsigned long long m = __ballot(scj[SC_STATUS << 6] == 0.0 && scj[SC_NEED << 6] != 0.0);
+          const int c = __popcll(m), n = (int)threadIdx.x - base;
+          if (n >= 0 && n < c) {
+            tig = j;
+            lane = nth_set_bit(m, n);
+            mine = true;
+          }
+          base += c;
+        }
+        if (base == 0) return;
+      }
+    }
+    const int64_t g = g0 + tig;
+    double* sc = a.scal + ((g * SC_COUNT) << 6) + lane;
+    const bool need = mine && sc[SC_STATUS << 6] == 0.0 && sc[SC_NEED << 6] != 0.0;
+    if (!__any(need)) {
+      if (k > 1) continue;   // (first rounds: on to the group's next tile)
+      return;
+    }
+    bufs.slot(a, tig, lane);
+    const double mu = sc[SC_MU << 6];
+    // (limited-memory mode: the diagonal sigma I of B_0 rides on the primal regularisation)
+    const double dw = sc[SC_TRY_DW << 6] + (DTO_QN_HOT && a.opt.qn_lbfgs ? sc[SC_QN_SIGMA << 6] : 0.0), gam = sc[SC_TRY_GAM << 6];
+    Carry<M> cy;
+    Spike<M> sp;
+#pragma unroll
+    for (int i = 0; i < M::MAX_NX * (M::MAX_NX + 1) / 2; ++i) cy.P[i] = sp.RLL[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < M::MAX_NX; ++i) cy.py[i] = sp.rL[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < M::MAX_NX * M::MAX_NX; ++i) sp.Cx[i] = 0.0;
+    bool ok = true;
+    int nneg = 0;
+    // the attempt after which retry_update stops whatever the inertia: its factorisation is the one that gets used
+    const bool keep_lost = DTO_NEWTON(a.opt) || (int)sc[SC_ATTEMPT << 6] >= a.opt.max_refactor;
+    // walk the horizon run by run: kind dispatch and table look-ups once per run, arithmetic offsets inside
+    bool lost = false;
+    for (int r = 0; r < a.n_runs && !lost; ++r) {
+      const dto_stage_run run = load_run(a.runs, r);
+      dispatch_uniform<M>(run.kind, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        if constexpr (heavy_kind<M, K>()) {
+          for (int t = run.t0; t < run.t1; ++t) {
+            Carry<M> cyc = cy;
+            Spike<M> spc = sp;
+            int okneg[3] = {ok ? 1 : 0, nneg, keep_lost ? 1 : 0};
+            // the callee gets its own copy of the argument block: handing out the address of the kernel's would move every
+            // pointer of the hot loop to the stack as well (reloads, generic instead of global addressing)
+            const dto_kkt_args acold = a;
+            stage_forward_cold<M, K, false>(acold, g, lane, t, mu, dw, gam, false, need, &cyc, &spc, okneg);
+            cy = cyc;
+            ok = okneg[0] != 0;
+            nneg = okneg[1];
+            if (!__any(need && (ok || keep_lost))) { lost = true; break; }
+          }
+        } else {
+          auto sweep = [&](auto bounded) {
+            using IO = SoaPreIO<M, K, decltype(bounded)::value, false, false, SlotBufs>;
+            // (stages with long records -- quasi-Newton blocks, stored derivatives -- are not double-buffered: twice their
+            // rows do not fit the register file next to the block algebra)
+            constexpr bool PRE = DTO_SEQ_PREFETCH_FWD && sizeof(typename IO::In) <= DTO_SEQ_PREFETCH_MAX * sizeof(double);
+            typename IO::In nxt, cur;
+            if (PRE) nxt.load(bufs, run, run.t0);
+            for (int t = run.t0; t < run.t1; ++t) {
+              if (PRE) {
+                cur = nxt;
+                nxt.load(bufs, run, min(t + 1, run.t1 - 1));   // in flight while stage t is worked on
+              } else {
+                cur.load(bufs, run, t);
+              }
+              stage_forward<M, K, false>(a.opt, IO(a, bufs, run, t, cur), mu, dw, gam, false, need, cy, sp, ok, nneg, keep_lost);
+              // the attempt of a lane is lost with the first stage whose pivots have the wrong signs (stage_forward clears
+              // ok): once that has happened to every lane that asked for a factorisation the rest of the sweep is pointless
+              if (!__any(need && (ok || keep_lost))) { lost = true; break; }
+            }
+          };
+          if (run.bounded) sweep(std::integral_constant<bool, true>{}); else sweep(std::integral_constant<bool, false>{});
+        }
+      });
+    }
+    if (need) retry_update(a, sc, ok, nneg);
+    if (a.opt.newton_only) return;  // one factorisation with the caller's delta_w
+    // the next pass reads the verdicts, and may rewrite the carries, through other lanes of this wavefront
+    if (k > 1) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  }
+}
+
+// CHUNKED = true: one round of the time-partitioned form per launch (k_kkt_sep joins its chunks in between).  CHUNKED = false:
+// the plain sequential sweep, kkt_fwd_seq_body.
 template <class M, bool CHUNKED>
 __device__ __forceinline__ void kkt_fwd_body(const dto_kkt_args& a) {
+  if constexpr (!CHUNKED) {
+    kkt_fwd_seq_body<M>(a);
+  } else {
   const int64_t g = blockIdx.x / a.P;
   const int p = blockIdx.x % a.P;
   double* sc = a.scal + ((g * SC_COUNT) << 6) + threadIdx.x;
-  // The sequential form owns its tile for the whole inertia-correction loop: sweep, judge the inertia, pick the next
-  // (delta_w, gamma) and sweep again until every lane of the tile has a factorisation -- no launch per round.  The
-  // time-partitioned form does one round per launch (k_kkt_sep joins its chunks in between).
-  for (int round = 0; CHUNKED || a.fwd_rounds <= 0 || round < a.fwd_rounds; ++round) {
+  {
     const bool need = sc[SC_STATUS << 6] == 0.0 && sc[SC_NEED << 6] != 0.0;
     if (!__any(need)) return;
     const double mu = sc[SC_MU << 6];
@@ -2184,54 +2441,7 @@ __device__ __forceinline__ void kkt_fwd_body(const dto_kkt_args& a) {
     int nneg = 0;
     // the attempt after which retry_update stops whatever the inertia: its factorisation is the one that gets used
     const bool keep_lost = DTO_NEWTON(a.opt) || (int)sc[SC_ATTEMPT << 6] >= a.opt.max_refactor;
-    if constexpr (!CHUNKED) {
-      // walk the horizon run by run: kind dispatch and table look-ups once per run, arithmetic offsets inside
-      const SoaBufs bufs(a, g);
-      bool lost = false;
-      for (int r = 0; r < a.n_runs && !lost; ++r) {
-        const dto_stage_run run = load_run(a.runs, r);
-        dispatch_uniform<M>(run.kind, [&](auto kc) {
-          constexpr int K = decltype(kc)::value;
-          if constexpr (heavy_kind<M, K>()) {
-            for (int t = run.t0; t < run.t1; ++t) {
-              Carry<M> cyc = cy;
-              Spike<M> spc = sp;
-              int okneg[3] = {ok ? 1 : 0, nneg, keep_lost ? 1 : 0};
-              // the callee gets its own copy of the argument block: handing out the address of the kernel's would move every
-              // pointer of the hot loop to the stack as well (reloads, generic instead of global addressing)
-              const dto_kkt_args acold = a;
-              stage_forward_cold<M, K, false>(acold, g, t, mu, dw, gam, false, need, &cyc, &spc, okneg);
-              cy = cyc;
-              ok = okneg[0] != 0;
-              nneg = okneg[1];
-              if (!__any(need && (ok || keep_lost))) { lost = true; break; }
-            }
-          } else {
-            auto sweep = [&](auto bounded) {
-              using IO = SoaPreIO<M, K, decltype(bounded)::value, false>;
-              // (stages with long records -- quasi-Newton blocks, stored derivatives -- are not double-buffered: twice their
-              // rows do not fit the register file next to the block algebra)
-              constexpr bool PRE = DTO_SEQ_PREFETCH_FWD && sizeof(typename IO::In) <= DTO_SEQ_PREFETCH_MAX * sizeof(double);
-              typename IO::In nxt, cur;
-              if (PRE) nxt.load(bufs, run, run.t0);
-              for (int t = run.t0; t < run.t1; ++t) {
-                if (PRE) {
-                  cur = nxt;
-                  nxt.load(bufs, run, min(t + 1, run.t1 - 1));   // in flight while stage t is worked on
-                } else {
-                  cur.load(bufs, run, t);
-                }
-                stage_forward<M, K, false>(a.opt, IO(a, bufs, run, t, cur), mu, dw, gam, false, need, cy, sp, ok, nneg, keep_lost);
-                // the attempt of a lane is lost with the first stage whose pivots have the wrong signs (stage_forward clears
-                // ok): once that has happened to every lane that asked for a factorisation the rest of the sweep is pointless
-                if (!__any(need && (ok || keep_lost))) { lost = true; break; }
-              }
-            };
-            if (run.bounded) sweep(std::integral_constant<bool, true>{}); else sweep(std::integral_constant<bool, false>{});
-          }
-        });
-      }
-    } else {
+    {
 #if DTO_CHUNK_PREFETCH
     // the chunk's stages run by run, as the sequential form walks the horizon: offsets by arithmetic, the rows of the next stage
     // requested before the arithmetic of this one (a chunk sweep is one dependent chain per lane like the sequential one; until
@@ -2287,10 +2497,7 @@ __device__ __forceinline__ void kkt_fwd_body(const dto_kkt_args& a) {
     }
 #endif
     }
-    if constexpr (!CHUNKED) {
-      if (need) retry_update(a, sc, ok, nneg);
-      if (a.opt.newton_only) return;  // one factorisation with the caller's delta_w
-    } else {
+    {
       if (!need) return;
       using CS = ChunkSum<M>;
       double* cs = a.csum + (((g * a.P + p) * CS::SIZE) << 6) + threadIdx.x;
@@ -2311,6 +2518,7 @@ __device__ __forceinline__ void kkt_fwd_body(const dto_kkt_args& a) {
       return;
     }
   }
+  }
 }
 
 template <class M>
@@ -2322,9 +2530,11 @@ __global__ __launch_bounds__(WAVE, DTO_SEQ_FWD_OCC) void k_kkt_fwd_seq(dto_kkt_a
   if (a.fwd_started && threadIdx.x == 0) atomicAdd(a.fwd_started, 1);
   kkt_fwd_body<M, false>(a);
   if (a.tile_fwd_tag) {
-    // this tile's factorisation is complete: tell the early back substitutions (k_kkt_bwd_early, other stream)
+    // the factorisations of this block's tiles are complete: tell the early back substitutions (k_kkt_bwd_early, other stream)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    if (threadIdx.x == 0) __hip_atomic_store(a.tile_fwd_tag + blockIdx.x, a.sweep_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int k = a.fwd_group > 1 ? a.fwd_group : 1, g0 = (int)blockIdx.x * k;
+    if ((int)threadIdx.x < k && g0 + (int)threadIdx.x < a.G)
+      __hip_atomic_store(a.tile_fwd_tag + g0 + threadIdx.x, a.sweep_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -3001,9 +3211,14 @@ __global__ __launch_bounds__(WAVE, 1) void k_kkt_fwdbwd_seq(dto_kkt_args a) {
 // weight the arbitration: without the gate the forward launch got 9 ms longer).  One wavefront in front of it on the second
 // stream: returns when every forward block has started -- from then on free slots are slots the forward launch cannot use.
 // Bounded (~0.3 s), one slot of 1 024.
+// blocks of a sequential forward launch: one per group of a.fwd_group tiles
+__host__ __device__ inline int fwd_seq_blocks(const dto_kkt_args& a) {
+  const int k = a.fwd_group > 1 ? a.fwd_group : 1;
+  return (a.G + k - 1) / k;
+}
 static __global__ __launch_bounds__(WAVE) void k_kkt_bwd_gate(dto_kkt_args a) {
   for (int spin = 0; spin < 100000; ++spin) {
-    if (__hip_atomic_load(a.fwd_started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= a.G) return;
+    if (__hip_atomic_load(a.fwd_started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= fwd_seq_blocks(a)) return;
     __builtin_amdgcn_s_sleep(127);
   }
 }
@@ -4217,7 +4432,7 @@ int launch_kkt(int op, const dto_kkt_args* args, void* stream_) {
           if (per == rounds) { hipLaunchKernelGGL(k_kkt_fwdbwd_seq<M>, dim3(gp), dim3(WAVE), 0, st, a); } else
 #endif
           {
-          for (int r = 0; r < rounds; r += per) hipLaunchKernelGGL(k_kkt_fwd_seq<M>, dim3(gp), dim3(WAVE), 0, st, a);
+          for (int r = 0; r < rounds; r += per) hipLaunchKernelGGL(k_kkt_fwd_seq<M>, dim3((unsigned)fwd_seq_blocks(a)), dim3(WAVE), 0, st, a);
           hipLaunchKernelGGL(k_kkt_bwd_seq<M>, dim3(gp), dim3(WAVE), 0, st, a);
           }
         }
@@ -4226,7 +4441,7 @@ int launch_kkt(int op, const dto_kkt_args* args, void* stream_) {
       }
       case DTO_KKT_FWD:
         if (a.P > 1) hipLaunchKernelGGL(k_kkt_fwd<M>, dim3((unsigned)((int64_t)a.G * a.P)), dim3(WAVE), 0, st, a);
-        else hipLaunchKernelGGL(k_kkt_fwd_seq<M>, dim3((unsigned)((int64_t)a.G * a.P)), dim3(WAVE), 0, st, a);
+        else hipLaunchKernelGGL(k_kkt_fwd_seq<M>, dim3((unsigned)fwd_seq_blocks(a)), dim3(WAVE), 0, st, a);
         break;
       case DTO_KKT_SEP: hipLaunchKernelGGL(k_kkt_sep<M>, dim3((unsigned)a.G), dim3(WAVE), 0, st, a); break;
       case DTO_KKT_BWD:

@@ -1465,7 +1465,35 @@ static bool fused_update_available(Problem* p) {
   return true;
 }
 
+// Adjacent tiles per wavefront of the sequential forward sweep (csrc/dto_kkt_kernels.hpp: kkt_fwd_seq_body): the retry rounds
+// of a group run on its packed needing lanes.  Only where the tiles outnumber the wavefront slots (one wavefront per SIMD)
+// several times over: k = tiles / (4 x compute units), at most DTO_FWD_GROUP_MAX -- below that every tile has a slot of its own
+// and grouping would only remove parallelism (65 536 instances, the tail of a full solve).  DTO_FWD_GROUP=1 forces one tile
+// per wavefront, n > 1 groups of n whatever the batch (read at every call: tests flip it).  One tile per wavefront whenever a
+// launch does not run all its rounds (DTO_FWD_ROUNDS) and for the single factorisation of the linear-solver entry points.
+#ifndef DTO_FWD_GROUP_MAX
+#define DTO_FWD_GROUP_MAX 4
+#endif
+static int fwd_group_for(Problem* p, const dto_kkt_args& a) {
+  const SolverState& S = *p->solver;
+  if (a.P != 1 || a.fwd_rounds > 0 || a.opt.newton_only || a.G < 2) return 1;
+  int k = (int)std::min<int64_t>(DTO_FWD_GROUP_MAX, (int64_t)a.G / std::max(1, S.n_simd));
+  if (const char* e = getenv("DTO_FWD_GROUP")) { const int v = atoi(e); if (v >= 1) k = std::min(v, 64); }
+  // a group's rows of every array stay below 2 GiB: the sweep addresses them with 32-bit offsets inside one buffer resource
+  const int64_t rows = std::max<int64_t>({a.Nz, a.Nc, a.Ni, a.Nw, a.rec_total, a.fac_total, 1});
+  k = (int)std::min<int64_t>(k, (((int64_t)1 << 31) - 1) / (rows * 512));
+  return std::max(1, std::min(k, a.G));
+}
+
 static int kkt_launch(Problem* p, int op, const dto_kkt_args& a, hipStream_t st) {
+  if ((op == DTO_KKT_FWD || op == DTO_KKT_FACTOR_SOLVE || op == DTO_KKT_BWD_GATE) && a.fwd_group == 0 && p->solver) {
+    const int k = fwd_group_for(p, a);
+    if (k > 1) {
+      dto_kkt_args b = a;
+      b.fwd_group = k;
+      return kkt_launch(p, op, b, st);
+    }
+  }
   LaunchTrace* tr = (p->trace && p->trace->on && p->trace->recs.size() < LaunchTrace::MAX_RECS) ? p->trace : nullptr;
   int e0 = -1, e1 = -1;
   if (tr) {

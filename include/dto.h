@@ -448,7 +448,9 @@ int dto_solver_stats(dto_problem* p, int32_t* status, int32_t* iterations, doubl
  * number of times between calls that touch finished tiles) so a caller can time it with events on `stream`.
  * dto_solver_iterate itself runs UPDATE_EVAL wherever it can and, for batches of more than 1 024 tiles (65 536 instances), the
  * back substitutions of finished tiles on a second low-priority stream next to the forward launch (joined before it
- * returns to the caller's stream order); both bit-identical to the plain sequence (DTO_FUSE_UPDATE=0, DTO_OVERLAP_SWEEPS=0). */
+ * returns to the caller's stream order); both bit-identical to the plain sequence (DTO_FUSE_UPDATE=0, DTO_OVERLAP_SWEEPS=0).
+ * From 2 048 tiles on (256 compute units) the sequential forward sweep gives a wavefront a group of up to four adjacent tiles and runs their
+ * inertia-correction rounds on the packed lanes that need one; bit-identical to one tile per wavefront (DTO_FWD_GROUP=1). */
 int dto_solver_launch_op(dto_problem* p, int op, void* stream);
 /* chunks of the time-partitioned block-tridiagonal factorisation: 0 = chosen from the batch size so that
  * tiles x chunks fills the GPU's SIMDs; 1 = plain sequential sweep.  Takes effect at the next begin/step. */
