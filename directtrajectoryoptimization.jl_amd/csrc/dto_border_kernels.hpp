@@ -294,6 +294,56 @@ static __global__ __launch_bounds__(64) void k_border_mul_fin(int nb, int chunks
   out_b[b * ldob + j] = acc;
 }
 
+// ---- the bordered step of the solver on the tile path (dto_solver.cpp: bordered_step_tile): everything dto_kkt_border_factor /
+//      dto_kkt_border_solve are given, from the derivatives at the point.  One thread per (instance, column) -- a thread owns
+//      column `col` of instance b in r_x, rhs_x and all ng panel rows, so nothing is summed across threads:
+//          r_x = grad f + J' mu (entries of a column in COO order, as k_border_rx),  rhs_x = -r_x
+//          panel row b * ng + j = row j of the general rows' Jacobian, Nz entries, EVERY one written (zeros included)
+//      and, on the first threads of the same grid (B * Ns < B * Nz: a dynamics row per state),
+//          rhs_c = -c on the Ns stage-part rows (pitch Nc),  rhs_b = -(c_g + gshift),  C = -(delta_c + gdiag) I as [B][ng * ng]
+//      pin (with fixed[col]): the variable keeps its value -- its column of the panel and its entry of rhs_x are zero (the factor
+//      holds 1e16 on its diagonal).  J is indexed through the CSC tables of the constant pattern
+//      (cptr [Nz + 1], ck: position in the COO value array, crow: 0-based row).
+static __global__ void k_border_point(int64_t B, int64_t Nz, int64_t Nc, int64_t Ns, int ng, int64_t nnzJ, const double* J, const double* g,
+                                      const double* c, const double* mu, int64_t ldmu, const int* cptr, const int* ck, const int* crow,
+                                      const int* fixed, int pin, double delta_c, const double* gdiag, const double* gshift, double* rx,
+                                      double* rhsx, double* panel, double* rhsc, double* rhsb, double* cblk) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < B * Ns) {
+    const int64_t b = idx / Ns, k = idx - b * Ns;
+    rhsc[b * Nc + k] = -c[b * Nc + k];
+  }
+  if (idx < B * ng * ng) {
+    const int64_t b = idx / (ng * ng);
+    const int e = (int)(idx - b * ng * ng), a = e / ng, q = e - a * ng;
+    cblk[idx] = a == q ? -(delta_c + (gdiag ? gdiag[b * ng + a] : 0.0)) : 0.0;
+    if (q == 0) rhsb[b * ng + a] = -(c[b * Nc + Ns + a] + (gshift ? gshift[b * ng + a] : 0.0));
+  }
+  if (idx >= B * Nz) return;
+  const int64_t b = idx / Nz, col = idx - b * Nz;
+  const bool pinned = pin && fixed[col];
+  double* prow = panel + b * ng * Nz + col;
+  for (int j = 0; j < ng; ++j) prow[(int64_t)j * Nz] = 0.0;
+  double acc = g[idx];
+  for (int e = cptr[col]; e < cptr[col + 1]; ++e) {
+    const double v = J[b * nnzJ + ck[e]];
+    const int row = crow[e];
+    acc += v * mu[b * ldmu + row];
+    if (row >= Ns && !pinned) prow[(int64_t)(row - Ns) * Nz] += v;
+  }
+  rx[idx] = acc;
+  rhsx[idx] = pinned ? 0.0 : -acc;
+}
+
+// the step of a pinned variable (1e16 on its diagonal, zero right-hand side: what is left is the 1e-16-sized answer to its couplings) is
+// exactly zero
+static __global__ void k_border_unpin(int64_t B, int64_t Nz, const int* fixed, double* dx, int64_t lddx) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * Nz) return;
+  const int64_t b = idx / Nz, k = idx - b * Nz;
+  if (fixed[k]) dx[b * lddx + k] = 0.0;
+}
+
 // resid[b] = NaN for the instances whose Schur complement is singular (their solution is NaN in every entry; the maximum of
 // k_rows_maxabs ignores NaN)
 static __global__ void k_border_resid_singular(int64_t B, const int* singular, double* resid) {

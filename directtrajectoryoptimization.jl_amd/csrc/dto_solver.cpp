@@ -223,6 +223,18 @@ struct KktBorder {
   DevBuf<double> ref_r, ref_d;   // [B][Nz + Nc + 16] each: residual and correction (or M sol) of dto_kkt_border_solve_refined, allocated
                                  // by its first call with passes > 0 or a residual norm to report
 };
+// constraint rows of K as the border entry points see it: on the tile path the stage part (GeneralConstraint rows, the tail of
+// every constraint-side array, are neither read nor written there)
+static inline int64_t kkt_rows(const Problem* p) {
+  return p->vt->launch_wide ? p->L.Nc - p->L.Ngen : p->L.Nc;
+}
+// tile path with GeneralConstraint rows: solved by the bordered path of dto_solve_batch only (general_solve_batch): the stepwise
+// entry points and per-instance bounds belong to the tile solver, which has no border
+static inline int wide_general_refused(const Problem* p, const char* who) {
+  if (!p->vt->launch_wide || p->L.Ngen == 0) return DTO_OK;
+  return set_error(DTO_ERR_UNSUPPORTED, std::string(who) + ": GeneralConstraint rows on the tile path are solved by the bordered path of "
+                                        "dto_solve_batch, which has no stepwise, warm-started or shifted solves and no per-instance bounds");
+}
 static inline void kkt_border_taken(Problem* p) {
   if (p->kkt_border) p->kkt_border->valid = false;
 }
@@ -295,7 +307,9 @@ static void wide_kkt_args(Problem* p, dto_wide_args& a) {
   a.z = K.z; a.ldz = L.Nz; a.mu = K.mu; a.ldmu = L.Nc;
   a.delta_w = K.delta_w; a.delta_c = K.delta_c; a.piv_tol = 1e-9;
   a.dz = nullptr; a.lddz = 0; a.dmu = nullptr; a.lddmu = 0;
-  a.fac = p->wide_fac; a.flags = K.flags; a.Nc = L.Nc; a.prof = nullptr;
+  // (GeneralConstraint rows, the tail of every constraint-side array, are not part of K: the kernels reach multipliers through
+  //  cdoff[t] only, and the inertia test expects one negative pivot per dynamics row)
+  a.fac = p->wide_fac; a.flags = K.flags; a.Nc = L.Nc - L.Ngen; a.prof = nullptr;
   a.fixed_lo = a.fixed_hi = nullptr; a.ldb = 0; a.dw_inst = nullptr; a.gam_inst = nullptr; a.active = nullptr; a.stats = nullptr; a.merit = nullptr;
   a.zl = a.zu = nullptr; a.mu_inst = nullptr; a.tau_min = 0.99;
   wide_args_no_linear(a);
@@ -304,7 +318,10 @@ static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_syste
   int rc = p->ensure_device();
   if (rc) return rc;
   const Layout& L = p->L;
-  if (L.Nstage != 0 || L.Ngen != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows and bounds only");
+  // GeneralConstraint rows: K is the stage part, of dimension Nz + Ns (as on the lane path); their entries of mu and sigma_c are
+  // not read
+  if (L.Nstage != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows, GeneralConstraint rows and bounds only");
+  const size_t Ns = (size_t)(L.Nc - L.Ngen);
   if (b->B < 1) return set_error(DTO_ERR_INVALID, "empty batch");
   if (b->params && L.Nw > 0 && b->ldp < L.Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
   if (!p->wide_kkt) p->wide_kkt = new WideKkt();
@@ -325,7 +342,7 @@ static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_syste
   K.own_params = b->params != nullptr && Nw > 0;
   if (K.own_params && (rc = grow_buf(K.params, B * Nw, "dto_kkt_assemble: hipMalloc of the parameters"))) return rc;
   K.use_sigx = sys->sigma_x != nullptr;
-  K.use_sigc = sys->sigma_c != nullptr && L.Nc > 0;
+  K.use_sigc = sys->sigma_c != nullptr && Ns > 0;
   if (K.use_sigx && (rc = grow_buf(K.sigx, B * Nz, "dto_kkt_assemble: hipMalloc of sigma_x"))) return rc;
   if (K.use_sigc && (rc = grow_buf(K.sigc, B * Nc, "dto_kkt_assemble: hipMalloc of sigma_c"))) return rc;
   HIP_TRY(K.flags.grow(2 * B));
@@ -333,11 +350,14 @@ static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_syste
   auto copy = [&](double* dst, size_t n, const double* src, int64_t ld) {
     return hipMemcpy2DAsync(dst, n * sizeof(double), src, (size_t)ld * sizeof(double), n * sizeof(double), B, hipMemcpyDeviceToDevice, st);
   };
+  auto copy2 = [&](double* dst, size_t pitch, size_t n, const double* src, int64_t ld) {   // n entries of rows `pitch` apart
+    return hipMemcpy2DAsync(dst, pitch * sizeof(double), src, (size_t)ld * sizeof(double), n * sizeof(double), B, hipMemcpyDeviceToDevice, st);
+  };
   HIP_TRY(copy(K.z, Nz, b->x, b->ldx));
-  if (L.Nc > 0) HIP_TRY(copy(K.mu, (size_t)L.Nc, sys->mu, sys->ldmu));
+  if (Ns > 0) HIP_TRY(copy2(K.mu, Nc, Ns, sys->mu, sys->ldmu));
   if (K.own_params) HIP_TRY(copy(K.params, Nw, b->params, b->ldp));
   if (K.use_sigx) HIP_TRY(copy(K.sigx, Nz, sys->sigma_x, sys->ldsx));
-  if (K.use_sigc) HIP_TRY(copy(K.sigc, (size_t)L.Nc, sys->sigma_c, sys->ldsc));
+  if (K.use_sigc) HIP_TRY(copy2(K.sigc, Nc, Ns, sys->sigma_c, sys->ldsc));
   // (dto_kkt_factor takes a stream of its own: the copies are complete when this returns)
   HIP_TRY(hipStreamSynchronize(st));
   K.B = b->B; K.delta_w = sys->delta_w; K.delta_c = sys->delta_c;
@@ -479,7 +499,7 @@ static int wide_kkt_solve_refined(Problem* p, int passes, const double* rhs_x, i
   int rc = wide_kkt_solve(p, rhs_x, ldrx, rhs_c, ldrc, sol_x, ldsx, sol_c, ldsc, st);
   if (rc || (passes == 0 && !resid)) return rc;
   WideKkt& K = *p->wide_kkt;
-  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, ld = Nz + Nc;
+  const int64_t Nz = p->L.Nz, Nc = p->L.Nc - p->L.Ngen, ld = Nz + Nc;   // (the stage part: general rows are not touched)
   const size_t need = (size_t)K.B * (size_t)ld;
   const std::string what = "dto_kkt_solve_refined: hipMalloc of a workspace array (" + std::to_string(need * sizeof(double)) + " bytes: " +
                            std::to_string(K.B) + " instances x " + std::to_string(ld) + " doubles)";
@@ -2203,9 +2223,74 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
   return DTO_OK;
 }
 
+// ---- the bordered step on the tile path: the stage part is factorised ONCE into the stored records, the n_g border rows go
+//      through one panel substitution (dto_kkt_border_factor) and the step is one single substitution and two passes over Y
+//      (dto_kkt_border_solve) -- instead of the n_g + 1 sweeps of the lane path above.  Fixed variables (pin_fixed): sigma_x = 1e16,
+//      as on the lane path (why not the identity rows of the tile solver, and why 1e16 is safe in
+//      k_wide_step's linear-solver mode); k_border_point zeroes their entries of the right-hand side and of the panel, and
+//      k_border_unpin the 1e-16-sized step that is left, so that a fixed variable keeps its value to the last bit.
+static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
+                              double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
+                              const double* gdiag, const double* gshift) {
+  const Layout& L = p->L;
+  const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
+  if (ng > KB_MAX) return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_border_factor: more than 16 border rows (one panel of right-hand sides)");
+  if (L.Nstage != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows, GeneralConstraint rows and bounds only");
+  hipStream_t st = (hipStream_t)b->stream;
+  dto_problem* h = reinterpret_cast<dto_problem*>(p);
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  if ((rc = ensure_border_csc(p))) return rc;
+  // workspace: J | c | grad | sigma | r_x | rhs_x | rhs_c | panel [B * ng][Nz] | C [B][ng * ng] | rhs_b [B][ng] | delta_w [B]
+  const size_t nBz = (size_t)B * Nz, nBc = (size_t)B * Nc, nBg = (size_t)B * ng;
+  HIP_TRY(p->border_ws.grow((size_t)B * nnzJ + 2 * nBc + 5 * nBz + nBg * Nz + nBg * ng + nBg + (size_t)B));
+  double* w = p->border_ws;
+  auto take = [&](size_t n) { double* q = w; w += n; return q; };
+  double *dJ = take((size_t)B * nnzJ), *dC = take(nBc), *dG = take(nBz), *dSig = take(nBz), *dRxv = take(nBz), *dRhsx = take(nBz),
+         *dRhsc = take(nBc), *dPanel = take(nBg * Nz), *dCb = take(nBg * ng), *dRhsb = take(nBg), *dDw = take((size_t)B);
+#define DRC(expr) do { rc = (expr); if (rc) return rc; } while (0)
+  if (!(stats && stats->reuse_point)) {   // (a further delta_w attempt at the same point keeps J, c, grad f and r_x)
+    DRC(dto_eval_jac_g_batch(h, b, dJ, nnzJ));
+    DRC(dto_eval_g_batch(h, b, dC, Nc));
+    DRC(dto_eval_grad_f_batch(h, b, dG, Nz));
+  }
+  // (the right-hand sides, the panel and C are written again at every attempt: one launch, and nothing to clear first)
+  {
+    const size_t n = std::max(nBz, std::max((size_t)B * Ns, nBg * ng));
+    hipLaunchKernelGGL(k_border_point, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, Nz, Nc, Ns, (int)ng, nnzJ, (const double*)dJ,
+                       (const double*)dG, (const double*)dC, mu, ldmu, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row,
+                       (const int*)p->d_var_fixed, pin_fixed ? 1 : 0, delta_c, gdiag, gshift, dRxv, dRhsx, dPanel, dRhsc, dRhsb, dCb);
+    HIP_TRY(hipGetLastError());
+  }
+  // per-instance delta_w through the sigma_x diagonal (pin_fixed: a variable with lo == hi keeps its value)
+  HIP_TRY(hipMemcpyAsync(dDw, dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_border_sig, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw, (const int*)p->d_var_fixed,
+                     pin_fixed ? 1 : 0, dSig);
+  dto_kkt_system sys;
+  sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
+  sys.delta_w = 0.0; sys.delta_c = delta_c;
+  DRC(wide_kkt_assemble(p, b, &sys));
+  std::vector<int32_t> iok((size_t)B, 1), negdef((size_t)B, 1), sing((size_t)B, 0);
+  DRC(wide_kkt_factor(p, iok.data(), nullptr, st));
+  DRC(dto_kkt_border_factor(h, ng, dPanel, Nz, nullptr, 0, dCb, ng * ng, negdef.data(), sing.data(), (void*)st));
+  DRC(dto_kkt_border_solve(h, dRhsx, Nz, dRhsc, Nc, dRhsb, ng, dx, lddx, dmu, lddmu, dmu + Ns, lddmu, (void*)st));
+#undef DRC
+  if (pin_fixed) {
+    hipLaunchKernelGGL(k_border_unpin, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const int*)p->d_var_fixed, dx, lddx);
+    HIP_TRY(hipGetLastError());
+  }
+  if (stats) { stats->d_grad = dG; stats->d_c = dC; stats->d_rx = dRxv; }
+  HIP_TRY(hipStreamSynchronize(st));
+  if (ok_out)
+    for (int64_t i = 0; i < B; ++i) ok_out[i] = (iok[(size_t)i] != 0 && negdef[(size_t)i] != 0 && sing[(size_t)i] == 0) ? 1 : 0;
+  return DTO_OK;
+}
+
 static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                          double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
                          const double* gdiag, const double* gshift) {
+  if (p->vt->launch_wide)
+    return bordered_step_tile(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift);
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
   {
@@ -2689,10 +2774,12 @@ int dto_kkt_step_batch(dto_problem* h, const dto_batch* b, const double* mu, int
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || !b || !b->x || !mu || !dx || !dmu) return set_error(DTO_ERR_INVALID, "null argument");
   if (b->ldx < p->L.Nz || ldmu < p->L.Nc || lddx < p->L.Nz || lddmu < p->L.Nc) return set_error(DTO_ERR_INVALID, "leading dimension too small");
-  if (p->vt->launch_wide) {
+  if (p->vt->launch_wide && p->L.Ngen == 0) {
     return dto::wide_step(p, b, mu, ldmu, delta_w, delta_c, dx, lddx, dmu, lddmu, inertia_ok);
   }
-  if (p->L.Ngen > 0) {   // GeneralConstraint rows coupling several knots: bordered system, Schur complement on the border
+  // GeneralConstraint rows coupling several knots: bordered system, Schur complement on the border (on the tile path: the stored
+  // factor, the panel substitution and one bordered solve)
+  if (p->L.Ngen > 0) {
     std::vector<double> dwv((size_t)b->B, delta_w);
     std::vector<int> okv((size_t)b->B, 1);
     int rcg = dto::bordered_step(p, b, mu, ldmu, dwv.data(), delta_c, dx, lddx, dmu, lddmu, okv.data(), nullptr);
@@ -2795,6 +2882,7 @@ int dto_solver_begin(dto_problem* h, const dto_options* opt, const dto_batch* b)
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || !b || !b->x) return set_error(DTO_ERR_INVALID, "null argument");
   if (b->ldx < p->L.Nz) return set_error(DTO_ERR_INVALID, "ldx < num_variables");
+  if (int rg = dto::wide_general_refused(p, "dto_solver_begin")) return rg;
   if (p->vt->launch_wide) return dto::wide_begin(p, opt, b, false, 0.0);   // tile path: cold start, as dto_solve_batch
   int rc = p->ensure_device();
   if (rc) return rc;
@@ -2874,6 +2962,7 @@ int dto_solver_iterate(dto_problem* h, int n, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (p && p->im_active && p->im && p->im->begun) return dto::im_iterate(p, n, (hipStream_t)stream);
   if (p && p->vt->launch_wide) {
+    if (int rg = dto::wide_general_refused(p, "dto_solver_iterate")) return rg;
     if (!p->wide || !p->wide->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin has not been called");
     return dto::wide_iterate(p, std::max(0, n), (hipStream_t)stream);
   }
@@ -3163,6 +3252,7 @@ static __global__ void k_shift_knots(const double* in, double* out, int64_t ld, 
 int dto_solver_shift(dto_problem* h, int knots, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || knots < 0) return set_error(DTO_ERR_INVALID, "bad arguments");
+  if (int rg = dto::wide_general_refused(p, "dto_solver_shift")) return rg;
   if (p->vt->launch_wide) return dto::wide_shift(p, knots, (hipStream_t)stream);
   if (p->im_active) return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_shift: SoA engine only");
   if (!p->solver || !p->solver->z) return set_error(DTO_ERR_INVALID, "dto_solver_shift needs the device state of a previous solve");
@@ -3230,6 +3320,7 @@ int dto_solver_set_bounds(dto_problem* h, int64_t B, const double* lower, int64_
   if (!p->vt->launch_wide)
     return set_error(DTO_ERR_UNSUPPORTED, "dto_solver_set_bounds: per-instance variable bounds are a tile-path (17..64-state) feature; on "
                                           "the lane-per-instance path per-instance values enter through parameters in stage rows");
+  if (int rg = dto::wide_general_refused(p, "dto_solver_set_bounds")) return rg;
   if (!lower && !upper) {
     p->d_bnd.reset(); p->bnd_B = 0;
     return DTO_OK;
@@ -3475,6 +3566,7 @@ int dto_solver_run(dto_problem* h, double* x_out, int64_t ldxo, double* mu_out, 
   Problem* p = reinterpret_cast<Problem*>(h);
   if (p && p->im_active && p->im && p->im->begun) return dto::im_run(p, x_out, ldxo, mu_out, ldmuo, status, iterations, (hipStream_t)stream);
   if (p && p->vt->launch_wide) {
+    if (int rg = dto::wide_general_refused(p, "dto_solver_run")) return rg;
     if (!p->wide || !p->wide->begun) return set_error(DTO_ERR_INVALID, "dto_solver_begin[_warm] has not been called");
     return dto::wide_run(p, x_out, ldxo, mu_out, ldmuo, status, iterations, (hipStream_t)stream);
   }
@@ -3536,7 +3628,7 @@ int dto_solve_batch(dto_problem* h, const dto_options* opt, const dto_batch* b, 
   Problem* p = reinterpret_cast<Problem*>(h);
   // (the tile and the bordered paths have no limited-memory mode: they run the exact second derivatives of the traced
   //  expressions whatever dto_options.hessian_approximation asks for, and dto_solver_hessian_mode reports it -- ADVICE r5)
-  if (p && b && b->x && x_out && p->vt->launch_wide) {
+  if (p && b && b->x && x_out && p->vt->launch_wide && p->L.Ngen == 0) {
     // tile path: begin + run on the state of the handle, which stays allocated for dto_solver_begin_warm / dto_solver_shift
     int rc = dto::wide_begin(p, opt, b, false, 0.0);
     if (rc) return rc;
@@ -3554,6 +3646,7 @@ int dto_solve_batch(dto_problem* h, const dto_options* opt, const dto_batch* b, 
 int dto_solver_begin_warm(dto_problem* h, const dto_options* opt, const dto_batch* b, double mu0) {
   Problem* p = reinterpret_cast<Problem*>(h);
   if (!p || !b) return set_error(DTO_ERR_INVALID, "null argument");
+  if (int rg = dto::wide_general_refused(p, "dto_solver_begin_warm")) return rg;
   if (p->vt->launch_wide) return dto::wide_begin(p, opt, b, true, mu0);
   if (p->im_active && p->im && p->im->A) {
     if (p->im->B != b->B) return set_error(DTO_ERR_INVALID, "dto_solver_begin_warm needs the device state of a previous solve of the same batch size");
@@ -3750,9 +3843,11 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
     return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
   if (nb < 1) return set_error(DTO_ERR_INVALID, "dto_kkt_border_factor: nb < 1");
   if (nb > dto::KB_MAX) return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_border_factor: more than 16 border rows (one panel of right-hand sides)");
-  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc;
+  // tile path with GeneralConstraint rows: K is the stage part, a row of the panel and of Y has Nz + Ns entries and the tail of
+  // g_c is not read
+  const int64_t Nz = p->L.Nz, Nc = dto::kkt_rows(p), N = Nz + Nc;
   if (!g_x) return set_error(DTO_ERR_INVALID, "null argument");
-  if (ldgx < Nz || (g_c && ldgc < Nc) || (c && ldc < nb * nb)) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (ldgx < Nz || (g_c && ldgc < p->L.Nc) || (c && ldc < nb * nb)) return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if (wide && !p->wide_kkt->factored)
     return set_error(DTO_ERR_INVALID, "dto_kkt_factor has not been called (or dto_kkt_step_batch / the solver has used the factor storage since)");
   const int64_t B = wide ? p->wide_kkt->B : p->solver->B;
@@ -3831,7 +3926,7 @@ int dto_kkt_border_solve(dto_problem* h, const double* rhs_x, int64_t ldrx, cons
   dto::KktBorder& W = *p->kkt_border;
   if (!rhs_b || !sol_b) return set_error(DTO_ERR_INVALID, "null argument");
   if (ldrb < W.nb || ldsb < W.nb) return set_error(DTO_ERR_INVALID, "leading dimension too small");
-  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc, B = W.B;
+  const int64_t Nz = p->L.Nz, Nc = dto::kkt_rows(p), N = Nz + Nc, B = W.B;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = dto_kkt_solve(h, rhs_x, ldrx, rhs_c, ldrc, W.v0, N, W.v0 + Nz, N, stream))) return rc;
   const int* singular = W.iw + (size_t)B * 17;
@@ -3865,7 +3960,7 @@ static int check_border_vectors(Problem* p, const char* who, const char* bad, co
 static int border_multiply(Problem* p, const double* v_x, int64_t ldvx, const double* v_c, int64_t ldvc, const double* v_b, int64_t ldvb,
                            double* out_x, int64_t ldox, double* out_c, int64_t ldoc, double* out_b, int64_t ldob, hipStream_t st) {
   dto::KktBorder& W = *p->kkt_border;
-  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc, B = W.B;
+  const int64_t Nz = p->L.Nz, Nc = dto::kkt_rows(p), N = Nz + Nc, B = W.B;
   if (int rc = dto::wide_kkt_multiply(p, v_x, ldvx, v_c, ldvc, out_x, ldox, out_c, ldoc, st)) return rc;
   hipLaunchKernelGGL(dto::k_border_mul, dim3((unsigned)(B * W.chunks)), dim3(dto::KB_THREADS), 0, st, W.nb, Nz, W.n_c, W.chunk, W.chunks,
                      (const double*)W.g, N, (const double*)(W.g + Nz), N, v_x, ldvx, v_c, ldvc, v_b, ldvb, out_x, ldox, out_c, ldoc,
@@ -3905,7 +4000,7 @@ int dto_kkt_border_solve_refined(dto_problem* h, int passes, const double* rhs_x
   if ((rc = dto_kkt_border_solve(h, rhs_x, ldrx, rhs_c, ldrc, rhs_b, ldrb, sol_x, ldsx, sol_c, ldsc, sol_b, ldsb, stream))) return rc;
   if (passes == 0 && !resid) return DTO_OK;
   dto::KktBorder& W = *p->kkt_border;
-  const int64_t Nz = p->L.Nz, Nc = p->L.Nc, N = Nz + Nc, ld = N + dto::KB_MAX, B = W.B;
+  const int64_t Nz = p->L.Nz, Nc = dto::kkt_rows(p), N = Nz + Nc, ld = N + dto::KB_MAX, B = W.B;
   const int nb = W.nb;
   hipStream_t st = (hipStream_t)stream;
   const size_t need = (size_t)B * (size_t)ld;

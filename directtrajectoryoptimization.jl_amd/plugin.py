@@ -103,8 +103,10 @@ class Structure:
             self.wide_nu = nu0
         # (the tile KKT kernels have dynamics rows and variable bounds, no stage rows: problems with stage constraints are solved
         #  through the embedding of solver.py: pad_to_wide, which turns the rows into auxiliary states -- their own plugin, the
-        #  one with the Constraint objects, carries the evaluator callbacks only)
-        self.wide_solver = self.wide and self.wide_n == WIDE_STATE and not self.con and self.general is None
+        #  one with the Constraint objects, carries the evaluator callbacks only).  GeneralConstraint rows do not stand in the
+        #  way: the tile kernels address multipliers through cdoff[t] and never reach the tail of general rows, which the
+        #  runtime library solves through the border (csrc/dto_solver.cpp: bordered_step_tile)
+        self.wide_solver = self.wide and self.wide_n == WIDE_STATE and not self.con
         if self.evaluate_hessian:
             # all objects must agree on the flag
             for o in list(self.dyn) + list(self.cost) + list(self.con):
@@ -374,7 +376,8 @@ def generate_wide_source(st: Structure, name: str) -> str:
         host_tables.append(_int_array(f"con{i}_hr", c.hessian_sparsity[0] if nh else []))
         host_tables.append(_int_array(f"con{i}_hc", c.hessian_sparsity[1] if nh else []))
         host_tables.append(_int_array(f"con{i}_iq", sorted(c.indices_inequality)))
-    # GeneralConstraint (round 6): evaluator callbacks only; the solver reaches such rows through solver.py's transformations
+    # GeneralConstraint: evaluator callbacks (k_wide_general), beside the tile KKT kernels when the structure is a solver plugin;
+    # the solver reaches such rows through the border of the runtime library or through solver.py's transformations
     g = st.general
     if g is not None:
         va = {"z": "z", "w": "w", "lam": "lam"}

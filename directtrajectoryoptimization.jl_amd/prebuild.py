@@ -34,6 +34,36 @@ def _entries():
     ]
 
 
+def tile_border_solvers():
+    """The problems of tests/test_wide_general_border_*.py: coupling GeneralConstraint rows on the tile path (64 states, and 24
+    states through the embedding).  Knots, totals and names are literals of the generated code, so every problem is a plugin of
+    its own; constructing the Solver builds what it loads (the callbacks plugin and, for 24 states, the embedded solver form).  Returns the
+    names."""
+    from .solver import Options, Solver
+
+    def solver(name, rows, options=None, **kw):
+        p = P.build_acrobot_padded(general_row=list(rows) if len(rows) > 1 else rows[0], **kw)
+        Solver(p["dynamics"], p["objective"], p["constraints"], p["bounds"], evaluate_hessian=True,
+               general_constraint=p["general_constraint"], options=options, name=name)
+        return name
+
+    pairs = lambda count, T: [(a, b) for a in range(1, T + 1) for b in range(a + 1, T + 1)][:count]
+    tot = P.ACROBOT_PADDED_COUPLING_TOTALS
+    out = [solver("acrobot_padded_g", [(2, 5, 0.2)], T=6),
+           solver("acrobot24gp", [(2, 5, 0.2, False, "product")], T=6, n=24, target=0.4, terminal="physical"),
+           solver("acrobot24gpc", [(2, 5, 0.2, False, "product")], T=6, n=24, target=0.4, terminal="physical",
+                  stage_constraints=(0.4, -2.56, 0.1))]
+    for m in (1, 2):
+        out.append(solver(f"acrobot_padded_g_m{m}", [(2, 5, 0.2), (3, 6, 0.1, False, "product")], T=6, m=m))
+    for count in (16, 17):
+        out.append(solver(f"acrobot_padded_g{count}", [(a, b, 0.1 * (j + 1)) for j, (a, b) in enumerate(pairs(count, 8))], T=8))
+    for row in ((10, 20, tot["sum"]), (10, 20, tot["product"], False, "product"), (10, 20, tot["sum<=0"], True)):
+        out.append(solver("acrobot_padded_g", [row], T=30, target=0.5, terminal="physical"))
+    out.append(solver("acrobot24gp", [(10, 20, tot["product24"], False, "product")], T=30, n=24, target=0.4, terminal="physical"))
+    out.append(solver("acrobot24g", [(10, 20, 0.2)], T=30, n=24, target=0.4, terminal="physical", options=Options(general_rows="border")))
+    return out
+
+
 def all_structures():
     out = []
     for name, builder, kw in _entries():

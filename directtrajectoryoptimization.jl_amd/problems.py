@@ -262,6 +262,15 @@ def padded_action_cost(x, u):
     return c
 
 
+# Totals of the coupling rows of tests/test_wide_general_border_gpu.py on build_acrobot_padded(T=30, terminal="physical"), knots 10
+# and 20 (a total is a literal of the generated plugin, so the tests and prebuild.py share these).  Each is the value of the row's
+# expression at the solution WITHOUT the row, moved by 0.3 so that the row binds (the 64-state product by 0.1: at + 0.3, where q1[10]
+# or q1[20] has to change sign, two of three guesses ran into the 1000-iteration limit), to two decimals: "sum" / "product" / "sum<=0"
+# on the 64-state problem with target 0.5 (free q1: 0.3341 and -0.6501, sum -0.3160, product -0.2172), "product24" on the 24-state
+# problem with target 0.4 (free q1: 0.3771 and -0.6103, product -0.2301).
+ACROBOT_PADDED_COUPLING_TOTALS = {"sum": -0.02, "product": -0.12, "sum<=0": -0.62, "product24": 0.07}
+
+
 def build_acrobot_padded(T=2000, n=64, evaluate_hessian=True, target=PI, terminal="full", u_max=None, m=1, parameters=None,
                          stage_constraints=None, general_row=None):
     """cfg5 (BASELINE.json configs[4]): acrobot swing-up with the state padded to n = 64 so that the per-stage KKT
@@ -310,13 +319,27 @@ def build_acrobot_padded(T=2000, n=64, evaluate_hessian=True, target=PI, termina
     if general_row is not None:
         # general_row = (ka, kb, total[, inequality]): one GeneralConstraint row coupling two knots (src/general_constraint.jl:18-59),
         # q1 at knot ka + q1 at knot kb - total (= 0 | <= 0) -- round 6: coupling rows on a model with more than 16 states
+        # (ka, kb, total, inequality, "product"): q1[ka] * q1[kb] - total instead -- NOT a sum of one-knot terms, so no accumulator
+        # state can carry it: such a row is solved through the border of the tile path.  A list of such tuples: several rows.
+        # Rows with second derivatives are built without Hessians, as build_pendulum_coupled(nonlinear=True) does
+        # (src/general_constraint.jl:87 is broken; the layout refuses general rows with Hessian entries).
         from .model import GeneralConstraint
-        ka, kb, tot = int(general_row[0]), int(general_row[1]), float(general_row[2])
-        iq = bool(general_row[3]) if len(general_row) > 3 else False
+        rows = list(general_row) if isinstance(general_row, list) else [general_row]
         nz = n * T + m * (T - 1)
-        ia, ib = (ka - 1) * (n + m), (kb - 1) * (n + m)
-        gc = GeneralConstraint(lambda z, w: np.array([z[ia] + z[ib] - tot], dtype=object), nz, 0, indices_inequality=([1] if iq else []),
-                               evaluate_hessian=evaluate_hessian)
+        spec = []
+        for r in rows:
+            ka, kb, tot = int(r[0]), int(r[1]), float(r[2])
+            spec.append(((ka - 1) * (n + m), (kb - 1) * (n + m), tot, bool(r[3]) if len(r) > 3 else False,
+                         len(r) > 4 and r[4] == "product"))
+        if len(spec) == 1 and not spec[0][4]:
+            ia, ib, tot, iq = spec[0][:4]
+            gc = GeneralConstraint(lambda z, w: np.array([z[ia] + z[ib] - tot], dtype=object), nz, 0, indices_inequality=([1] if iq else []),
+                                   evaluate_hessian=evaluate_hessian)
+        else:
+            gc = GeneralConstraint(lambda z, w: np.array([(z[ia] * z[ib] if prod else z[ia] + z[ib]) - tot for ia, ib, tot, _, prod in spec],
+                                                         dtype=object), nz, 0,
+                                   indices_inequality=[j + 1 for j, s in enumerate(spec) if s[3]],
+                                   evaluate_hessian=evaluate_hessian and not any(s[4] for s in spec))
     return dict(
         dynamics=[dt] * (T - 1),
         objective=[ct] * (T - 1) + [cT],

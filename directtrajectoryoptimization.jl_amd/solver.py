@@ -492,10 +492,31 @@ class Solver:
                     zmap, mumap, musign = zmap[za], mumap[ma], musign[ma] * sa
                 self._pad = (zmap, mumap, musign)
                 changed = wide_embedded = True
+        # ---- 2b. 17 .. 63 states with GeneralConstraint rows that stayed rows (not sums of one-knot terms, or
+        #      Options.general_rows = "border"): the same embedding, with the rows re-indexed to its layout; the runtime library
+        #      solves them through the border of the tile path (csrc/dto_solver.cpp: bordered_step_tile).  Equality stage rows ride
+        #      auxiliary states beside them; the bordered loop has no barrier, so inequality stage rows and finite bounds do not
+        border_refusal = None
+        if gen is not None and s_eh and _WMIN <= n_max < _WST:
+            border_refusal = _no_barrier_beside_general(s_con, s_bounds)
+            padded = pad_to_wide(s_dyn, s_obj, s_con, s_bounds, s_eh) if border_refusal is None else None
+            if padded is not None:
+                s_dyn, s_obj, s_con, s_bounds, zmap, mumap, musign = padded
+                nz_pad = sum(o.num_state + o.num_action for o in s_obj)
+                nc_pad = sum(d.num_next_state for d in s_dyn)
+                gen = embed_general_constraint(gen, zmap, nz_pad)
+                # the general rows: behind the embedded dynamics rows, as they are, sign +1
+                mumap = np.concatenate([mumap, nc_pad + np.arange(gen.num_constraint, dtype=np.int64)])
+                musign = np.concatenate([musign, np.ones(gen.num_constraint)])
+                self._stage_rows = np.asarray(mumap)[np.asarray(musign) < 0]
+                self._pad = (zmap, mumap, musign)
+                changed = wide_embedded = True
         # 17 .. 63 states that the embedding cannot take: the problem gets evaluator callbacks (a tile-family plugin of its own
         # size) but no solver -- say so here, not as "plugin has no KKT kernels" at the first solve
         if _WMIN <= n_max < _WST and not wide_embedded:
-            why = ("GeneralConstraint rows that are not sums of one-knot terms" if gen is not None else
+            why = (border_refusal if border_refusal is not None else
+                   "GeneralConstraint rows beside more than four actions, varying dimensions, user-Jacobian dynamics or more "
+                   "stage-constraint rows in one stage than there are padding states" if gen is not None else
                    "the per-stage SR1 mode (no second derivatives to embed)" if not s_eh else
                    "more than four actions, varying dimensions, user-Jacobian dynamics, or more stage-constraint rows in one stage than "
                    "there are padding states (rows affine in one variable are restated as bounds and do not count; rows of the last knot count "
@@ -1138,6 +1159,33 @@ def pad_to_wide(dynamics, objective, constraints, bounds, evaluate_hessian):
         musign += [-1.0] * Q[t]
     return (dyn2, obj2, [Constraint() for _ in range(T)], bnd2, np.asarray(zmap, dtype=np.int64), np.asarray(mumap, dtype=np.int64),
             np.asarray(musign))
+
+
+def _no_barrier_beside_general(constraints, bounds):
+    """What the bordered solve loop cannot take beside GeneralConstraint rows (it has no barrier: csrc/dto_solver.cpp,
+    general_solve_batch), as the text of Solver.solve_unsupported -- or None."""
+    if any(c.num_constraint and c.indices_inequality for c in constraints):
+        return ("inequality rows of a stage Constraint beside GeneralConstraint rows (inequality rows beside general rows would ride "
+                "bounded auxiliary states, and the bordered solve loop has no barrier for them)")
+    for b in bounds:
+        for lo, hi in ((b.state_lower, b.state_upper), (b.action_lower, b.action_upper)):
+            lo, hi = np.asarray(lo, dtype=float), np.asarray(hi, dtype=float)
+            if np.any((lo != hi) & (np.isfinite(lo) | np.isfinite(hi))):
+                return ("finite variable bounds beside GeneralConstraint rows (the bordered solve loop has no barrier: variables may be "
+                        "free or fixed by equal bounds)")
+    return None
+
+
+def embed_general_constraint(general, zmap, num_variables):
+    """`general` over the variables of an embedded problem: variable i of the problem is variable zmap[i] of the embedding (the
+    map pad_batch uses), the other variables of the embedding do not occur.  Rows, inequality set and Hessian flag are kept."""
+    from .symbolic import expr as E
+    z = E.variables("z", general.num_variables)
+    rows = list(general.evaluate_expr)
+    return GeneralConstraint(lambda zz, w: np.array(E.substitute(rows, {z[i]: zz[int(zmap[i])] for i in range(general.num_variables)}),
+                                                    dtype=object),
+                             int(num_variables), general.num_parameter, indices_inequality=list(general.indices_inequality),
+                             evaluate_hessian=general.evaluate_hessian)
 
 
 def pins_to_bounds(constraints, bounds, evaluate_hessian):

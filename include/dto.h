@@ -241,6 +241,12 @@ int dto_kkt_step_batch(dto_problem* p, const dto_batch* b, const double* mu, int
  *    handle: any of them invalidates the stored factor, and dto_kkt_solve then fails with DTO_ERR_INVALID until
  *    dto_kkt_factor is called again (the assembled system is kept).  dto_kkt_assemble copies the point, the multipliers, the
  *    diagonals and the batch's parameters, so the caller's arrays may change after it returns.
+ *  Problems with GeneralConstraint rows (both paths): K is the STAGE part K_s, of dimension num_variables + Ns with Ns =
+ *  num_constraint - (number of general rows); the general rows are the caller's border (dto_kkt_border_factor below).  Every
+ *  constraint-side array keeps its length and leading dimension (>= num_constraint), but on the tile path its last entries, those of
+ *  the general rows, are neither read nor written -- mu, sigma_c, rhs_c, sol_c here, v_c / out_c of dto_kkt_multiply, g_c of
+ *  dto_kkt_border_factor -- and inertia_ok expects Ns negative pivots.  This holds for every entry point of this block and of the
+ *  two blocks below (stage Constraint rows are not taken on the tile path: DTO_ERR_UNSUPPORTED).
  *  Order: assemble, factor, solve; dto_kkt_factor before dto_kkt_assemble and dto_kkt_solve before dto_kkt_factor fail with
  *  DTO_ERR_INVALID.  The single factorisation attempt is swept to the end whatever its inertia: dto_kkt_solve returns
  *  K^-1 rhs (unpivoted) also when inertia_ok is 0.
@@ -379,9 +385,15 @@ int dto_kkt_border_solve_refined(dto_problem* p, int passes, const double* rhs_x
  * kernels for 64-state models (variables free, fixed or bounded; no stage constraints, one to four actions, shared or per-instance parameters;
  * 17..63-state models through their 64-state embedding; stepwise, warm-started and shifted solves through the entry points below); a
  * GeneralConstraint whose rows couple several knots is solved through a border (general rows equalities or inequalities,
- * dynamics / stage rows equalities, variables free or fixed):
- * one factorisation and n_g + 1 sweeps per step, the border algebra on the device since round 4 (DTO_BORDER_HOST=1: on the
- * host), the filter line-search loop around it driven from the host. */
+ * dynamics / stage rows equalities, variables free or fixed; shared parameters only), the filter line-search loop around it
+ * driven from the host:
+ * - lane-per-instance path: one factorisation and n_g + 1 sweeps per step, the border algebra on the device since round 4
+ *   (DTO_BORDER_HOST=1: on the host);
+ * - tile path (a 64-state model with general rows, or a 17..63-state problem embedded with them): one stored factorisation, one
+ *   panel substitution for all n_g rows and one bordered solve per step (dto_kkt_border_factor / dto_kkt_border_solve inside); at
+ *   most 16 general rows (more: DTO_ERR_UNSUPPORTED), no stage rows.  dto_solve_batch, dto_solve and dto_kkt_step_batch take such a
+ *   problem; dto_solver_begin / begin_warm / iterate / run / shift and dto_solver_set_bounds return DTO_ERR_UNSUPPORTED for it
+ *   (cold starts only, the problem's shared bounds).  dto_solver_hessian_mode reports DTO_HESSIAN_EXACT, kkt_refinement is ignored. */
 int dto_solve_batch(dto_problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                     double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 
