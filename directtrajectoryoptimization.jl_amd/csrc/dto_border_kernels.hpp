@@ -294,6 +294,70 @@ static __global__ __launch_bounds__(64) void k_border_mul_fin(int nb, int chunks
   out_b[b * ldob + j] = acc;
 }
 
+// ---- finite variable bounds in the bordered solve loop (dto_solver.cpp: general_solve_batch): primal-dual barrier with the bound
+//      multipliers eliminated, as wide_outer has it.  The per-variable pieces are wide_bar / wide_bar_step of dto_wide_kernels.hpp
+//      (include that header first); lo == hi is a fixed variable and has no barrier term.
+// What bordered_step is given beside the point: device pointers, z / zl / zu instance-major [B][Nz], lo / hi the problem's shared
+// bounds [Nz], mu the barrier parameter per instance [B].  z == NULL: no barrier terms, the step is the plain Newton step.
+struct BorderBar {
+  const double *z = nullptr, *zl = nullptr, *zu = nullptr, *lo = nullptr, *hi = nullptr, *mu = nullptr;
+};
+enum { BORDER_BAR_APMAX = 0, BORDER_BAR_ADMAX, BORDER_BAR_LOGBAR, BORDER_BAR_DPHI, BORDER_BAR_SZMAX, BORDER_BAR_ISZMAX, BORDER_BAR_SUMZ,
+       BORDER_BAR_DINF, BORDER_BAR_NSTAT };
+// What the host loop needs of the bounds at the point and along the step dz, per instance (one wavefront each, lane-strided partial
+// results and a fixed tree, so the same numbers at every run): the fraction-to-the-boundary steps alpha_p^max / alpha_d^max with
+// tau = max(tau_min, 1 - mu), sum log(gap), the barrier part of the merit's directional derivative -mu sum dx/(x-lo) + mu sum dx/(hi-x),
+// max gap z and max 1 / (gap z) (DTO_WIDE_SZMAX / ISZMAX of the tile solver: compl_at(mu) on the host for any mu), sum z_L + sum z_U,
+// and the dual infeasibility over the non-fixed variables of an r_x that already holds - z_L + z_U.
+static __global__ __launch_bounds__(64) void k_border_bar_stats(int64_t Nz, BorderBar bar, const double* dz, const double* rx,
+                                                                const int* fixed, double tau_min, double* out) {
+  const int64_t b = blockIdx.x;
+  const int l = threadIdx.x;
+  const double mu = bar.mu[b], tau = fmax(tau_min, 1.0 - mu);
+  double ap = 1.0, ad = 1.0, logb = 0.0, dphi = 0.0, szmax = 0.0, iszmax = 0.0, sumz = 0.0, dinf = 0.0;
+  for (int64_t k = l; k < Nz; k += 64) {
+    const int64_t i = b * Nz + k;
+    const double x = bar.z[i], dx = dz[i], lo = bar.lo[k], hi = bar.hi[k], zl = bar.zl[i], zu = bar.zu[i];
+    const wide::WideBar wb = wide::wide_bar(x, lo, hi, zl, zu, mu);
+    logb += wb.logb; sumz += wb.sum_z; dphi -= wb.br * dx;
+    szmax = fmax(szmax, wb.sz_max); iszmax = fmax(iszmax, wb.isz_max);
+    wide::wide_bar_step(x, dx, lo, hi, zl, zu, mu, tau, ap, ad);
+    if (!fixed[k]) dinf = fmax(dinf, fabs(rx[i]));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    logb += __shfl_down(logb, off, 64); sumz += __shfl_down(sumz, off, 64); dphi += __shfl_down(dphi, off, 64);
+    szmax = fmax(szmax, __shfl_down(szmax, off, 64)); iszmax = fmax(iszmax, __shfl_down(iszmax, off, 64));
+    dinf = fmax(dinf, __shfl_down(dinf, off, 64));
+    ap = fmin(ap, __shfl_down(ap, off, 64)); ad = fmin(ad, __shfl_down(ad, off, 64));
+  }
+  if (l == 0) {
+    double* o = out + b * BORDER_BAR_NSTAT;
+    o[BORDER_BAR_APMAX] = ap; o[BORDER_BAR_ADMAX] = ad; o[BORDER_BAR_LOGBAR] = logb; o[BORDER_BAR_DPHI] = dphi;
+    o[BORDER_BAR_SZMAX] = szmax; o[BORDER_BAR_ISZMAX] = iszmax; o[BORDER_BAR_SUMZ] = sumz; o[BORDER_BAR_DINF] = dinf;
+  }
+}
+// A trial point of the line search with bounds, one launch: out[2 b] = sum_k |rows[b][k] (+ shift)|, the sum of k_rows_abs_sum in
+// its order, and out[2 b + 1] = sum log(gap) of the trial point x ([B][Nz]; inside the bounds by the fraction-to-the-boundary rule)
+static __global__ __launch_bounds__(64) void k_border_trial(const double* rows, int64_t ld, int64_t n, const double* shift, int64_t n0,
+                                                            int64_t nsh, const double* x, int64_t Nz, const double* lo, const double* hi,
+                                                            double* out) {
+  const int64_t b = blockIdx.x;
+  double acc = 0.0, logb = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 64) acc += fabs(rows[b * ld + i] + ((shift && i >= n0) ? shift[b * nsh + (i - n0)] : 0.0));
+  for (int64_t k = threadIdx.x; k < Nz; k += 64) {
+    const double a = lo[k], c = hi[k], v = x[b * Nz + k];
+    if (a == c) continue;
+    double t = 0.0;   // (per variable first, as wide_bar sums it at the iterate)
+    if (a > -1e300) t += log(v - a);
+    if (c < 1e300) t += log(c - v);
+    logb += t;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { acc += __shfl_down(acc, off, 64); logb += __shfl_down(logb, off, 64); }
+  if (threadIdx.x == 0) { out[2 * b] = acc; out[2 * b + 1] = logb; }
+}
+
 // ---- the bordered step of the solver on the tile path (dto_solver.cpp: bordered_step_tile): everything dto_kkt_border_factor /
 //      dto_kkt_border_solve are given, from the derivatives at the point.  One thread per (instance, column) -- a thread owns
 //      column `col` of instance b in r_x, rhs_x and all ng panel rows, so nothing is summed across threads:
@@ -304,10 +368,12 @@ static __global__ __launch_bounds__(64) void k_border_mul_fin(int nb, int chunks
 //      pin (with fixed[col]): the variable keeps its value -- its column of the panel and its entry of rhs_x are zero (the factor
 //      holds 1e16 on its diagonal).  J is indexed through the CSC tables of the constant pattern
 //      (cptr [Nz + 1], ck: position in the COO value array, crow: 0-based row).
+//      bar (bar.z != NULL: finite variable bounds, see BorderBar below): r_x gets - z_L + z_U and rhs_x the barrier gradient,
+//          rhs_x = -(grad f + J' mu - mu_b/(x-lo) + mu_b/(hi-x)); this kernel runs at every delta_w attempt, so the terms are here.
 static __global__ void k_border_point(int64_t B, int64_t Nz, int64_t Nc, int64_t Ns, int ng, int64_t nnzJ, const double* J, const double* g,
                                       const double* c, const double* mu, int64_t ldmu, const int* cptr, const int* ck, const int* crow,
                                       const int* fixed, int pin, double delta_c, const double* gdiag, const double* gshift, double* rx,
-                                      double* rhsx, double* panel, double* rhsc, double* rhsb, double* cblk) {
+                                      double* rhsx, double* panel, double* rhsc, double* rhsb, double* cblk, BorderBar bar) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < B * Ns) {
     const int64_t b = idx / Ns, k = idx - b * Ns;
@@ -330,6 +396,12 @@ static __global__ void k_border_point(int64_t B, int64_t Nz, int64_t Nc, int64_t
     const int row = crow[e];
     acc += v * mu[b * ldmu + row];
     if (row >= Ns && !pinned) prow[(int64_t)(row - Ns) * Nz] += v;
+  }
+  if (bar.z) {
+    const wide::WideBar wb = wide::wide_bar(bar.z[idx], bar.lo[col], bar.hi[col], bar.zl[idx], bar.zu[idx], bar.mu[b]);
+    rx[idx] = acc + wb.zdiff;
+    rhsx[idx] = pinned ? 0.0 : -(acc - wb.br);
+    return;
   }
   rx[idx] = acc;
   rhsx[idx] = pinned ? 0.0 : -acc;

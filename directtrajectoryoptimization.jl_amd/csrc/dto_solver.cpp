@@ -187,7 +187,7 @@ struct BorderStats;
 
 static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                          double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed = false,
-                         const double* gdiag = nullptr, const double* gshift = nullptr);
+                         const double* gdiag = nullptr, const double* gshift = nullptr, const BorderBar* bar = nullptr);
 static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                                double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 
@@ -2006,7 +2006,8 @@ constexpr int BORDER_MAX_NG = 16;
 // r_x = grad f + J' mu column by column (entries of a column in COO order: the same sums as the host loop of round 3), the
 // general rows of J as dense vectors, the first right-hand side
 static __global__ void k_border_rx(int64_t B, int64_t Nz, int64_t Ns, int64_t nnzJ, const double* J, const double* g, const double* mu,
-                                   int64_t ldmu, const int* cptr, const int* ck, const int* crow, double* rx, double* rhsx, double* Grow) {
+                                   int64_t ldmu, const int* cptr, const int* ck, const int* crow, double* rx, double* rhsx, double* Grow,
+                                   BorderBar bar) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * Nz) return;
   const int64_t b = idx / Nz, col = idx - b * Nz;
@@ -2016,6 +2017,14 @@ static __global__ void k_border_rx(int64_t B, int64_t Nz, int64_t Ns, int64_t nn
     const int row = crow[e];
     acc += v * mu[b * ldmu + row];
     if (row >= Ns) Grow[((int64_t)(row - Ns) * B + b) * Nz + col] += v;   // (this thread owns column col of instance b)
+  }
+  if (bar.z) {
+    // finite bounds: r_x with the bound multipliers, the right-hand side with the barrier gradient (this kernel runs once per point:
+    // a further delta_w attempt keeps both)
+    const wide::WideBar wb = wide::wide_bar(bar.z[idx], bar.lo[col], bar.hi[col], bar.zl[idx], bar.zu[idx], bar.mu[b]);
+    rx[idx] = acc + wb.zdiff;
+    rhsx[idx] = -(acc - wb.br);
+    return;
   }
   rx[idx] = acc;
   rhsx[idx] = -acc;
@@ -2043,11 +2052,17 @@ static __global__ __launch_bounds__(64) void k_border_stats(int64_t Nz, int64_t 
   }
   if (l == 0) { double* o = out + b * 5; o[0] = th1; o[1] = thinf; o[2] = dinf; o[3] = slam; o[4] = gd; }
 }
-// per-instance delta_w on the primal diagonal; a variable with lo == hi gets a huge entry instead (its step is ~1e-16 r)
-static __global__ void k_border_sig(int64_t B, int64_t Nz, const double* dw, const int* fixed, int pin_fixed, double* sig) {
+// per-instance delta_w on the primal diagonal; a variable with lo == hi gets a huge entry instead (its step is ~1e-16 r); with
+// finite bounds (bar.z != NULL) the others get delta_w + z_L/(x-lo) + z_U/(hi-x)
+static __global__ void k_border_sig(int64_t B, int64_t Nz, const double* dw, const int* fixed, int pin_fixed, double* sig, BorderBar bar) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * Nz) return;
-  sig[idx] = (pin_fixed && fixed[idx % Nz]) ? 1e16 : dw[idx / Nz];
+  const int64_t b = idx / Nz, col = idx % Nz;
+  if (bar.z && !(pin_fixed && fixed[col])) {
+    sig[idx] = dw[b] + wide::wide_bar(bar.z[idx], bar.lo[col], bar.hi[col], bar.zl[idx], bar.zu[idx], bar.mu[b]).sig;
+    return;
+  }
+  sig[idx] = (pin_fixed && fixed[col]) ? 1e16 : dw[b];
 }
 static __global__ void k_border_rhsc(int64_t B, int64_t Nc, int64_t Ns, const double* c, double* rhsc) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2165,11 +2180,12 @@ static int ensure_border_csc(Problem* p) {
 
 static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                                 double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
-                                const double* gdiag, const double* gshift) {
+                                const double* gdiag, const double* gshift, const BorderBar* barp) {
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
   hipStream_t st = (hipStream_t)b->stream;
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
+  const BorderBar bar = barp ? *barp : BorderBar();   // (no bounds: all NULL, the kernels take their old branches)
   int rc = ensure_border_csc(p);
   if (rc) return rc;
   // workspace: J | c | g | sig | rx | rhsx | rhsc | zero_c | v0x | v0c | Grow[ng] | Yx[ng] | Yc[ng] | hdx | hdm | rho | flags
@@ -2191,13 +2207,13 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
     HIP_TRY(hipMemsetAsync(dGrow, 0, (size_t)ng * nBz * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(dZeroC, 0, nBc * sizeof(double), st));
     hipLaunchKernelGGL(k_border_rx, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, Ns, nnzJ, (const double*)dJ, (const double*)dG,
-                       mu, ldmu, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row, dRxv, dRhsx, dGrow);
+                       mu, ldmu, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row, dRxv, dRhsx, dGrow, bar);
     hipLaunchKernelGGL(k_border_rhsc, dim3((unsigned)((nBc + 255) / 256)), dim3(256), 0, st, B, Nc, Ns, (const double*)dC, dRhsc);
   }
   // per-instance delta_w through the sigma_x diagonal (pin_fixed: a variable with lo == hi keeps its value)
   HIP_TRY(hipMemcpyAsync(dDw, dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_border_sig, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw, (const int*)p->d_var_fixed,
-                     pin_fixed ? 1 : 0, dSig);
+                     pin_fixed ? 1 : 0, dSig, bar);
   dto_kkt_system sys;
   sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
   sys.delta_w = 0.0; sys.delta_c = delta_c;
@@ -2231,13 +2247,14 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
 //      k_border_unpin the 1e-16-sized step that is left, so that a fixed variable keeps its value to the last bit.
 static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                               double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
-                              const double* gdiag, const double* gshift) {
+                              const double* gdiag, const double* gshift, const BorderBar* barp) {
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
   if (ng > KB_MAX) return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_border_factor: more than 16 border rows (one panel of right-hand sides)");
   if (L.Nstage != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows, GeneralConstraint rows and bounds only");
   hipStream_t st = (hipStream_t)b->stream;
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
+  const BorderBar bar = barp ? *barp : BorderBar();   // (no bounds: all NULL, the kernels take their old branches)
   int rc = p->ensure_device();
   if (rc) return rc;
   if ((rc = ensure_border_csc(p))) return rc;
@@ -2259,13 +2276,13 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
     const size_t n = std::max(nBz, std::max((size_t)B * Ns, nBg * ng));
     hipLaunchKernelGGL(k_border_point, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, Nz, Nc, Ns, (int)ng, nnzJ, (const double*)dJ,
                        (const double*)dG, (const double*)dC, mu, ldmu, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row,
-                       (const int*)p->d_var_fixed, pin_fixed ? 1 : 0, delta_c, gdiag, gshift, dRxv, dRhsx, dPanel, dRhsc, dRhsb, dCb);
+                       (const int*)p->d_var_fixed, pin_fixed ? 1 : 0, delta_c, gdiag, gshift, dRxv, dRhsx, dPanel, dRhsc, dRhsb, dCb, bar);
     HIP_TRY(hipGetLastError());
   }
   // per-instance delta_w through the sigma_x diagonal (pin_fixed: a variable with lo == hi keeps its value)
   HIP_TRY(hipMemcpyAsync(dDw, dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_border_sig, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw, (const int*)p->d_var_fixed,
-                     pin_fixed ? 1 : 0, dSig);
+                     pin_fixed ? 1 : 0, dSig, bar);
   dto_kkt_system sys;
   sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
   sys.delta_w = 0.0; sys.delta_c = delta_c;
@@ -2288,15 +2305,16 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
 
 static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                          double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
-                         const double* gdiag, const double* gshift) {
+                         const double* gdiag, const double* gshift, const BorderBar* barp) {
   if (p->vt->launch_wide)
-    return bordered_step_tile(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift);
+    return bordered_step_tile(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp);
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
   {
     const char* e = getenv("DTO_BORDER_HOST");
     if (!(e && atoi(e) != 0) && ng <= BORDER_MAX_NG)
-      return bordered_step_device(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift);
+      return bordered_step_device(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp);
+    if (barp) return set_error(DTO_ERR_UNSUPPORTED, "variable bounds beside GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
     if (gdiag) return set_error(DTO_ERR_UNSUPPORTED, "inequality GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
   }
   hipStream_t st = (hipStream_t)b->stream;
@@ -2433,7 +2451,13 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
 // ------------------------------------------------------------------------------------------------
 // Solve for models with multi-knot GeneralConstraint rows: the filter line-search SQP iteration of the other paths, driven
 // from the host like the wide-stage solver, with bordered_step as its linear solver.  Scope: equality rows (dynamics, stage,
-// general) and variables that are free or fixed by equal bounds -- no barrier.
+// general), inequality rows among the general rows (slacks, on the host over n_g <= 16 entries) and variable bounds: free, fixed
+// by equal bounds, or finite on either side.  Finite bounds are a primal-dual barrier with the bound multipliers eliminated, as in
+// wide_outer: z_L / z_U live on the device as [B][Nz], the barrier terms of the KKT system are written by the step's own kernels
+// (BorderBar), k_border_bar_stats reduces what the host rules need to eight numbers per instance that ride the copy of
+// k_border_stats, k_border_trial adds sum log(gap) of a trial point to the launch that sums its violation, and
+// k_wide_init_bounds / k_wide_update_bounds keep the multipliers.  Without a finite bound none of that is allocated or launched.
+// The bound multipliers are not returned.
 // ------------------------------------------------------------------------------------------------
 // out[b] = sum_k |rows[b][k]| in a fixed order (lane-strided partial sums, then a tree): the l1 constraint violation of a trial point
 static __global__ __launch_bounds__(64) void k_rows_abs_sum(const double* rows, int64_t ld, int64_t n, double* out, const double* shift = nullptr,
@@ -2453,9 +2477,11 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   if (rc) return rc;
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc;
+  // finite bound sides of the variables that are not fixed (the tests of k_wide_init_bounds: a side is finite inside +-1e300)
+  int64_t n_bound = 0;
   for (int64_t i = 0; i < Nz; ++i)
-    if (L.var_lo[i] != L.var_hi[i] && (std::isfinite(L.var_lo[i]) || std::isfinite(L.var_hi[i])))
-      return set_error(DTO_ERR_UNSUPPORTED, "GeneralConstraint solve path: variables may be free or fixed (lo == hi), not bounded");
+    if (L.var_lo[i] != L.var_hi[i]) n_bound += (L.var_lo[i] > -1e300 ? 1 : 0) + (L.var_hi[i] < 1e300 ? 1 : 0);
+  const bool bounds = n_bound > 0;
   // inequality rows (c <= 0: src/general_constraint.jl:15-19 `indices_inequality`) among the GENERAL rows are carried with slacks
   // g_i + s_i = 0, s_i >= 0 (round 4): the border's diagonal gets s_i / nu_i, its right-hand side mu / nu_i; dynamics and stage
   // rows stay equalities on this path
@@ -2478,7 +2504,8 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   // the temporaries of this call: released on every return
   DevBuf<double> z, lam, dz, dlam, zt, df, dc, dal, dth;
   DevBuf<double> dgd, dgs, dst, dnu;   // [B][ng]: s / nu, mu / nu, trial slacks, multipliers of the general rows
-  DevBuf<double> d5;                   // [B][5] statistics of the point and the step
+  DevBuf<double> d5;                   // [B][5] statistics of the point and the step; with bounds [B][BORDER_BAR_NSTAT] behind them
+  DevBuf<double> zl, zu, dlo, dhi, dmub, dad;   // finite bounds only: multipliers [B][Nz], shared bounds [Nz], mu and alpha_d [B]
   HIP_TRY(z.alloc((size_t)B * Nz));
   HIP_TRY(lam.alloc((size_t)B * Nc));
   HIP_TRY(dz.alloc((size_t)B * Nz));
@@ -2487,25 +2514,49 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   HIP_TRY(df.alloc((size_t)B));
   HIP_TRY(dc.alloc((size_t)B * Nc));
   HIP_TRY(dal.alloc((size_t)B));
-  HIP_TRY(dth.alloc((size_t)B));
+  HIP_TRY(dth.alloc((size_t)B * (bounds ? 2 : 1)));   // (with bounds: theta and sum log(gap) of a trial point)
   if (ni > 0) {
     for (DevBuf<double>* q : {&dgd, &dgs, &dst, &dnu}) HIP_TRY(q->alloc((size_t)B * ng));
   }
-  // the guess, with the fixed variables put on their values
-  std::vector<double> hz((size_t)B * Nz);
-  HIP_TRY(hipMemcpy2DAsync(hz.data(), Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  for (int64_t i = 0; i < B; ++i)
-    for (int64_t k = 0; k < Nz; ++k)
-      if (L.var_lo[k] == L.var_hi[k]) hz[(size_t)i * Nz + k] = L.var_lo[k];
-  HIP_TRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  BorderBar bar;
+  std::vector<double> hz;
+  if (bounds) {
+    // the guess pushed inside the bounds, fixed variables on their values, z_L / z_U on the central path of mu_init: the cold
+    // start of the tile solver, instance-major over [B][Nz] with the problem's shared bounds (ldb = 0)
+    HIP_TRY(zl.alloc((size_t)B * Nz));
+    HIP_TRY(zu.alloc((size_t)B * Nz));
+    HIP_TRY(dlo.alloc((size_t)Nz));
+    HIP_TRY(dhi.alloc((size_t)Nz));
+    HIP_TRY(dmub.alloc((size_t)B));
+    HIP_TRY(dad.alloc((size_t)B));
+    HIP_TRY(hipMemcpyAsync(dlo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dhi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (double*)z, (double*)zl, (double*)zu,
+                       (const double*)dlo, (const double*)dhi, (int64_t)0, o.mu_init, o.bound_push, o.bound_frac, Nz);
+    HIP_TRY(hipGetLastError());
+    bar.z = z; bar.zl = zl; bar.zu = zu; bar.lo = dlo; bar.hi = dhi; bar.mu = dmub;
+  } else {
+    // the guess, with the fixed variables put on their values
+    hz.resize((size_t)B * Nz);
+    HIP_TRY(hipMemcpy2DAsync(hz.data(), Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < B; ++i)
+      for (int64_t k = 0; k < Nz; ++k)
+        if (L.var_lo[k] == L.var_hi[k]) hz[(size_t)i * Nz + k] = L.var_lo[k];
+    HIP_TRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  }
   HIP_TRY(hipMemsetAsync(lam, 0, (size_t)B * Nc * sizeof(double), st));
-  using Inst = GlobInst;   // (mu: inequality general rows only)
+  using Inst = GlobInst;   // (mu: finite bounds and inequality general rows)
   std::vector<Inst> I((size_t)B);
+  const bool barrier = bounds || ni > 0;
+  if (barrier)
+    for (int64_t i = 0; i < B; ++i) I[(size_t)i].mu = o.mu_init;
+  std::vector<double> hmu((size_t)(bounds ? B : 0)), had((size_t)(bounds ? B : 0));
   // slacks and multipliers of the general rows on the host (the multipliers are mirrored into lam after every update)
   std::vector<double> hs((size_t)B * std::max<int64_t>(1, ng), 0.0), hnu((size_t)B * std::max<int64_t>(1, ng), 0.0), hds((size_t)B * std::max<int64_t>(1, ng), 0.0);
   std::vector<double> hgd((size_t)B * std::max<int64_t>(1, ng), 0.0), hgs((size_t)B * std::max<int64_t>(1, ng), 0.0), hst((size_t)B * std::max<int64_t>(1, ng), 0.0);
-  std::vector<double> dwv((size_t)B), hf((size_t)B), hth((size_t)B), hal((size_t)B), hphi0((size_t)B);
+  std::vector<double> dwv((size_t)B), hf((size_t)B), hth((size_t)B * (bounds ? 2 : 1)), hal((size_t)B), hphi0((size_t)B);
   std::vector<int> okv((size_t)B);
   constexpr int TRIALS = DTO_LS_TRIALS;
   dto_batch bz = *b;
@@ -2542,12 +2593,17 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       HIP_TRY(hipMemcpyAsync(dgd, hgd.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(dgs, hgs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
     }
+    if (bounds) {   // the barrier parameter the step is computed with
+      for (int64_t i = 0; i < B; ++i) hmu[(size_t)i] = I[(size_t)i].mu;
+      HIP_TRY(hipMemcpyAsync(dmub, hmu.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    }
     // ---- step at the current point: delta_w ladder per instance (Algorithm IC), all instances share the sweeps
     for (int64_t i = 0; i < B; ++i) dwv[(size_t)i] = I[(size_t)i].ls_fail ? ladder_after_ls_fail(o, I[(size_t)i].dlast) : 0.0;
     BorderStats bs;
     for (int attempt = 0;; ++attempt) {
       bs.reuse_point = attempt > 0;
-      if ((rc = bordered_step(p, &bz, lam, Nc, dwv.data(), o.delta_c, dz, Nz, dlam, Nc, okv.data(), &bs, true, ni > 0 ? dgd : nullptr, ni > 0 ? dgs : nullptr))) return rc;
+      if ((rc = bordered_step(p, &bz, lam, Nc, dwv.data(), o.delta_c, dz, Nz, dlam, Nc, okv.data(), &bs, true, ni > 0 ? dgd : nullptr, ni > 0 ? dgs : nullptr,
+                              bounds ? &bar : nullptr))) return rc;
       bool again = false;
       for (int64_t i = 0; i < B; ++i) {
         Inst& s = I[(size_t)i];
@@ -2561,11 +2617,16 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     std::vector<double> hst5, hdnu;
     if (dev_stats) {
       // device border: five numbers per instance (and the steps of the general rows' multipliers) instead of five vectors
-      if (!d5) HIP_TRY(d5.alloc((size_t)B * 5));
+      // (with bounds BORDER_BAR_NSTAT more behind them, in the same buffer and the same copy)
+      const size_t n5 = (size_t)B * 5, nstat = n5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0);
+      if (!d5) HIP_TRY(d5.alloc(nstat));
       if (ni > 0) HIP_TRY(hipMemcpyAsync(dst, hs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));   // slack shift of theta
       hipLaunchKernelGGL(k_border_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, Nc, bs.d_c, bs.d_rx, bs.d_grad, (const double*)dz, (const double*)lam,
                          (const int*)p->d_var_fixed, (const double*)(ni > 0 ? dst : nullptr), Ns, ng, d5);
-      hst5.resize((size_t)B * 5);
+      if (bounds)
+        hipLaunchKernelGGL(k_border_bar_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, bar, (const double*)dz, bs.d_rx, (const int*)p->d_var_fixed,
+                           o.tau_min, d5 + n5);
+      hst5.resize(nstat);
       HIP_TRY(hipMemcpyAsync(hst5.data(), d5, hst5.size() * sizeof(double), hipMemcpyDeviceToHost, st));
       if (ng > 0) {
         hdnu.resize((size_t)B * ng);
@@ -2613,17 +2674,26 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
         hds[e] = (s.mu - sv * nv) / nv - (sv / nv) * dnu;
         bar_d += hds[e] / sv;
       }
+      // finite variable bounds: the bound multipliers join the scaling, the largest and the smallest gap z give the complementarity
+      // error against any mu (as wide_convergence forms it), r_x already holds - z_L + z_U
+      const double* qb = bounds ? &hst5[(size_t)B * 5 + (size_t)i * BORDER_BAR_NSTAT] : nullptr;
+      auto compl_bounds = [&](double mu_at) {
+        if (!bounds) return 0.0;
+        const double szmin = qb[BORDER_BAR_ISZMAX] > 0.0 ? 1.0 / qb[BORDER_BAR_ISZMAX] : 1e300;
+        return std::max(qb[BORDER_BAR_SZMAX] - mu_at, mu_at - szmin);
+      };
+      if (bounds) { dinf = qb[BORDER_BAR_DINF]; c0 = std::max(c0, compl_bounds(o.mu_target)); }
       // (the slack's bound multiplier of a slack-eliminated row IS its nu: it counts among the bound multipliers, as the slack
       //  multipliers do in conv_body)
-      const ErrScale es = ipopt_scaling(o, slam, Nc, snu, ni);
+      const ErrScale es = ipopt_scaling(o, slam, Nc, snu + (bounds ? qb[BORDER_BAR_SUMZ] : 0.0), ni + n_bound);
       const IterMeasures m{hf[(size_t)i], th1, thinf, dinf, std::max(std::max(dinf / es.sd, thinf), c0 / es.sc), c0};
       mu_moved[(size_t)i] = 0;
       s.status = terminal_status(o, s.iter, m, 0);   // acc_count = 0: no acceptable-level termination on this path
-      if (s.status == 0 && ni > 0) {
+      if (s.status == 0 && barrier) {
         // Ipopt's monotone rule: once the barrier problem is solved to kappa_eps mu the parameter drops (and the filter is reset);
         // the step computed above belongs to the old mu: this instance waits one round (alpha = 0) for the step of the new one
         const double mu = monotone_mu(o, s.mu, std::max(dinf / es.sd, thinf), es.sc, [&](double mu_at) {
-          double c = 0.0;
+          double c = compl_bounds(mu_at);
           for (int64_t q = 0; q < ng; ++q)
             if (ineq[(size_t)q]) c = std::max(c, std::fabs(hs[(size_t)(i * ng + q)] * hnu[(size_t)(i * ng + q)] - mu_at));
           return c;
@@ -2632,6 +2702,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       }
       init_theta_limits(s, th1);
       th0[(size_t)i] = th1; gphid[(size_t)i] = gd - s.mu * bar_d;
+      if (bounds) gphid[(size_t)i] += qb[BORDER_BAR_DPHI];
       if (s.status == 0) {
         any = true;
         if (dwv[(size_t)i] > 0.0) s.dlast = dwv[(size_t)i]; else s.dlast = 0.0;
@@ -2648,10 +2719,17 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     std::vector<MostFeasible> best_a((size_t)B);
     // inequality rows: the trials start from the fraction-to-the-boundary step of the slacks, the merit is the barrier function
     std::vector<double> apmax((size_t)B, 1.0), admax((size_t)B, 1.0);
-    for (int64_t i = 0; i < B && ni > 0; ++i) {
+    // finite bounds: the same from the device's statistics -- alpha_p^max and alpha_d^max combined by min, sum log(gap) in the merit
+    for (int64_t i = 0; i < B && barrier; ++i) {
       Inst& s = I[(size_t)i];
       if (s.status != 0) continue;
       if (mu_moved[(size_t)i]) { chosen_a[(size_t)i] = 0.0; continue; }   // waits for the step of its new barrier parameter
+      if (bounds) {
+        const double* qb = &hst5[(size_t)B * 5 + (size_t)i * BORDER_BAR_NSTAT];
+        apmax[(size_t)i] = qb[BORDER_BAR_APMAX]; admax[(size_t)i] = qb[BORDER_BAR_ADMAX];
+        hphi0[(size_t)i] -= s.mu * qb[BORDER_BAR_LOGBAR];
+      }
+      if (ni == 0) continue;
       const double tau = std::max(o.tau_min, 1.0 - s.mu);
       double lb = 0.0;
       for (int64_t q = 0; q < ng; ++q) {
@@ -2685,15 +2763,20 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       bt.x = zt;
       if ((rc = dto_eval_f_batch(h, &bt, df))) return rc;
       if ((rc = dto_eval_g_batch(h, &bt, dc, Nc))) return rc;
-      hipLaunchKernelGGL(k_rows_abs_sum, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, dth, (const double*)(ni > 0 ? dst : nullptr), Ns, ng);
+      if (bounds)   // the violation and sum log(gap) of the trial point in one launch, both in the copy of theta
+        hipLaunchKernelGGL(k_border_trial, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, (const double*)(ni > 0 ? dst : nullptr), Ns, ng,
+                           (const double*)zt, Nz, (const double*)dlo, (const double*)dhi, (double*)dth);
+      else
+        hipLaunchKernelGGL(k_rows_abs_sum, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, dth, (const double*)(ni > 0 ? dst : nullptr), Ns, ng);
       HIP_TRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(hth.data(), dth, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(hth.data(), dth, hth.size() * sizeof(double), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       for (int64_t i = 0; i < B; ++i) {
         Inst& s = I[(size_t)i];
         if (s.status != 0 || chosen_a[(size_t)i] >= 0.0) continue;
         double pk = hf[(size_t)i];
-        const double tk = hth[(size_t)i];
+        const double tk = bounds ? hth[(size_t)(2 * i)] : hth[(size_t)i];
+        if (bounds) pk -= s.mu * hth[(size_t)(2 * i + 1)];
         for (int64_t q = 0; q < ng && ni > 0; ++q)
           if (ineq[(size_t)q]) pk -= s.mu * std::log(hst[(size_t)(i * ng + q)]);
         note_most_feasible(best_a[(size_t)i], k, tk);
@@ -2705,13 +2788,22 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       hal[(size_t)i] = 0.0;
       Inst& s = I[(size_t)i];
       if (s.status != 0) continue;
-      if (ni > 0 && mu_moved[(size_t)i]) continue;   // no step, no iteration: its barrier parameter just moved
+      if (barrier && mu_moved[(size_t)i]) continue;   // no step, no iteration: its barrier parameter just moved
       // (an instance whose trials were all rejected had all TRIALS of them evaluated)
       hal[(size_t)i] = finish_line_search(s, chosen_a[(size_t)i], ftype_a[(size_t)i] != 0, best_a[(size_t)i], th0[(size_t)i], hphi0[(size_t)i],
                                           apmax[(size_t)i], TRIALS, okv[(size_t)i] ? 0 : 1);
       s.iter++;
     }
     HIP_TRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    if (bounds) {
+      // bound multipliers first (their update reads the old point): alpha_d^max with the kappa_Sigma clamp against the instance's
+      // mu; an instance that takes no step (terminated, or its mu just moved) keeps them
+      for (int64_t i = 0; i < B; ++i) had[(size_t)i] = hal[(size_t)i] == 0.0 ? 0.0 : admax[(size_t)i];
+      HIP_TRY(hipMemcpyAsync(dad, had.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_wide_update_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (const double*)z, (const double*)dz,
+                         (double*)zl, (double*)zu, (const double*)dlo, (const double*)dhi, (int64_t)0, (const double*)dal, (const double*)dad,
+                         (const double*)dmub, Nz);
+    }
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)dal, Nz, Nz, Nz);
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, lam, (const double*)dlam, (const double*)dal, Nc, Nc, Nc);
     if (ni > 0) {

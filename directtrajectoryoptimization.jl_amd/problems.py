@@ -269,6 +269,15 @@ def padded_action_cost(x, u):
 # on the 64-state problem with target 0.5 (free q1: 0.3341 and -0.6501, sum -0.3160, product -0.2172), "product24" on the 24-state
 # problem with target 0.4 (free q1: 0.3771 and -0.6103, product -0.2301).
 ACROBOT_PADDED_COUPLING_TOTALS = {"sum": -0.02, "product": -0.12, "sum<=0": -0.62, "product24": 0.07}
+# Action bounds |u| <= U beside those rows (tests/test_wide_general_border_bounds_gpu.py): a fraction of the smallest peak |u| of
+# the unbounded solutions, to one decimal, so that the bound binds.  "64": the 64-state problem with the "sum" row, guesses
+# PCG64(0..2): peaks 40.5877 / 40.5877 / 40.5877 (with the "product" row 33.3618 each), times 0.8.  At 0.7 x (28.4) the "sum" row
+# converged in 73 / 57 / 61 iterations but the "product" row ran into the 1000-iteration limit from guess 0 (165 and 308
+# iterations from the others), at 30.0 from guess 1 and at 31.0 from guess 0, so U was moved towards the peak: at 32.5 the
+# product row takes 167 / 89 / 317 iterations (at 32.0: 57 / 624 / 42) and the bound still binds on both rows.  "24": the
+# 24-state problem (target 0.4) with q1[10] + q1[20] = 0.2, guess PCG64(0): peak 42.8479, times 0.7.  Bounds are layout data,
+# no literals of a plugin.
+ACROBOT_PADDED_COUPLING_U_MAX = {"64": 32.5, "24": 30.0}
 
 
 def build_acrobot_padded(T=2000, n=64, evaluate_hessian=True, target=PI, terminal="full", u_max=None, m=1, parameters=None,

@@ -495,7 +495,7 @@ class Solver:
         # ---- 2b. 17 .. 63 states with GeneralConstraint rows that stayed rows (not sums of one-knot terms, or
         #      Options.general_rows = "border"): the same embedding, with the rows re-indexed to its layout; the runtime library
         #      solves them through the border of the tile path (csrc/dto_solver.cpp: bordered_step_tile).  Equality stage rows ride
-        #      auxiliary states beside them; the bordered loop has no barrier, so inequality stage rows and finite bounds do not
+        #      auxiliary states beside them and finite bounds go with the variables; inequality stage rows do not (no barrier for them)
         border_refusal = None
         if gen is not None and s_eh and _WMIN <= n_max < _WST:
             border_refusal = _no_barrier_beside_general(s_con, s_bounds)
@@ -1162,17 +1162,12 @@ def pad_to_wide(dynamics, objective, constraints, bounds, evaluate_hessian):
 
 
 def _no_barrier_beside_general(constraints, bounds):
-    """What the bordered solve loop cannot take beside GeneralConstraint rows (it has no barrier: csrc/dto_solver.cpp,
-    general_solve_batch), as the text of Solver.solve_unsupported -- or None."""
+    """What the bordered solve loop cannot take beside GeneralConstraint rows (csrc/dto_solver.cpp, general_solve_batch), as the
+    text of Solver.solve_unsupported -- or None.  Finite variable bounds are taken (the loop's barrier for them: `bounds` needs no
+    check); inequality stage rows are not."""
     if any(c.num_constraint and c.indices_inequality for c in constraints):
         return ("inequality rows of a stage Constraint beside GeneralConstraint rows (inequality rows beside general rows would ride "
                 "bounded auxiliary states, and the bordered solve loop has no barrier for them)")
-    for b in bounds:
-        for lo, hi in ((b.state_lower, b.state_upper), (b.action_lower, b.action_upper)):
-            lo, hi = np.asarray(lo, dtype=float), np.asarray(hi, dtype=float)
-            if np.any((lo != hi) & (np.isfinite(lo) | np.isfinite(hi))):
-                return ("finite variable bounds beside GeneralConstraint rows (the bordered solve loop has no barrier: variables may be "
-                        "free or fixed by equal bounds)")
     return None
 
 
@@ -1322,8 +1317,8 @@ def accumulate_general_constraint(dynamics, objective, constraints, bounds, gene
         s_T + e_{r,T}(x_T) + const  (= | <=) 0   as one more stage-constraint row of the last knot;
     rows that touch one knot only (the reference's own use, test/solve.jl:273) join that knot's stage constraint as
     fold_general_constraint does.  The problem then has no general rows at all: it runs the lane-per-instance solver loop on the
-    device at full speed -- no border, no host-driven filter loop --, with variable bounds, stage inequalities and the
-    limited-memory mode beside the rows, none of which the bordered path (csrc/dto_solver.cpp: general_solve_batch) has.  The
+    device at full speed -- no border, no host-driven filter loop --, with stage inequalities and the limited-memory mode beside
+    the rows, neither of which the bordered path (csrc/dto_solver.cpp: general_solve_batch) has (variable bounds it takes).  The
     multiplier of a coupling row is the multiplier of its last-knot row.
 
     Returns (dynamics, objective, constraints, bounds, zmap, mumap, musign) in the convention of pad_to_wide, or None when a row is

@@ -385,8 +385,10 @@ int dto_kkt_border_solve_refined(dto_problem* p, int passes, const double* rhs_x
  * kernels for 64-state models (variables free, fixed or bounded; no stage constraints, one to four actions, shared or per-instance parameters;
  * 17..63-state models through their 64-state embedding; stepwise, warm-started and shifted solves through the entry points below); a
  * GeneralConstraint whose rows couple several knots is solved through a border (general rows equalities or inequalities,
- * dynamics / stage rows equalities, variables free or fixed; shared parameters only), the filter line-search loop around it
- * driven from the host:
+ * dynamics / stage rows equalities, variables free, fixed or bounded on either side -- the problem's shared bounds, by a
+ * primal-dual barrier whose bound multipliers are not returned; shared parameters only), the filter line-search loop around it
+ * driven from the host (dto_kkt_step_batch on such a problem stays the plain Newton step of the bordered system: no barrier
+ * terms of the bounds in it):
  * - lane-per-instance path: one factorisation and n_g + 1 sweeps per step, the border algebra on the device since round 4
  *   (DTO_BORDER_HOST=1: on the host);
  * - tile path (a 64-state model with general rows, or a 17..63-state problem embedded with them): one stored factorisation, one

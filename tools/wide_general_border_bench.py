@@ -1,12 +1,14 @@
 """Coupling GeneralConstraint rows on the tile path: what one outer iteration and one bordered step cost.
 
-    python tools/wide_general_border_bench.py [--B 3] [--T 30] [--reps 20]
+    python tools/wide_general_border_bench.py [--B 3] [--T 30] [--reps 20] [--bounded]
 
 1. solve_batch of the 64-state problem of tests/test_wide_general_border_gpu.py (q1[10] + q1[20] = total): wall time per outer
    iteration of the batch (the slowest instance's iteration count).
 2. The pieces of one bordered step at the solution, through the entry points the step itself calls, HIP events around each:
    the three callbacks (Jacobian, constraints, objective gradient), dto_kkt_assemble + dto_kkt_factor,
    dto_kkt_border_factor (panel substitution, Gram product, Schur complement) and dto_kkt_border_solve.
+--bounded: the same problem with the action bounds |u| <= problems.ACROBOT_PADDED_COUPLING_U_MAX["64"] of
+tests/test_wide_general_border_bounds_gpu.py (the barrier of the bordered loop); part 1 only -- the pieces of part 2 are the same calls.
 Numbers only, no threshold (DESIGN.md section 4.3 quotes a run)."""
 import argparse
 import os
@@ -26,9 +28,11 @@ def main():
     ap.add_argument("--B", type=int, default=3)
     ap.add_argument("--T", type=int, default=30)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--bounded", action="store_true")
     a = ap.parse_args()
     T, B = a.T, a.B
-    p = P.build_acrobot_padded(T=T, target=0.5, terminal="physical", general_row=(10, 20, P.ACROBOT_PADDED_COUPLING_TOTALS["sum"]))
+    u_max = P.ACROBOT_PADDED_COUPLING_U_MAX["64"] if a.bounded else None
+    p = P.build_acrobot_padded(T=T, target=0.5, terminal="physical", general_row=(10, 20, P.ACROBOT_PADDED_COUPLING_TOTALS["sum"]), u_max=u_max)
     s = dto_amd.Solver(p["dynamics"], p["objective"], p["constraints"], p["bounds"], evaluate_hessian=True,
                        general_constraint=p["general_constraint"], name="acrobot_padded_g")
     n = s.nlp
@@ -47,8 +51,10 @@ def main():
     status, iters = s.solve_batch(z0.data_ptr(), B, nz, zo.data_ptr(), nz, lam.data_ptr(), nc)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    print(f"solve_batch: B = {B}, T = {T}, status {status.tolist()}, iterations {iters.tolist()}, {wall * 1e3:.1f} ms, "
+    print(f"solve_batch{f' with |u| <= {u_max}' if a.bounded else ''}: B = {B}, T = {T}, status {status.tolist()}, iterations {iters.tolist()}, {wall * 1e3:.1f} ms, "
           f"{wall * 1e3 / max(1, int(iters.max())):.2f} ms per outer iteration of the batch")
+    if a.bounded:
+        return
 
     f64 = dict(device="cuda", dtype=torch.float64)
     J, c, g = torch.zeros((B, nnz), **f64), torch.zeros((B, nc), **f64), torch.zeros((B, nz), **f64)
