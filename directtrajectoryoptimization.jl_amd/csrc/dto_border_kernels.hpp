@@ -337,15 +337,107 @@ static __global__ __launch_bounds__(64) void k_border_bar_stats(int64_t Nz, Bord
     o[BORDER_BAR_SZMAX] = szmax; o[BORDER_BAR_ISZMAX] = iszmax; o[BORDER_BAR_SUMZ] = sumz; o[BORDER_BAR_DINF] = dinf;
   }
 }
+// ---- inequality rows (c <= 0) of stage Constraints in the bordered solve loop: slacks c + s = 0, s >= 0, eliminated as the loop
+//      eliminates those of inequality general rows -- s / nu on the constraint diagonal (dto_kkt_system.sigma_c), mu / nu in the
+//      right-hand side, nu the row's own entry of lam.  There are about T of them per instance, so they live on the device:
+// s and the step ds instance-major [B][Ns] (zero on equality rows), mask [Ns] 1 on the inequality rows, mu the barrier parameter per
+// instance [B] (shared with the bounds and the general rows' slacks).  s == NULL: no such rows, every kernel takes its old branch.
+struct BorderSlack {
+  double *s = nullptr, *ds = nullptr;
+  const int* mask = nullptr;
+  const double* mu = nullptr;
+  int64_t Ns = 0;
+};
+enum { BORDER_SLK_APMAX = 0, BORDER_SLK_ADMAX, BORDER_SLK_LOGS, BORDER_SLK_DSS, BORDER_SLK_SNUMAX, BORDER_SLK_ISNUMAX, BORDER_SLK_SUMNU,
+       BORDER_SLK_NSTAT };
+// the start: s = max(-c, 1e-2) and nu = 1 on the masked rows (as the general rows' slacks start), s = ds = 0 on the others
+static __global__ void k_border_slack_init(int64_t B, int64_t Nc, BorderSlack sl, const double* c, double* lam) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * sl.Ns) return;
+  const int64_t b = idx / sl.Ns, k = idx - b * sl.Ns;
+  sl.ds[idx] = 0.0;
+  if (!sl.mask[k]) { sl.s[idx] = 0.0; return; }
+  sl.s[idx] = fmax(-c[b * Nc + k], 1e-2);
+  lam[b * Nc + k] = 1.0;
+}
+// What the host loop needs of these slacks at the point and along the step dlam, per instance (one wavefront each, lane-strided
+// partial results and a fixed tree): ds = (mu - s nu) / nu - (s / nu) dnu, WRITTEN to sl.ds; alpha_p^max / alpha_d^max with
+// tau = max(tau_min, 1 - mu); sum log s; sum ds / s; max s nu and max 1 / (s nu) (compl_at(mu) on the host for any mu); sum nu.
+static __global__ __launch_bounds__(64) void k_border_slack_stats(int64_t Nc, BorderSlack sl, const double* lam, const double* dlam,
+                                                                  double tau_min, double* out) {
+  const int64_t b = blockIdx.x;
+  const int l = threadIdx.x;
+  const double mu = sl.mu[b], tau = fmax(tau_min, 1.0 - mu);
+  double ap = 1.0, ad = 1.0, logs = 0.0, dss = 0.0, snumax = 0.0, isnumax = 0.0, sumnu = 0.0;
+  for (int64_t k = l; k < sl.Ns; k += 64) {
+    if (!sl.mask[k]) continue;
+    const double s = sl.s[b * sl.Ns + k], nu = lam[b * Nc + k], dnu = dlam[b * Nc + k];
+    const double ds = (mu - s * nu) / nu - (s / nu) * dnu;
+    sl.ds[b * sl.Ns + k] = ds;
+    if (ds < 0.0) ap = fmin(ap, -tau * s / ds);
+    if (dnu < 0.0) ad = fmin(ad, -tau * nu / dnu);
+    logs += log(s); dss += ds / s; sumnu += fabs(nu);
+    snumax = fmax(snumax, s * nu); isnumax = fmax(isnumax, 1.0 / (s * nu));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    logs += __shfl_down(logs, off, 64); dss += __shfl_down(dss, off, 64); sumnu += __shfl_down(sumnu, off, 64);
+    snumax = fmax(snumax, __shfl_down(snumax, off, 64)); isnumax = fmax(isnumax, __shfl_down(isnumax, off, 64));
+    ap = fmin(ap, __shfl_down(ap, off, 64)); ad = fmin(ad, __shfl_down(ad, off, 64));
+  }
+  if (l == 0) {
+    double* o = out + b * BORDER_SLK_NSTAT;
+    o[BORDER_SLK_APMAX] = ap; o[BORDER_SLK_ADMAX] = ad; o[BORDER_SLK_LOGS] = logs; o[BORDER_SLK_DSS] = dss;
+    o[BORDER_SLK_SNUMAX] = snumax; o[BORDER_SLK_ISNUMAX] = isnumax; o[BORDER_SLK_SUMNU] = sumnu;
+  }
+}
+// The update of the multipliers with such slacks (in the place of lam += alpha dlam): on a masked row s += alpha ds and
+// nu += alpha_d dnu -- the dual fraction-to-the-boundary step, not alpha -- then Ipopt's kappa_Sigma clamp of nu against the instance's
+// mu and the new s; every other row moves with alpha.  One thread owns a row: it reads the old s and nu itself.  alpha == 0 (the
+// instance terminated, or its mu just moved): nothing of it is written.  Grid: B * blocks_per_row blocks.
+static __global__ void k_border_slack_update(int64_t Nc, BorderSlack sl, double* lam, const double* dlam, const double* alpha,
+                                             const double* alpha_d, double kappa_sigma, int blocks_per_row) {
+  const int64_t b = blockIdx.x / blocks_per_row;
+  const int64_t blk = blockIdx.x % blocks_per_row;
+  const double al = alpha[b];
+  if (al == 0.0) return;
+  const double ad = alpha_d[b], mu = sl.mu[b];
+  for (int64_t k = blk * blockDim.x + threadIdx.x; k < Nc; k += (int64_t)blocks_per_row * blockDim.x) {
+    if (k < sl.Ns && sl.mask[k]) {
+      const double s = sl.s[b * sl.Ns + k] + al * sl.ds[b * sl.Ns + k];
+      const double nu = lam[b * Nc + k] + ad * dlam[b * Nc + k];
+      sl.s[b * sl.Ns + k] = s;
+      lam[b * Nc + k] = fmax(fmin(nu, kappa_sigma * mu / s), mu / (kappa_sigma * s));
+    } else {
+      lam[b * Nc + k] += al * dlam[b * Nc + k];
+    }
+  }
+}
+
 // A trial point of the line search with bounds, one launch: out[2 b] = sum_k |rows[b][k] (+ shift)|, the sum of k_rows_abs_sum in
-// its order, and out[2 b + 1] = sum log(gap) of the trial point x ([B][Nz]; inside the bounds by the fraction-to-the-boundary rule)
+// its order, and out[2 b + 1] = sum log(gap) of the trial point x ([B][Nz]; inside the bounds by the fraction-to-the-boundary rule;
+// x == NULL: no bounds, 0).  With slacks of stage rows (sl.s != NULL; then the output has three numbers per instance): rows k < sl.Ns
+// get s + alpha ds added (zero on equality rows) and out[3 b + 2] = sum log(s + alpha ds) over the masked rows.
 static __global__ __launch_bounds__(64) void k_border_trial(const double* rows, int64_t ld, int64_t n, const double* shift, int64_t n0,
                                                             int64_t nsh, const double* x, int64_t Nz, const double* lo, const double* hi,
-                                                            double* out) {
+                                                            double* out, BorderSlack sl = BorderSlack(), const double* alpha = nullptr) {
   const int64_t b = blockIdx.x;
-  double acc = 0.0, logb = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 64) acc += fabs(rows[b * ld + i] + ((shift && i >= n0) ? shift[b * nsh + (i - n0)] : 0.0));
-  for (int64_t k = threadIdx.x; k < Nz; k += 64) {
+  double acc = 0.0, logb = 0.0, logs = 0.0;
+  if (sl.s) {
+    const double al = alpha[b];
+    for (int64_t i = threadIdx.x; i < n; i += 64) {
+      double v = rows[b * ld + i] + ((shift && i >= n0) ? shift[b * nsh + (i - n0)] : 0.0);
+      if (i < sl.Ns) {
+        const double st = sl.s[b * sl.Ns + i] + al * sl.ds[b * sl.Ns + i];
+        v += st;
+        if (sl.mask[i]) logs += log(st);
+      }
+      acc += fabs(v);
+    }
+  } else {
+    for (int64_t i = threadIdx.x; i < n; i += 64) acc += fabs(rows[b * ld + i] + ((shift && i >= n0) ? shift[b * nsh + (i - n0)] : 0.0));
+  }
+  for (int64_t k = threadIdx.x; x && k < Nz; k += 64) {
     const double a = lo[k], c = hi[k], v = x[b * Nz + k];
     if (a == c) continue;
     double t = 0.0;   // (per variable first, as wide_bar sums it at the iterate)
@@ -354,8 +446,14 @@ static __global__ __launch_bounds__(64) void k_border_trial(const double* rows, 
     logb += t;
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { acc += __shfl_down(acc, off, 64); logb += __shfl_down(logb, off, 64); }
-  if (threadIdx.x == 0) { out[2 * b] = acc; out[2 * b + 1] = logb; }
+  for (int off = 32; off > 0; off >>= 1) {
+    acc += __shfl_down(acc, off, 64); logb += __shfl_down(logb, off, 64);
+    if (sl.s) logs += __shfl_down(logs, off, 64);   // (uniform over the wavefront)
+  }
+  if (threadIdx.x == 0) {
+    if (sl.s) { out[3 * b] = acc; out[3 * b + 1] = logb; out[3 * b + 2] = logs; }
+    else { out[2 * b] = acc; out[2 * b + 1] = logb; }
+  }
 }
 
 // ---- the bordered step of the solver on the tile path (dto_solver.cpp: bordered_step_tile): everything dto_kkt_border_factor /

@@ -187,7 +187,8 @@ struct BorderStats;
 
 static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                          double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed = false,
-                         const double* gdiag = nullptr, const double* gshift = nullptr, const BorderBar* bar = nullptr);
+                         const double* gdiag = nullptr, const double* gshift = nullptr, const BorderBar* bar = nullptr,
+                         const BorderSlack* slk = nullptr);
 static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                                double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 
@@ -2033,12 +2034,16 @@ static __global__ void k_border_rx(int64_t B, int64_t Nz, int64_t Ns, int64_t nn
 // dual infeasibility over the free variables, sum |lam|, grad f' dz -- five numbers instead of five vectors over PCIe
 static __global__ __launch_bounds__(64) void k_border_stats(int64_t Nz, int64_t Nc, const double* c, const double* rx, const double* g,
                                                             const double* dz, const double* lam, const int* fixed, const double* shift,
-                                                            int64_t n0, int64_t nsh, double* out) {
+                                                            int64_t n0, int64_t nsh, double* out, const double* sshift = nullptr,
+                                                            int64_t nss = 0) {
+  // sshift (optional, [B][nss]): the slacks of the stage rows, added to rows 0 .. nss - 1 (zero on equality rows)
   const int64_t b = blockIdx.x;
   const int l = threadIdx.x;
   double th1 = 0.0, thinf = 0.0, dinf = 0.0, slam = 0.0, gd = 0.0;
   for (int64_t k = l; k < Nc; k += 64) {
-    const double v = fabs(c[b * Nc + k] + ((shift && k >= n0) ? shift[b * nsh + (k - n0)] : 0.0));
+    double cv = c[b * Nc + k] + ((shift && k >= n0) ? shift[b * nsh + (k - n0)] : 0.0);
+    if (sshift && k < nss) cv += sshift[b * nss + k];
+    const double v = fabs(cv);
     th1 += v; thinf = fmax(thinf, v); slam += fabs(lam[b * Nc + k]);
   }
   for (int64_t k = l; k < Nz; k += 64) {
@@ -2064,9 +2069,22 @@ static __global__ void k_border_sig(int64_t B, int64_t Nz, const double* dw, con
   }
   sig[idx] = (pin_fixed && fixed[col]) ? 1e16 : dw[b];
 }
-static __global__ void k_border_rhsc(int64_t B, int64_t Nc, int64_t Ns, const double* c, double* rhsc) {
+// sl (sl.s != NULL: slack-eliminated inequality stage rows, see BorderSlack): such a row gets -(c + mu / nu) and s / nu in sigc
+// ([B][Nc], zero everywhere else), nu its entry of the multipliers
+static __global__ void k_border_rhsc(int64_t B, int64_t Nc, int64_t Ns, const double* c, double* rhsc, BorderSlack sl = BorderSlack(),
+                                     const double* mu = nullptr, int64_t ldmu = 0, double* sigc = nullptr) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * Nc) return;
+  if (sl.s) {
+    const int64_t b = idx / Nc, k = idx - b * Nc;
+    if (k < Ns && sl.mask[k]) {
+      const double nu = mu[b * ldmu + k];
+      rhsc[idx] = -(c[idx] + sl.mu[b] / nu);
+      sigc[idx] = sl.s[b * sl.Ns + k] / nu;
+      return;
+    }
+    sigc[idx] = 0.0;
+  }
   rhsc[idx] = (idx % Nc) < Ns ? -c[idx] : 0.0;
 }
 // one wavefront per instance: S = -(G Y_x + dc I), r_g = -c_g - G v0_x (lane-strided partial sums, fixed tree), then lane 0: S
@@ -2180,17 +2198,20 @@ static int ensure_border_csc(Problem* p) {
 
 static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                                 double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
-                                const double* gdiag, const double* gshift, const BorderBar* barp) {
+                                const double* gdiag, const double* gshift, const BorderBar* barp, const BorderSlack* slk) {
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
   hipStream_t st = (hipStream_t)b->stream;
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
   const BorderBar bar = barp ? *barp : BorderBar();   // (no bounds: all NULL, the kernels take their old branches)
+  const BorderSlack sl = slk ? *slk : BorderSlack();  // (no inequality stage rows: the same)
   int rc = ensure_border_csc(p);
   if (rc) return rc;
-  // workspace: J | c | g | sig | rx | rhsx | rhsc | zero_c | v0x | v0c | Grow[ng] | Yx[ng] | Yc[ng] | hdx | hdm | rho | flags
+  // workspace: J | c | g | sig | rx | rhsx | rhsc | zero_c | v0x | v0c | Grow[ng] | Yx[ng] | Yc[ng] | hdx | hdm | rho | flags | dw
+  // (| sigma_c behind them, with inequality stage rows only)
   const size_t nBz = (size_t)B * Nz, nBc = (size_t)B * Nc;
-  const size_t ws_need = (size_t)B * nnzJ + nBc + nBz * 6 + nBc * 4 + (size_t)ng * (2 * nBz + nBc) + (size_t)B * ng + 2 * (size_t)B + 8;
+  const size_t ws_need = (size_t)B * nnzJ + nBc + nBz * 6 + nBc * 4 + (size_t)ng * (2 * nBz + nBc) + (size_t)B * ng + 2 * (size_t)B + 8 +
+                         (sl.s ? nBc : 0);
   HIP_TRY(p->border_ws.grow(ws_need));
   double* w = p->border_ws;
   auto take = [&](size_t n) { double* q = w; w += n; return q; };
@@ -2199,6 +2220,7 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
          *dYx = take((size_t)ng * nBz), *dYc = take((size_t)ng * nBc), *dHdx = take(nBz), *dHdm = take(nBc), *dRho = take((size_t)B * ng);
   int* dFlag = reinterpret_cast<int*>(take((size_t)B / 2 + 4));
   double* dDw = take((size_t)B);
+  double* dSigC = sl.s ? take(nBc) : nullptr;
 #define DRC(expr) do { rc = (expr); if (rc) return rc; } while (0)
   if (!(stats && stats->reuse_point)) {   // (a further delta_w attempt at the same point keeps all of this in the workspace)
     DRC(dto_eval_jac_g_batch(h, b, dJ, nnzJ));
@@ -2208,14 +2230,15 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
     HIP_TRY(hipMemsetAsync(dZeroC, 0, nBc * sizeof(double), st));
     hipLaunchKernelGGL(k_border_rx, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, Ns, nnzJ, (const double*)dJ, (const double*)dG,
                        mu, ldmu, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row, dRxv, dRhsx, dGrow, bar);
-    hipLaunchKernelGGL(k_border_rhsc, dim3((unsigned)((nBc + 255) / 256)), dim3(256), 0, st, B, Nc, Ns, (const double*)dC, dRhsc);
+    hipLaunchKernelGGL(k_border_rhsc, dim3((unsigned)((nBc + 255) / 256)), dim3(256), 0, st, B, Nc, Ns, (const double*)dC, dRhsc, sl, mu, ldmu,
+                       dSigC);
   }
   // per-instance delta_w through the sigma_x diagonal (pin_fixed: a variable with lo == hi keeps its value)
   HIP_TRY(hipMemcpyAsync(dDw, dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_border_sig, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw, (const int*)p->d_var_fixed,
                      pin_fixed ? 1 : 0, dSig, bar);
   dto_kkt_system sys;
-  sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
+  sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = dSigC; sys.ldsc = dSigC ? Nc : 0;
   sys.delta_w = 0.0; sys.delta_c = delta_c;
   DRC(dto_kkt_assemble(h, b, &sys));
   std::vector<int32_t> iok((size_t)B, 1);
@@ -2305,15 +2328,16 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
 
 static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                          double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
-                         const double* gdiag, const double* gshift, const BorderBar* barp) {
-  if (p->vt->launch_wide)
+                         const double* gdiag, const double* gshift, const BorderBar* barp, const BorderSlack* slk) {
+  if (p->vt->launch_wide)   // (no stage rows on the tile path: slk is NULL)
     return bordered_step_tile(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp);
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
   {
     const char* e = getenv("DTO_BORDER_HOST");
     if (!(e && atoi(e) != 0) && ng <= BORDER_MAX_NG)
-      return bordered_step_device(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp);
+      return bordered_step_device(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp, slk);
+    if (slk) return set_error(DTO_ERR_UNSUPPORTED, "inequality stage rows beside GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
     if (barp) return set_error(DTO_ERR_UNSUPPORTED, "variable bounds beside GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
     if (gdiag) return set_error(DTO_ERR_UNSUPPORTED, "inequality GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
   }
@@ -2451,8 +2475,11 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
 // ------------------------------------------------------------------------------------------------
 // Solve for models with multi-knot GeneralConstraint rows: the filter line-search SQP iteration of the other paths, driven
 // from the host like the wide-stage solver, with bordered_step as its linear solver.  Scope: equality rows (dynamics, stage,
-// general), inequality rows among the general rows (slacks, on the host over n_g <= 16 entries) and variable bounds: free, fixed
-// by equal bounds, or finite on either side.  Finite bounds are a primal-dual barrier with the bound multipliers eliminated, as in
+// general), inequality rows c <= 0 among the general rows (slacks, on the host over n_g <= 16 entries) and among the rows of stage
+// Constraints (lane path, device border: slacks on the device, BorderSlack -- k_border_slack_init / _stats / _update, the shifted
+// sums of k_border_stats and k_border_trial, s / nu through dto_kkt_system.sigma_c), shared or per-instance parameters, and
+// variable bounds: free, fixed by equal bounds, or finite on either side.  One barrier parameter per instance serves all of them.
+// Finite bounds are a primal-dual barrier with the bound multipliers eliminated, as in
 // wide_outer: z_L / z_U live on the device as [B][Nz], the barrier terms of the KKT system are written by the step's own kernels
 // (BorderBar), k_border_bar_stats reduces what the host rules need to eight numbers per instance that ride the copy of
 // k_border_stats, k_border_trial adds sum log(gap) of a trial point to the launch that sums its violation, and
@@ -2477,24 +2504,33 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   if (rc) return rc;
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc;
+  // per-instance parameters (dto_batch.params, [B][ldp]): every callback of this loop and both linear solvers read the instance's own
+  // (dto_kkt_assemble / wide_kkt_assemble take them from the batch at every call, a further delta_w attempt at the same point included)
+  if (b->params && L.Nw > 0 && b->ldp < L.Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
   // finite bound sides of the variables that are not fixed (the tests of k_wide_init_bounds: a side is finite inside +-1e300)
   int64_t n_bound = 0;
   for (int64_t i = 0; i < Nz; ++i)
     if (L.var_lo[i] != L.var_hi[i]) n_bound += (L.var_lo[i] > -1e300 ? 1 : 0) + (L.var_hi[i] < 1e300 ? 1 : 0);
   const bool bounds = n_bound > 0;
   // inequality rows (c <= 0: src/general_constraint.jl:15-19 `indices_inequality`) among the GENERAL rows are carried with slacks
-  // g_i + s_i = 0, s_i >= 0 (round 4): the border's diagonal gets s_i / nu_i, its right-hand side mu / nu_i; dynamics and stage
-  // rows stay equalities on this path
+  // g_i + s_i = 0, s_i >= 0 (round 4): the border's diagonal gets s_i / nu_i, its right-hand side mu / nu_i.  Inequality rows of
+  // stage Constraints get the same elimination with their slacks on the device (BorderSlack: about T of them per instance), s / nu
+  // through dto_kkt_system.sigma_c; dynamics rows are equalities
   const int64_t ng = L.Ngen, Ns = Nc - ng;
   std::vector<char> ineq((size_t)std::max<int64_t>(1, ng), 0);
-  int64_t ni = 0;
+  std::vector<int> smask;
+  int64_t ni = 0, nsi = 0;
   for (int64_t i = 0; i < Nc; ++i) {
     if (L.con_lo[i] == L.con_hi[i]) continue;
-    if (i < Ns || !(L.con_hi[i] == 0.0) || std::isfinite(L.con_lo[i]))
-      return set_error(DTO_ERR_UNSUPPORTED, "GeneralConstraint solve path: equality rows, and inequality rows (c <= 0) among the general rows only");
-    ineq[(size_t)(i - Ns)] = 1; ++ni;
+    if (i < L.Ndyn || !(L.con_hi[i] == 0.0) || std::isfinite(L.con_lo[i]))
+      return set_error(DTO_ERR_UNSUPPORTED, "GeneralConstraint solve path: equality rows and inequality rows c <= 0");
+    if (i < Ns) {
+      if (smask.empty()) smask.assign((size_t)Ns, 0);
+      smask[(size_t)i] = 1; ++nsi;
+    } else {
+      ineq[(size_t)(i - Ns)] = 1; ++ni;
+    }
   }
-  if (b->params) return set_error(DTO_ERR_UNSUPPORTED, "GeneralConstraint solve path: shared parameters only");
   dto_options u;
   if (opt) u = *opt; else dto_options_default(&u);
   dto_solver_opts o;
@@ -2505,7 +2541,12 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   DevBuf<double> z, lam, dz, dlam, zt, df, dc, dal, dth;
   DevBuf<double> dgd, dgs, dst, dnu;   // [B][ng]: s / nu, mu / nu, trial slacks, multipliers of the general rows
   DevBuf<double> d5;                   // [B][5] statistics of the point and the step; with bounds [B][BORDER_BAR_NSTAT] behind them
-  DevBuf<double> zl, zu, dlo, dhi, dmub, dad;   // finite bounds only: multipliers [B][Nz], shared bounds [Nz], mu and alpha_d [B]
+  DevBuf<double> zl, zu, dlo, dhi, dmub, dad;   // finite bounds only: multipliers [B][Nz], shared bounds [Nz]; mu and alpha_d [B]: those
+                                                // and inequality stage rows
+  DevBuf<double> ss, sds;                       // inequality stage rows only: slacks and their step [B][Ns]
+  DevBuf<int> dsmask;                           //   and the 0/1 mask of those rows [Ns]
+  const bool bounds_or_slk = bounds || nsi > 0;
+  const int nth = nsi > 0 ? 3 : (bounds ? 2 : 1);   // numbers per instance of a trial point (k_rows_abs_sum / k_border_trial)
   HIP_TRY(z.alloc((size_t)B * Nz));
   HIP_TRY(lam.alloc((size_t)B * Nc));
   HIP_TRY(dz.alloc((size_t)B * Nz));
@@ -2514,11 +2555,16 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   HIP_TRY(df.alloc((size_t)B));
   HIP_TRY(dc.alloc((size_t)B * Nc));
   HIP_TRY(dal.alloc((size_t)B));
-  HIP_TRY(dth.alloc((size_t)B * (bounds ? 2 : 1)));   // (with bounds: theta and sum log(gap) of a trial point)
+  HIP_TRY(dth.alloc((size_t)B * nth));   // (with bounds: theta and sum log(gap) of a trial point; with stage slacks sum log(s) behind)
   if (ni > 0) {
     for (DevBuf<double>* q : {&dgd, &dgs, &dst, &dnu}) HIP_TRY(q->alloc((size_t)B * ng));
   }
+  if (bounds_or_slk) {
+    HIP_TRY(dmub.alloc((size_t)B));
+    HIP_TRY(dad.alloc((size_t)B));
+  }
   BorderBar bar;
+  BorderSlack slk;
   std::vector<double> hz;
   if (bounds) {
     // the guess pushed inside the bounds, fixed variables on their values, z_L / z_U on the central path of mu_init: the cold
@@ -2527,8 +2573,6 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     HIP_TRY(zu.alloc((size_t)B * Nz));
     HIP_TRY(dlo.alloc((size_t)Nz));
     HIP_TRY(dhi.alloc((size_t)Nz));
-    HIP_TRY(dmub.alloc((size_t)B));
-    HIP_TRY(dad.alloc((size_t)B));
     HIP_TRY(hipMemcpyAsync(dlo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dhi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpy2DAsync(z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
@@ -2547,24 +2591,36 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     HIP_TRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
   HIP_TRY(hipMemsetAsync(lam, 0, (size_t)B * Nc * sizeof(double), st));
-  using Inst = GlobInst;   // (mu: finite bounds and inequality general rows)
+  using Inst = GlobInst;   // (mu: finite bounds, inequality general rows and inequality stage rows share one per instance)
   std::vector<Inst> I((size_t)B);
-  const bool barrier = bounds || ni > 0;
+  const bool barrier = bounds || ni > 0 || nsi > 0;
   if (barrier)
     for (int64_t i = 0; i < B; ++i) I[(size_t)i].mu = o.mu_init;
-  std::vector<double> hmu((size_t)(bounds ? B : 0)), had((size_t)(bounds ? B : 0));
+  std::vector<double> hmu((size_t)(bounds_or_slk ? B : 0)), had((size_t)(bounds_or_slk ? B : 0));
   // slacks and multipliers of the general rows on the host (the multipliers are mirrored into lam after every update)
   std::vector<double> hs((size_t)B * std::max<int64_t>(1, ng), 0.0), hnu((size_t)B * std::max<int64_t>(1, ng), 0.0), hds((size_t)B * std::max<int64_t>(1, ng), 0.0);
   std::vector<double> hgd((size_t)B * std::max<int64_t>(1, ng), 0.0), hgs((size_t)B * std::max<int64_t>(1, ng), 0.0), hst((size_t)B * std::max<int64_t>(1, ng), 0.0);
-  std::vector<double> dwv((size_t)B), hf((size_t)B), hth((size_t)B * (bounds ? 2 : 1)), hal((size_t)B), hphi0((size_t)B);
+  std::vector<double> dwv((size_t)B), hf((size_t)B), hth((size_t)B * nth), hal((size_t)B), hphi0((size_t)B);
   std::vector<int> okv((size_t)B);
   constexpr int TRIALS = DTO_LS_TRIALS;
   dto_batch bz = *b;
-  bz.x = z; bz.ldx = Nz; bz.params = nullptr; bz.ldp = 0;
+  bz.x = z; bz.ldx = Nz;   // (params / ldp stay the caller's: the point, the trials, the slack initialisation and bordered_step)
   auto put_nu = [&]() -> int {   // host multipliers of the general rows -> their columns of lam
     HIP_TRY(hipMemcpy2DAsync(lam + Ns, Nc * sizeof(double), hnu.data(), ng * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
     return DTO_OK;
   };
+  if (nsi > 0) {
+    // the same start for the slacks of the inequality stage rows, on the device: s = max(-c, 1e-2), nu = 1 in their entries of lam
+    HIP_TRY(ss.alloc((size_t)B * Ns));
+    HIP_TRY(sds.alloc((size_t)B * Ns));
+    HIP_TRY(dsmask.alloc((size_t)Ns));
+    HIP_TRY(hipMemcpyAsync(dsmask, smask.data(), (size_t)Ns * sizeof(int), hipMemcpyHostToDevice, st));
+    slk.s = ss; slk.ds = sds; slk.mask = dsmask; slk.mu = dmub; slk.Ns = Ns;
+    if ((rc = dto_eval_g_batch(h, &bz, dc, Nc))) return rc;
+    hipLaunchKernelGGL(k_border_slack_init, dim3((unsigned)(((size_t)B * Ns + 255) / 256)), dim3(256), 0, st, B, Nc, slk, (const double*)dc,
+                       (double*)lam);
+    HIP_TRY(hipGetLastError());
+  }
   if (ni > 0) {
     // slacks from the constraint values at the guess, pushed inside (s >= 1e-2), multipliers 1 (Ipopt's bound_mult_init_val), mu_init
     if ((rc = dto_eval_g_batch(h, &bz, dc, Nc))) return rc;
@@ -2593,7 +2649,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       HIP_TRY(hipMemcpyAsync(dgd, hgd.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(dgs, hgs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
     }
-    if (bounds) {   // the barrier parameter the step is computed with
+    if (bounds_or_slk) {   // the barrier parameter the step is computed with
       for (int64_t i = 0; i < B; ++i) hmu[(size_t)i] = I[(size_t)i].mu;
       HIP_TRY(hipMemcpyAsync(dmub, hmu.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
     }
@@ -2603,7 +2659,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     for (int attempt = 0;; ++attempt) {
       bs.reuse_point = attempt > 0;
       if ((rc = bordered_step(p, &bz, lam, Nc, dwv.data(), o.delta_c, dz, Nz, dlam, Nc, okv.data(), &bs, true, ni > 0 ? dgd : nullptr, ni > 0 ? dgs : nullptr,
-                              bounds ? &bar : nullptr))) return rc;
+                              bounds ? &bar : nullptr, nsi > 0 ? &slk : nullptr))) return rc;
       bool again = false;
       for (int64_t i = 0; i < B; ++i) {
         Inst& s = I[(size_t)i];
@@ -2618,14 +2674,19 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     if (dev_stats) {
       // device border: five numbers per instance (and the steps of the general rows' multipliers) instead of five vectors
       // (with bounds BORDER_BAR_NSTAT more behind them, in the same buffer and the same copy)
-      const size_t n5 = (size_t)B * 5, nstat = n5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0);
+      // (with inequality stage rows BORDER_SLK_NSTAT more behind those)
+      const size_t n5 = (size_t)B * 5, nbar = n5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0),
+                   nstat = nbar + (nsi > 0 ? (size_t)B * BORDER_SLK_NSTAT : 0);
       if (!d5) HIP_TRY(d5.alloc(nstat));
       if (ni > 0) HIP_TRY(hipMemcpyAsync(dst, hs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));   // slack shift of theta
       hipLaunchKernelGGL(k_border_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, Nc, bs.d_c, bs.d_rx, bs.d_grad, (const double*)dz, (const double*)lam,
-                         (const int*)p->d_var_fixed, (const double*)(ni > 0 ? dst : nullptr), Ns, ng, d5);
+                         (const int*)p->d_var_fixed, (const double*)(ni > 0 ? dst : nullptr), Ns, ng, d5, (const double*)slk.s, slk.Ns);
       if (bounds)
         hipLaunchKernelGGL(k_border_bar_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, bar, (const double*)dz, bs.d_rx, (const int*)p->d_var_fixed,
                            o.tau_min, d5 + n5);
+      if (nsi > 0)
+        hipLaunchKernelGGL(k_border_slack_stats, dim3((unsigned)B), dim3(64), 0, st, Nc, slk, (const double*)lam, (const double*)dlam, o.tau_min,
+                           d5 + nbar);
       hst5.resize(nstat);
       HIP_TRY(hipMemcpyAsync(hst5.data(), d5, hst5.size() * sizeof(double), hipMemcpyDeviceToHost, st));
       if (ng > 0) {
@@ -2683,9 +2744,18 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
         return std::max(qb[BORDER_BAR_SZMAX] - mu_at, mu_at - szmin);
       };
       if (bounds) { dinf = qb[BORDER_BAR_DINF]; c0 = std::max(c0, compl_bounds(o.mu_target)); }
+      // inequality stage rows: the same two extremes of s nu from the device (nsi > 0 implies the device border), their ds / s in
+      // the merit's directional derivative exactly as the general rows' slacks
+      const double* qs = nsi > 0 ? &hst5[(size_t)B * 5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0) + (size_t)i * BORDER_SLK_NSTAT] : nullptr;
+      auto compl_slack = [&](double mu_at) {
+        if (!qs) return 0.0;
+        const double snumin = qs[BORDER_SLK_ISNUMAX] > 0.0 ? 1.0 / qs[BORDER_SLK_ISNUMAX] : 1e300;
+        return std::max(qs[BORDER_SLK_SNUMAX] - mu_at, mu_at - snumin);
+      };
+      if (qs) { c0 = std::max(c0, compl_slack(o.mu_target)); snu += qs[BORDER_SLK_SUMNU]; bar_d += qs[BORDER_SLK_DSS]; }
       // (the slack's bound multiplier of a slack-eliminated row IS its nu: it counts among the bound multipliers, as the slack
       //  multipliers do in conv_body)
-      const ErrScale es = ipopt_scaling(o, slam, Nc, snu + (bounds ? qb[BORDER_BAR_SUMZ] : 0.0), ni + n_bound);
+      const ErrScale es = ipopt_scaling(o, slam, Nc, snu + (bounds ? qb[BORDER_BAR_SUMZ] : 0.0), ni + n_bound + nsi);
       const IterMeasures m{hf[(size_t)i], th1, thinf, dinf, std::max(std::max(dinf / es.sd, thinf), c0 / es.sc), c0};
       mu_moved[(size_t)i] = 0;
       s.status = terminal_status(o, s.iter, m, 0);   // acc_count = 0: no acceptable-level termination on this path
@@ -2693,7 +2763,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
         // Ipopt's monotone rule: once the barrier problem is solved to kappa_eps mu the parameter drops (and the filter is reset);
         // the step computed above belongs to the old mu: this instance waits one round (alpha = 0) for the step of the new one
         const double mu = monotone_mu(o, s.mu, std::max(dinf / es.sd, thinf), es.sc, [&](double mu_at) {
-          double c = compl_bounds(mu_at);
+          double c = std::max(compl_bounds(mu_at), compl_slack(mu_at));
           for (int64_t q = 0; q < ng; ++q)
             if (ineq[(size_t)q]) c = std::max(c, std::fabs(hs[(size_t)(i * ng + q)] * hnu[(size_t)(i * ng + q)] - mu_at));
           return c;
@@ -2729,6 +2799,11 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
         apmax[(size_t)i] = qb[BORDER_BAR_APMAX]; admax[(size_t)i] = qb[BORDER_BAR_ADMAX];
         hphi0[(size_t)i] -= s.mu * qb[BORDER_BAR_LOGBAR];
       }
+      if (nsi > 0) {   // the slacks of the inequality stage rows: the same three numbers
+        const double* qs = &hst5[(size_t)B * 5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0) + (size_t)i * BORDER_SLK_NSTAT];
+        apmax[(size_t)i] = std::min(apmax[(size_t)i], qs[BORDER_SLK_APMAX]); admax[(size_t)i] = std::min(admax[(size_t)i], qs[BORDER_SLK_ADMAX]);
+        hphi0[(size_t)i] -= s.mu * qs[BORDER_SLK_LOGS];
+      }
       if (ni == 0) continue;
       const double tau = std::max(o.tau_min, 1.0 - s.mu);
       double lb = 0.0;
@@ -2763,9 +2838,11 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       bt.x = zt;
       if ((rc = dto_eval_f_batch(h, &bt, df))) return rc;
       if ((rc = dto_eval_g_batch(h, &bt, dc, Nc))) return rc;
-      if (bounds)   // the violation and sum log(gap) of the trial point in one launch, both in the copy of theta
+      if (bounds_or_slk)   // the violation and sum log(gap) of the trial point in one launch, both in the copy of theta (with inequality
+                           // stage rows: their slacks at alpha in the violation, and sum log of them as a third number)
         hipLaunchKernelGGL(k_border_trial, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, (const double*)(ni > 0 ? dst : nullptr), Ns, ng,
-                           (const double*)zt, Nz, (const double*)dlo, (const double*)dhi, (double*)dth);
+                           (const double*)(bounds ? (double*)zt : nullptr), Nz, (const double*)dlo, (const double*)dhi, (double*)dth, slk,
+                           (const double*)dal);
       else
         hipLaunchKernelGGL(k_rows_abs_sum, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, dth, (const double*)(ni > 0 ? dst : nullptr), Ns, ng);
       HIP_TRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2775,8 +2852,9 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
         Inst& s = I[(size_t)i];
         if (s.status != 0 || chosen_a[(size_t)i] >= 0.0) continue;
         double pk = hf[(size_t)i];
-        const double tk = bounds ? hth[(size_t)(2 * i)] : hth[(size_t)i];
-        if (bounds) pk -= s.mu * hth[(size_t)(2 * i + 1)];
+        const double tk = hth[(size_t)(nth * i)];
+        if (bounds) pk -= s.mu * hth[(size_t)(nth * i + 1)];
+        if (nsi > 0) pk -= s.mu * hth[(size_t)(nth * i + 2)];
         for (int64_t q = 0; q < ng && ni > 0; ++q)
           if (ineq[(size_t)q]) pk -= s.mu * std::log(hst[(size_t)(i * ng + q)]);
         note_most_feasible(best_a[(size_t)i], k, tk);
@@ -2795,17 +2873,23 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       s.iter++;
     }
     HIP_TRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    if (bounds_or_slk) {
+      for (int64_t i = 0; i < B; ++i) had[(size_t)i] = hal[(size_t)i] == 0.0 ? 0.0 : admax[(size_t)i];
+      HIP_TRY(hipMemcpyAsync(dad, had.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    }
     if (bounds) {
       // bound multipliers first (their update reads the old point): alpha_d^max with the kappa_Sigma clamp against the instance's
       // mu; an instance that takes no step (terminated, or its mu just moved) keeps them
-      for (int64_t i = 0; i < B; ++i) had[(size_t)i] = hal[(size_t)i] == 0.0 ? 0.0 : admax[(size_t)i];
-      HIP_TRY(hipMemcpyAsync(dad, had.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_wide_update_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (const double*)z, (const double*)dz,
                          (double*)zl, (double*)zu, (const double*)dlo, (const double*)dhi, (int64_t)0, (const double*)dal, (const double*)dad,
                          (const double*)dmub, Nz);
     }
     hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)dal, Nz, Nz, Nz);
-    hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, lam, (const double*)dlam, (const double*)dal, Nc, Nc, Nc);
+    if (nsi > 0)   // the multipliers of the inequality stage rows move with alpha_d and are clamped, their slacks with alpha; the other rows as below
+      hipLaunchKernelGGL(k_border_slack_update, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, Nc, slk, (double*)lam, (const double*)dlam,
+                         (const double*)dal, (const double*)dad, kappa_sigma, AXPY_BLOCKS_PER_ROW);
+    else
+      hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, lam, (const double*)dlam, (const double*)dal, Nc, Nc, Nc);
     if (ni > 0) {
       // general rows: equality multipliers move with the primal step, slack / multiplier pairs of the inequality rows with
       // alpha and the dual fraction-to-the-boundary step, then Ipopt's kappa_sigma safeguard; mirrored into lam

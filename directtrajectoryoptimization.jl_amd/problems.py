@@ -507,6 +507,39 @@ def build_pendulum_coupled(T=50, total=1.0, inequality=True, u_max=None, nonline
     return p
 
 
+def build_pendulum_speed_limit(T=50, v_max=3.35, row=None, total=1.0, u_max=None):
+    """The pendulum swing-up with an obstacle-style INEQUALITY stage row at every knot (examples/car/car.jl:53-60 puts one
+    `Constraint` with `indices_inequality` at every knot): thetadot^2 - v_max^2 <= 0, beside the endpoint equality rows.  Without
+    the row the speed peaks at 4.184.  row: None, or one GeneralConstraint row coupling knots 15 and 35 -- "sum<=0":
+    theta_15 + theta_35 - total <= 0; "product": theta_15 * theta_35 - total = 0 (no sum of one-knot terms: only the border carries
+    it; built without Hessians as build_pendulum_coupled(nonlinear=True)).  u_max: action bounds |u| <= u_max at every knot."""
+    from .model import GeneralConstraint
+    p = build_pendulum(T=T, evaluate_hessian=True)
+    n, m = 2, 1
+    x1, xT = p["x1"], p["xT"]
+    speed = lambda x: x[1] * x[1] - v_max ** 2.0
+    con1 = Constraint(lambda x, u, w: np.array(list(x - x1) + [speed(x)], dtype=object), n, m, indices_inequality=[n + 1], evaluate_hessian=True)
+    cont = Constraint(lambda x, u, w: np.array([speed(x)], dtype=object), n, m, indices_inequality=[1], evaluate_hessian=True)
+    conT = Constraint(lambda x, u, w: np.array(list(x - xT) + [speed(x)], dtype=object), n, 0, indices_inequality=[n + 1], evaluate_hessian=True)
+    p["constraints"] = [con1] + [cont] * (T - 2) + [conT]
+    if u_max is not None:
+        p["bounds"] = [Bound(n, m, action_lower=-u_max * np.ones(m), action_upper=u_max * np.ones(m))] * (T - 1) + [Bound(n, 0)]
+    nz = n * T + m * (T - 1)
+    i15, i35 = 14 * (n + m), 34 * (n + m)
+    p["general_constraint"] = None
+    if row == "sum<=0":
+        p["general_constraint"] = GeneralConstraint(lambda z, w: np.array([z[i15] + z[i35] - total], dtype=object), nz, 0,
+                                                    indices_inequality=[1], evaluate_hessian=True)
+    elif row == "product":
+        p["general_constraint"] = GeneralConstraint(lambda z, w: np.array([z[i15] * z[i35] - total], dtype=object), nz, 0,
+                                                    evaluate_hessian=False)   # src/general_constraint.jl:87 is broken
+    elif row is not None:
+        raise ValueError(row)
+    p["coupling"] = (i15, i35, total)
+    p["v_max"] = v_max
+    return p
+
+
 def build_acrobot_coupled(T=8):
     """The acrobot (nonlinear dynamics, pinned endpoints) with two GeneralConstraint rows that couple knots: q1 at knot 3 minus
     q1 at knot 6 equals 0.2; q2 at knots 2 and 7 plus the action at knot 4 add up to zero.  Used for the bordered KKT step."""
@@ -577,6 +610,30 @@ def build_mpc_pendulum(T=30, x1=(0.0, 0.0), goal=PI):
                 constraints=[con1] + [Constraint() for _ in range(T - 2)] + [conT],
                 bounds=[Bound(n, m)] * (T - 1) + [Bound(n, 0)], parameters=[w.copy() for _ in range(T)],
                 T=T, n=n, m=m, nw=nw, evaluate_hessian=True)
+
+
+def build_mpc_pendulum_coupled(T=50, x1=(0.0, 0.0), goal=PI, total=1.0):
+    """build_mpc_pendulum with a fourth parameter per knot, w_t = [x1_0, x1_1, goal, total], and one GeneralConstraint row that
+    couples knots 15 and 35 with that parameter on its right-hand side: theta_15 + theta_35 - total <= 0, `total` being entry 3 of
+    the flattened parameter vector the general row is handed (src/moi.jl:48,68).  A row that reads w rides no accumulator state
+    (solver.py: accumulate_general_constraint), so it always takes the bordered path -- where instances of one batch differ
+    through dto_batch.params (a per-rollout budget)."""
+    from .model import GeneralConstraint
+    n, m, nw = 2, 1, 4
+    dt = Dynamics(lambda y, x, u, w: pendulum_midpoint(y, x, u, w), n, n, m, num_parameter=nw, evaluate_hessian=True)
+    ct = Cost(lambda x, u, w: 0.1 * dot(x, x) + 0.1 * dot(u, u), n, m, num_parameter=nw, evaluate_hessian=True)
+    cT = Cost(lambda x, u, w: 0.1 * dot(x, x), n, 0, num_parameter=nw, evaluate_hessian=True)
+    con1 = Constraint(lambda x, u, w: x - w[0:2], n, m, num_parameter=nw, evaluate_hessian=True)
+    conT = Constraint(lambda x, u, w: np.array([x[0] - w[2], x[1]], dtype=object), n, 0, num_parameter=nw, evaluate_hessian=True)
+    w = np.array([x1[0], x1[1], goal, total], dtype=float)
+    nz = n * T + m * (T - 1)
+    i15, i35 = 14 * (n + m), 34 * (n + m)
+    gc = GeneralConstraint(lambda z, w: np.array([z[i15] + z[i35] - w[3]], dtype=object), nz, nw * T, indices_inequality=[1],
+                           evaluate_hessian=True)
+    return dict(dynamics=[dt] * (T - 1), objective=[ct] * (T - 1) + [cT],
+                constraints=[con1] + [Constraint() for _ in range(T - 2)] + [conT],
+                bounds=[Bound(n, m)] * (T - 1) + [Bound(n, 0)], parameters=[w.copy() for _ in range(T)],
+                general_constraint=gc, coupling=(i15, i35, 3), T=T, n=n, m=m, nw=nw, evaluate_hessian=True)
 
 
 def build_mpc_acrobot_padded(T=30, n=24, x1=None, target=PI, u_max=None):

@@ -1317,9 +1317,9 @@ def accumulate_general_constraint(dynamics, objective, constraints, bounds, gene
         s_T + e_{r,T}(x_T) + const  (= | <=) 0   as one more stage-constraint row of the last knot;
     rows that touch one knot only (the reference's own use, test/solve.jl:273) join that knot's stage constraint as
     fold_general_constraint does.  The problem then has no general rows at all: it runs the lane-per-instance solver loop on the
-    device at full speed -- no border, no host-driven filter loop --, with stage inequalities and the limited-memory mode beside
-    the rows, neither of which the bordered path (csrc/dto_solver.cpp: general_solve_batch) has (variable bounds it takes).  The
-    multiplier of a coupling row is the multiplier of its last-knot row.
+    device at full speed -- no border, no host-driven filter loop --, with warm starts and the limited-memory mode beside the
+    rows, neither of which the bordered path (csrc/dto_solver.cpp: general_solve_batch) has (variable bounds, inequality stage rows
+    and per-instance parameters it takes).  The multiplier of a coupling row is the multiplier of its last-knot row.
 
     Returns (dynamics, objective, constraints, bounds, zmap, mumap, musign) in the convention of pad_to_wide, or None when a row is
     not additively separable over the knots (a product of variables of two knots, ...), reads parameters, or the state would

@@ -384,13 +384,18 @@ int dto_kkt_border_solve_refined(dto_problem* p, int passes, const double* rhs_x
  * Paths by model: lane-per-instance tiles (states <= 16; bounds, inequality rows, per-instance parameters); the tile (MFMA)
  * kernels for 64-state models (variables free, fixed or bounded; no stage constraints, one to four actions, shared or per-instance parameters;
  * 17..63-state models through their 64-state embedding; stepwise, warm-started and shifted solves through the entry points below); a
- * GeneralConstraint whose rows couple several knots is solved through a border (general rows equalities or inequalities,
- * dynamics / stage rows equalities, variables free, fixed or bounded on either side -- the problem's shared bounds, by a
- * primal-dual barrier whose bound multipliers are not returned; shared parameters only), the filter line-search loop around it
+ * GeneralConstraint whose rows couple several knots is solved through a border (general rows and the rows of stage Constraints
+ * equalities or inequalities c <= 0, variables free, fixed or bounded on either side -- the problem's shared bounds, by a
+ * primal-dual barrier whose bound multipliers are not returned; shared parameters or dto_batch.params, ldp < num_parameters being
+ * DTO_ERR_INVALID before anything is written; no warm start, no limited-memory mode), the filter line-search loop around it
  * driven from the host (dto_kkt_step_batch on such a problem stays the plain Newton step of the bordered system: no barrier
- * terms of the bounds in it):
+ * terms of the bounds or of inequality rows in it).  All barrier kinds of an instance -- bounds, slacks of inequality general
+ * rows, slacks of inequality stage rows -- share one barrier parameter; the multiplier of an inequality row comes back >= 0 in
+ * mu_out, the slacks are not returned:
  * - lane-per-instance path: one factorisation and n_g + 1 sweeps per step, the border algebra on the device since round 4
- *   (DTO_BORDER_HOST=1: on the host);
+ *   (DTO_BORDER_HOST=1: on the host -- equality rows and free or fixed variables only: bounds, inequality general rows and
+ *   inequality stage rows need the device border, DTO_ERR_UNSUPPORTED otherwise, as with more than 16 general rows); the slacks of
+ *   inequality stage rows stay on the device, s / nu enters through dto_kkt_system.sigma_c;
  * - tile path (a 64-state model with general rows, or a 17..63-state problem embedded with them): one stored factorisation, one
  *   panel substitution for all n_g rows and one bordered solve per step (dto_kkt_border_factor / dto_kkt_border_solve inside); at
  *   most 16 general rows (more: DTO_ERR_UNSUPPORTED), no stage rows.  dto_solve_batch, dto_solve and dto_kkt_step_batch take such a
