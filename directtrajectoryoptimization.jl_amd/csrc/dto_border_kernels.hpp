@@ -98,8 +98,9 @@ static_assert(4 * 256 <= KB_MAX * KB_LD, "the reduction of k_border_gram reuses 
 // below the diagonal, U on and above) and piv [B][16] (row exchanged with row k at step k); flags [2][B]: negdef, singular
 // (a pivot that is zero -- or not a number -- was met; the elimination of that column is skipped).  csym [B][256], stride 16, keeps
 // (C + C')/2 (zeros without c and beyond nb) for k_border_mul_fin.
+// skeep (optional, [B][256], stride 16): S before the elimination, for a caller that wants its eigenvalue signs (dto_kkt_lbfgs_border).
 static __global__ __launch_bounds__(64) void k_border_schur(int64_t B, int nb, int chunks, const double* part, const double* c, int64_t ldc,
-                                                            double* lu, int* piv, int* flags, double* csym) {
+                                                            double* lu, int* piv, int* flags, double* csym, double* skeep = nullptr) {
   __shared__ double P[256], S[256], L[256];
   const int64_t b = blockIdx.x;
   const int l = threadIdx.x;
@@ -120,6 +121,7 @@ static __global__ __launch_bounds__(64) void k_border_schur(int64_t B, int nb, i
     }
     S[i] = v;
     csym[b * 256 + i] = cs;
+    if (skeep) skeep[b * 256 + i] = v;
   }
   __syncthreads();
   if (l != 0) return;
@@ -292,6 +294,116 @@ static __global__ __launch_bounds__(64) void k_border_mul_fin(int nb, int chunks
   for (int ch = 0; ch < chunks; ++ch) acc += tpart[(b * chunks + ch) * KB_MAX + j];
   for (int q = 0; q < nb; ++q) acc += csym[b * 256 + j * 16 + q] * v_b[b * ldvb + q];
   out_b[b * ldob + j] = acc;
+}
+
+// ---- the compact limited-memory BFGS matrix as a border (dto_kkt_lbfgs_border; dto_kkt_kernels.hpp, "limited-memory BFGS"):
+//          B = sigma I - W M^-1 W',  W = [sigma S, Y],  M = [[sigma S'S, L], [L', -D]]   (L, D: strictly lower part / diagonal of S'Y)
+//      so K0 - [W; 0] M^-1 [W; 0]' is the Schur complement of the bordered matrix [K0 U; U' M] with U' = the panel below.
+// The panel of instance b: rows 0 .. m-1 = sigma_b s_j, rows m .. 2m-1 = y_j (pair j = row b * m + j of s and y, oldest first), the
+// rows of the pairs j >= npairs[b] zeros.  One thread per entry of the variables' part; the constraint part is cleared by the caller.
+static __global__ void k_lbfgs_panel(int64_t B, int m, int64_t Nz, const double* s, int64_t lds, const double* y, int64_t ldy,
+                                     const int* npairs, const double* sigma, double* g, int64_t ldg) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * m * Nz) return;
+  const int64_t row = idx / Nz, k = idx - row * Nz, b = row / m;
+  const int j = (int)(row - b * m);
+  const bool have = j < npairs[b];
+  g[(b * 2 * m + j) * ldg + k] = have ? sigma[b] * s[row * lds + k] : 0.0;
+  g[(b * 2 * m + m + j) * ldg + k] = have ? y[row * ldy + k] : 0.0;
+}
+// M of instance b from the Gram matrix of its panel (the partials of k_border_gram with the panel as both operands, summed in chunk
+// order): P = [[sigma^2 S'S, sigma S'Y], [sigma Y'S, Y'Y]].  c [B][4 m m], row-major.  A pair the instance does not have gets +1 on
+// the diagonal of the S block and -1 on that of the Y block: the Schur complement stays regular and keeps its inertia.
+static __global__ __launch_bounds__(64) void k_lbfgs_c(int m, int chunks, const double* part, const int* npairs, const double* sigma, double* c) {
+  __shared__ double P[256];
+  const int64_t b = blockIdx.x;
+  const int l = threadIdx.x, nb = 2 * m, np = npairs[b];
+  const double sg = sigma[b];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    double acc = 0.0;
+    for (int ch = 0; ch < chunks; ++ch) acc += part[(b * chunks + ch) * 256 + l + 64 * e];
+    P[l + 64 * e] = acc;
+  }
+  __syncthreads();
+  for (int i = l; i < nb * nb; i += 64) {
+    const int a = i / nb, q = i - a * nb;
+    double v;
+    if (a < m && q < m) {
+      v = (a < np && q < np) ? 0.5 * (P[a * 16 + q] + P[q * 16 + a]) / sg : (a == q ? 1.0 : 0.0);
+    } else if (a >= m && q >= m) {
+      v = a != q ? 0.0 : (a - m < np ? -P[(a - m) * 16 + a] / sg : -1.0);
+    } else {
+      const int si = a < m ? a : q, yj = (a < m ? q : a) - m;   // the entry s_si' y_yj of L (or of L')
+      v = (si > yj && si < np) ? P[si * 16 + m + yj] / sg : 0.0;
+    }
+    c[b * nb * nb + i] = v;
+  }
+}
+
+// ---- the secant pairs of the limited-memory mode in the bordered solve loop (dto_solver.cpp: general_solve_batch with a QnHistory).
+//      Instance-major, a thread owns a column, sums in a fixed order.
+// grad_x L(x, lam) without bound-multiplier terms = grad f + J' lam, columns through the CSC tables of k_border_point.
+__device__ __forceinline__ double qn_grad_l(int64_t b, int64_t col, int64_t nnzJ, const double* J, const double* g, int64_t Nz,
+                                            const double* lam, int64_t ldl, const int* cptr, const int* ck, const int* crow) {
+  double acc = g[b * Nz + col];
+  for (int e = cptr[col]; e < cptr[col + 1]; ++e) acc += J[b * nnzJ + ck[e]] * lam[b * ldl + crow[e]];
+  return acc;
+}
+// after an accepted step: s = alpha dz and gl = grad_x L(x_k, lam_{k+1}) from grad f and J of the OLD point (still in the step's
+// workspace) and the NEW multipliers.  alpha[b] == 0: the instance took no step, nothing of it is written.
+static __global__ void k_border_qn_save(int64_t B, int64_t Nz, int64_t nnzJ, const double* J, const double* g, const double* lam, int64_t ldl,
+                                 const int* cptr, const int* ck, const int* crow, const double* dz, const double* alpha, double* s, double* gl) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * Nz) return;
+  const int64_t b = idx / Nz, col = idx - b * Nz;
+  const double al = alpha[b];
+  if (al == 0.0) return;
+  s[idx] = al * dz[idx];
+  gl[idx] = qn_grad_l(b, col, nnzJ, J, g, Nz, lam, ldl, cptr, ck, crow);
+}
+// at the new point: y = grad_x L(x_{k+1}, lam_{k+1}) - gl (zero, with s, on a fixed variable), and dots [B][3] = s'y, s's, y'y:
+// one workgroup of 256 per instance, thread t adds columns t, t + 256, ... in that order, a shuffle tree, the four wavefront sums in
+// wavefront order.  pending[b] == 0: the instance has no saved step, nothing of it is written.
+static __global__ __launch_bounds__(256) void k_border_qn_y(int64_t Nz, int64_t nnzJ, const double* J, const double* g, const double* lam, int64_t ldl,
+                                                     const int* cptr, const int* ck, const int* crow, const int* fixed, const int* pending,
+                                                     double* s, const double* gl, double* y, double* dots) {
+  __shared__ double red[3][4];
+  const int64_t b = blockIdx.x;
+  if (!pending[b]) return;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  double sy = 0.0, ss = 0.0, yy = 0.0;
+  for (int64_t col = t; col < Nz; col += 256) {
+    const int64_t i = b * Nz + col;
+    double sv = s[i], yv = 0.0;
+    if (fixed[col]) { sv = 0.0; s[i] = 0.0; }
+    else yv = qn_grad_l(b, col, nnzJ, J, g, Nz, lam, ldl, cptr, ck, crow) - gl[i];
+    y[i] = yv;
+    sy += sv * yv; ss += sv * sv; yy += yv * yv;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { sy += __shfl_down(sy, off, 64); ss += __shfl_down(ss, off, 64); yy += __shfl_down(yy, off, 64); }
+  if (lane == 0) { red[0][wave] = sy; red[1][wave] = ss; red[2][wave] = yy; }
+  __syncthreads();
+  if (t < 3) dots[b * 3 + t] = ((red[t][0] + red[t][1]) + red[t][2]) + red[t][3];
+}
+// push the pair (s, y) of the instances with slot[b] >= 0 into their histories S, Y [B][m][Nz], oldest first: slot[b] = m drops the
+// oldest pair first (rows 1 .. m-1 move down, the new pair is row m-1), slot[b] < m writes row slot[b].  A thread owns a column of
+// an instance, so the move needs no barrier.
+static __global__ void k_border_qn_push(int64_t B, int m, int64_t Nz, const int* slot, const double* s, const double* y, double* S, double* Y) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * Nz) return;
+  const int64_t b = idx / Nz, col = idx - b * Nz;
+  int k = slot[b];
+  if (k < 0) return;
+  double* Sb = S + b * m * Nz + col;
+  double* Yb = Y + b * m * Nz + col;
+  if (k >= m) {
+    for (int j = 1; j < m; ++j) { Sb[(int64_t)(j - 1) * Nz] = Sb[(int64_t)j * Nz]; Yb[(int64_t)(j - 1) * Nz] = Yb[(int64_t)j * Nz]; }
+    k = m - 1;
+  }
+  Sb[(int64_t)k * Nz] = s[idx];
+  Yb[(int64_t)k * Nz] = y[idx];
 }
 
 // ---- finite variable bounds in the bordered solve loop (dto_solver.cpp: general_solve_batch): primal-dual barrier with the bound

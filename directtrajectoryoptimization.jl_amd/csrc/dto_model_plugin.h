@@ -13,7 +13,7 @@
 
 #include <stdint.h>
 
-#define DTO_PLUGIN_ABI 9
+#define DTO_PLUGIN_ABI 10
 
 #ifdef __cplusplus
 extern "C" {

@@ -190,13 +190,14 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
                          const double* gdiag = nullptr, const double* gshift = nullptr, const BorderBar* bar = nullptr,
                          const BorderSlack* slk = nullptr);
 static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
-                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
+                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs = false);
 
 // ---- wide-stage models, the linear solver alone: device copies of what dto_kkt_assemble was given.  The factor itself is in
 //      p->wide_fac, which dto_kkt_step_batch and the solver write too: each of them clears `factored`
 struct WideKkt {
   int64_t B = 0;
   bool assembled = false, factored = false, own_params = false, use_sigx = false, use_sigc = false;
+  bool first_order = false;      // dto_kkt_assemble_first_order: W = 0, the multipliers are not read (mu holds zeros)
   double delta_w = 0.0, delta_c = 0.0;
   DevBuf<double> z, mu, params, sigx, sigc;
   DevBuf<int> flags;             // [2][B]: inertia flags, negative-pivot counts
@@ -223,6 +224,9 @@ struct KktBorder {
   DevBuf<double> tpart;    // [B][chunks][16]: partial G v of k_border_mul
   DevBuf<double> ref_r, ref_d;   // [B][Nz + Nc + 16] each: residual and correction (or M sol) of dto_kkt_border_solve_refined, allocated
                                  // by its first call with passes > 0 or a residual norm to report
+  // ---- dto_kkt_lbfgs_border: M [B][nb * nb], the Schur complement before its LU [B][256], sigma [B] and the pair counts [B]
+  DevBuf<double> qc, skeep, qsig;
+  DevBuf<int> qnp;
 };
 // constraint rows of K as the border entry points see it: on the tile path the stage part (GeneralConstraint rows, the tail of
 // every constraint-side array, are neither read nor written there)
@@ -249,6 +253,7 @@ static inline void wide_args_no_linear(dto_wide_args& a) {
   a.rhs_x = a.rhs_c = nullptr; a.ldrx = a.ldrc = 0;
   a.nrhs = a.rhs0 = 0; a.ws = nullptr;
   a.kmul_s = 0;
+  a.first_order = 0;
 }
 
 // ---- wide-stage models (dto_wide_kernels.hpp): one workgroup per instance, AoS buffers used as they are
@@ -314,8 +319,9 @@ static void wide_kkt_args(Problem* p, dto_wide_args& a) {
   a.fixed_lo = a.fixed_hi = nullptr; a.ldb = 0; a.dw_inst = nullptr; a.gam_inst = nullptr; a.active = nullptr; a.stats = nullptr; a.merit = nullptr;
   a.zl = a.zu = nullptr; a.mu_inst = nullptr; a.tau_min = 0.99;
   wide_args_no_linear(a);
+  a.first_order = K.first_order ? 1 : 0;
 }
-static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_system* sys) {
+static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_system* sys, bool first_order = false) {
   int rc = p->ensure_device();
   if (rc) return rc;
   const Layout& L = p->L;
@@ -355,13 +361,15 @@ static int wide_kkt_assemble(Problem* p, const dto_batch* b, const dto_kkt_syste
     return hipMemcpy2DAsync(dst, pitch * sizeof(double), src, (size_t)ld * sizeof(double), n * sizeof(double), B, hipMemcpyDeviceToDevice, st);
   };
   HIP_TRY(copy(K.z, Nz, b->x, b->ldx));
-  if (Ns > 0) HIP_TRY(copy2(K.mu, Nc, Ns, sys->mu, sys->ldmu));
+  if (first_order) HIP_TRY(hipMemsetAsync(K.mu, 0, B * Nc * sizeof(double), st));   // (never part of a result: W = 0)
+  else if (Ns > 0) HIP_TRY(copy2(K.mu, Nc, Ns, sys->mu, sys->ldmu));
   if (K.own_params) HIP_TRY(copy(K.params, Nw, b->params, b->ldp));
   if (K.use_sigx) HIP_TRY(copy(K.sigx, Nz, sys->sigma_x, sys->ldsx));
   if (K.use_sigc) HIP_TRY(copy2(K.sigc, Nc, Ns, sys->sigma_c, sys->ldsc));
   // (dto_kkt_factor takes a stream of its own: the copies are complete when this returns)
   HIP_TRY(hipStreamSynchronize(st));
   K.B = b->B; K.delta_w = sys->delta_w; K.delta_c = sys->delta_c;
+  K.first_order = first_order;
   K.assembled = true;
   return DTO_OK;
 }
@@ -1997,7 +2005,41 @@ struct BorderStats {
   // device border: where grad f, c and r_x of the point lie in the problem's workspace (valid until the next step); the caller
   // fetches them -- and the step from its own buffers -- once per iteration instead of once per inertia-correction attempt
   const double *d_grad = nullptr, *d_c = nullptr, *d_rx = nullptr;
+  const double* d_J = nullptr;   // (tile path) the Jacobian values of the point, COO order, [B][nnzJ]
   bool reuse_point = false;   // in: the point did not move since the last call (another delta_w attempt): keep J, c, grad f, r_x, G
+  struct QnHistory* qn = nullptr;   // in (tile path, no general rows): the limited-memory mode -- the step is the compact L-BFGS one
+};
+
+// ---- limited-memory mode of the bordered loop on the tile path: the secant pairs of every instance on the device, the rules of
+//      Ipopt's limited-memory update (skip, reset, scalar1 initialisation) on the host -- qn_decide / qn_update of dto_kkt_kernels.hpp
+//      and of the CPU port.  The kernels are in dto_border_kernels.hpp (k_border_qn_save, k_border_qn_y, k_border_qn_push).
+struct QnHistory {
+  static constexpr int M = 6;      // pairs kept (Ipopt's limited_memory_max_history)
+  DevBuf<double> S, Y;             // [B][M][Nz], oldest first
+  DevBuf<double> s, gl, y;         // [B][Nz]: the saved step, grad_x L(x_k, lam_{k+1}), the new y
+  DevBuf<double> dots, rb, sb;     // [B][3]: s'y, s's, y'y; [B][16] each: the zero right-hand side and the unknowns of the border
+  DevBuf<int> flag;                // [2][B]: pending, slot
+  std::vector<int32_t> npairs;     // pairs in the history of each instance
+  std::vector<int> skipped, pending;
+  std::vector<double> sigma;
+  int init(int64_t B, int64_t Nz, hipStream_t st) {
+    const size_t hist = (size_t)B * M * (size_t)Nz;
+    for (DevBuf<double>* q : {&S, &Y})
+      if (const hipError_t e = q->alloc(hist); e != hipSuccess)
+        return hip_fail(e, ("limited-memory mode: hipMalloc of the history (" + std::to_string(2 * hist * sizeof(double)) + " bytes: " + std::to_string(B) +
+                            " instances x " + std::to_string(2 * M) + " vectors x " + std::to_string(Nz) + " doubles)").c_str());
+    for (DevBuf<double>* q : {&s, &gl, &y}) HIP_TRY(q->alloc((size_t)B * Nz));
+    HIP_TRY(dots.alloc((size_t)B * 3));
+    HIP_TRY(rb.alloc((size_t)B * 16));
+    HIP_TRY(sb.alloc((size_t)B * 16));
+    HIP_TRY(flag.alloc(2 * (size_t)B));
+    // (the panel kernel reads only the pairs an instance has, but the history starts defined)
+    HIP_TRY(hipMemsetAsync(S, 0, hist * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(Y, 0, hist * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(rb, 0, (size_t)B * 16 * sizeof(double), st));
+    npairs.assign((size_t)B, 0); skipped.assign((size_t)B, 0); pending.assign((size_t)B, 0); sigma.assign((size_t)B, 1.0);
+    return DTO_OK;
+  }
 };
 
 // ---- device side of the bordered step (round 4; DTO_BORDER_HOST=1 selects the host algebra of round 3 instead).  Only the
@@ -2262,6 +2304,49 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
   return DTO_OK;
 }
 
+// At a new point (J and grad f just evaluated there, lam the multipliers the step ended with): y and the three dot products of the
+// instances with a saved step, then the rules of the update -- a pair without curvature (s'y <= sqrt(eps) |s| |y|) is skipped, two
+// skips in a row drop the history, sigma = clamp(s'y / s's, 1e-8, 1e8) of the newest pair -- and the push.
+static int qn_update(Problem* p, QnHistory& Q, int64_t B, const double* dJ, const double* dG, const double* lam, int64_t ldl, hipStream_t st) {
+  bool any = false;
+  for (int v : Q.pending) any = any || v != 0;
+  if (!any) return DTO_OK;
+  const int64_t Nz = p->L.Nz, nnzJ = p->L.nnzJ;
+  int* dpend = Q.flag;
+  int* dslot = Q.flag + B;
+  HIP_TRY(hipMemcpyAsync(dpend, Q.pending.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_border_qn_y, dim3((unsigned)B), dim3(256), 0, st, Nz, nnzJ, dJ, dG, lam, ldl, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k,
+                     (const int*)p->d_csc_row, (const int*)p->d_var_fixed, (const int*)dpend, (double*)Q.s, (const double*)Q.gl, (double*)Q.y,
+                     (double*)Q.dots);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> hd((size_t)B * 3);
+  HIP_TRY(hipMemcpyAsync(hd.data(), Q.dots, hd.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<int> slot((size_t)B, -1);
+  bool push = false;
+  for (int64_t i = 0; i < B; ++i) {
+    if (!Q.pending[(size_t)i]) continue;
+    Q.pending[(size_t)i] = 0;
+    const double sy = hd[(size_t)i * 3], ss = hd[(size_t)i * 3 + 1], yy = hd[(size_t)i * 3 + 2];
+    if (!(sy > 1.4901161193847656e-08 * std::sqrt(ss) * std::sqrt(yy))) {
+      if (++Q.skipped[(size_t)i] >= 2) { Q.npairs[(size_t)i] = 0; Q.skipped[(size_t)i] = 0; }
+      continue;
+    }
+    Q.skipped[(size_t)i] = 0;
+    slot[(size_t)i] = Q.npairs[(size_t)i];   // (M: the oldest pair is dropped)
+    Q.npairs[(size_t)i] = std::min<int32_t>(QnHistory::M, Q.npairs[(size_t)i] + 1);
+    Q.sigma[(size_t)i] = std::min(1e8, std::max(1e-8, sy / ss));
+    push = true;
+  }
+  if (!push) return DTO_OK;
+  HIP_TRY(hipMemcpyAsync(dslot, slot.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_border_qn_push, dim3((unsigned)(((size_t)B * Nz + 255) / 256)), dim3(256), 0, st, B, (int)QnHistory::M, Nz, (const int*)dslot,
+                     (const double*)Q.s, (const double*)Q.y, (double*)Q.S, (double*)Q.Y);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));   // (slot is a local of this call)
+  return DTO_OK;
+}
+
 // ---- the bordered step on the tile path: the stage part is factorised ONCE into the stored records, the n_g border rows go
 //      through one panel substitution (dto_kkt_border_factor) and the step is one single substitution and two passes over Y
 //      (dto_kkt_border_solve) -- instead of the n_g + 1 sweeps of the lane path above.  Fixed variables (pin_fixed): sigma_x = 1e16,
@@ -2278,6 +2363,8 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
   hipStream_t st = (hipStream_t)b->stream;
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
   const BorderBar bar = barp ? *barp : BorderBar();   // (no bounds: all NULL, the kernels take their old branches)
+  QnHistory* qn = stats ? stats->qn : nullptr;
+  if (qn && ng != 0) return set_error(DTO_ERR_UNSUPPORTED, "limited-memory mode beside GeneralConstraint rows on the tile border");
   int rc = p->ensure_device();
   if (rc) return rc;
   if ((rc = ensure_border_csc(p))) return rc;
@@ -2293,6 +2380,7 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
     DRC(dto_eval_jac_g_batch(h, b, dJ, nnzJ));
     DRC(dto_eval_g_batch(h, b, dC, Nc));
     DRC(dto_eval_grad_f_batch(h, b, dG, Nz));
+    if (qn) DRC(qn_update(p, *qn, B, dJ, dG, mu, ldmu, st));   // the pair of the step that led here joins the history
   }
   // (the right-hand sides, the panel and C are written again at every attempt: one launch, and nothing to clear first)
   {
@@ -2303,23 +2391,35 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
     HIP_TRY(hipGetLastError());
   }
   // per-instance delta_w through the sigma_x diagonal (pin_fixed: a variable with lo == hi keeps its value)
-  HIP_TRY(hipMemcpyAsync(dDw, dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  // (limited-memory mode: sigma of the compact matrix rides the same diagonal)
+  std::vector<double> dws;
+  if (qn) {
+    dws.resize((size_t)B);
+    for (int64_t i = 0; i < B; ++i) dws[(size_t)i] = dw[i] + qn->sigma[(size_t)i];
+  }
+  HIP_TRY(hipMemcpyAsync(dDw, qn ? dws.data() : dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_border_sig, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw, (const int*)p->d_var_fixed,
                      pin_fixed ? 1 : 0, dSig, bar);
   dto_kkt_system sys;
   sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
   sys.delta_w = 0.0; sys.delta_c = delta_c;
-  DRC(wide_kkt_assemble(p, b, &sys));
+  DRC(wide_kkt_assemble(p, b, &sys, qn != nullptr));
   std::vector<int32_t> iok((size_t)B, 1), negdef((size_t)B, 1), sing((size_t)B, 0);
   DRC(wide_kkt_factor(p, iok.data(), nullptr, st));
-  DRC(dto_kkt_border_factor(h, ng, dPanel, Nz, nullptr, 0, dCb, ng * ng, negdef.data(), sing.data(), (void*)st));
-  DRC(dto_kkt_border_solve(h, dRhsx, Nz, dRhsc, Nc, dRhsb, ng, dx, lddx, dmu, lddmu, dmu + Ns, lddmu, (void*)st));
+  if (qn) {
+    // K0 = first-order system + (sigma + delta_w) I, the compact matrix as a border of 2 M rows; negdef carries inertia_ok
+    DRC(dto_kkt_lbfgs_border(h, QnHistory::M, qn->S, Nz, qn->Y, Nz, qn->npairs.data(), qn->sigma.data(), negdef.data(), sing.data(), (void*)st));
+    DRC(dto_kkt_border_solve(h, dRhsx, Nz, dRhsc, Nc, qn->rb, 16, dx, lddx, dmu, lddmu, qn->sb, 16, (void*)st));
+  } else {
+    DRC(dto_kkt_border_factor(h, ng, dPanel, Nz, nullptr, 0, dCb, ng * ng, negdef.data(), sing.data(), (void*)st));
+    DRC(dto_kkt_border_solve(h, dRhsx, Nz, dRhsc, Nc, dRhsb, ng, dx, lddx, dmu, lddmu, dmu + Ns, lddmu, (void*)st));
+  }
 #undef DRC
   if (pin_fixed) {
     hipLaunchKernelGGL(k_border_unpin, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const int*)p->d_var_fixed, dx, lddx);
     HIP_TRY(hipGetLastError());
   }
-  if (stats) { stats->d_grad = dG; stats->d_c = dC; stats->d_rx = dRxv; }
+  if (stats) { stats->d_grad = dG; stats->d_c = dC; stats->d_rx = dRxv; stats->d_J = dJ; }
   HIP_TRY(hipStreamSynchronize(st));
   if (ok_out)
     for (int64_t i = 0; i < B; ++i) ok_out[i] = (iok[(size_t)i] != 0 && negdef[(size_t)i] != 0 && sing[(size_t)i] == 0) ? 1 : 0;
@@ -2499,11 +2599,17 @@ static __global__ __launch_bounds__(64) void k_rows_abs_sum(const double* rows, 
 }
 
 static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
-                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations) {
+                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs) {
   int rc = p->ensure_device();
   if (rc) return rc;
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc;
+  // lbfgs: the limited-memory mode of the tile path (no general rows: the 12 border rows are the compact matrix).  Everything below is
+  // the loop as it stands for zero general rows; the step (bordered_step_tile) and the secant pairs after it are what differ
+  if (lbfgs && (!p->vt->launch_wide || L.Ngen != 0)) return set_error(DTO_ERR_UNSUPPORTED, "limited-memory bordered loop: tile path without GeneralConstraint rows");
+  if (lbfgs && b->B < 1) return set_error(DTO_ERR_INVALID, "empty batch");
+  if (lbfgs && (b->ldx < Nz || ldxo < Nz || (mu_out && ldmuo < Nc))) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (lbfgs && L.Nstage != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows, GeneralConstraint rows and bounds only");
   // per-instance parameters (dto_batch.params, [B][ldp]): every callback of this loop and both linear solvers read the instance's own
   // (dto_kkt_assemble / wide_kkt_assemble take them from the batch at every call, a further delta_w attempt at the same point included)
   if (b->params && L.Nw > 0 && b->ldp < L.Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
@@ -2591,6 +2697,11 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     HIP_TRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
   HIP_TRY(hipMemsetAsync(lam, 0, (size_t)B * Nc * sizeof(double), st));
+  QnHistory qn;   // (allocated in the limited-memory mode only; released on every return)
+  if (lbfgs) {
+    if ((rc = ensure_border_csc(p))) return rc;
+    if ((rc = qn.init(B, Nz, st))) return rc;
+  }
   using Inst = GlobInst;   // (mu: finite bounds, inequality general rows and inequality stage rows share one per instance)
   std::vector<Inst> I((size_t)B);
   const bool barrier = bounds || ni > 0 || nsi > 0;
@@ -2656,6 +2767,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     // ---- step at the current point: delta_w ladder per instance (Algorithm IC), all instances share the sweeps
     for (int64_t i = 0; i < B; ++i) dwv[(size_t)i] = I[(size_t)i].ls_fail ? ladder_after_ls_fail(o, I[(size_t)i].dlast) : 0.0;
     BorderStats bs;
+    bs.qn = lbfgs ? &qn : nullptr;
     for (int attempt = 0;; ++attempt) {
       bs.reuse_point = attempt > 0;
       if ((rc = bordered_step(p, &bz, lam, Nc, dwv.data(), o.delta_c, dz, Nz, dlam, Nc, okv.data(), &bs, true, ni > 0 ? dgd : nullptr, ni > 0 ? dgs : nullptr,
@@ -2909,6 +3021,15 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       }
       if ((rc = put_nu())) return rc;
     }
+    if (lbfgs) {
+      // the step just taken, and grad_x L at the point it left with the multipliers it arrived at: grad f and J of that point are
+      // still in the step's workspace.  An instance that took no step (alpha = 0) saves nothing and pushes nothing
+      hipLaunchKernelGGL(k_border_qn_save, dim3((unsigned)(((size_t)B * Nz + 255) / 256)), dim3(256), 0, st, B, Nz, L.nnzJ, bs.d_J, bs.d_grad,
+                         (const double*)lam, Nc, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row, (const double*)dz,
+                         (const double*)dal, (double*)qn.s, (double*)qn.gl);
+      HIP_TRY(hipGetLastError());
+      for (int64_t i = 0; i < B; ++i) qn.pending[(size_t)i] = hal[(size_t)i] != 0.0 ? 1 : 0;
+    }
     if (u.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > u.max_cpu_time) { timed_out = true; break; }
   }
   HIP_TRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), z, Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
@@ -2919,6 +3040,104 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
     if (iterations) iterations[i] = I[(size_t)i].iter;
   }
   return DTO_OK;
+}
+
+// ---- what dto_kkt_border_factor and dto_kkt_lbfgs_border share: the workspace of a border of nb rows (border_prepare), and, once
+//      the panel stands in W.g, Y = K^-1 G', the Schur complement and its LU (border_finish)
+struct BorderPlan {
+  int64_t B = 0, chunk = 0, n_c = 0;
+  int chunks = 0;
+};
+static int border_prepare(Problem* p, int64_t nb, bool has_gc, BorderPlan& P) {
+  const bool wide = p->vt->launch_wide != nullptr;
+  const int64_t Nz = p->L.Nz, Nc = kkt_rows(p), N = Nz + Nc;
+  int rc;
+  const int64_t B = wide ? p->wide_kkt->B : p->solver->B;
+  if (!p->kkt_border) p->kkt_border = new KktBorder();
+  KktBorder& W = *p->kkt_border;
+  W.valid = false;
+  // doubles of k per workgroup of k_border_gram, rounded up to the slab; read at every call so that a test can force several
+  // chunks on a small system (the sums of a result depend on it, nothing else does)
+  int64_t chunk = KB_CHUNK_DEFAULT;
+  if (const char* e = getenv("DTO_BORDER_GRAM_CHUNK")) {
+    const long long v = atoll(e);
+    if (v > 0) chunk = std::min<long long>(v, (long long)1 << 40);
+  }
+  chunk = (chunk + KB_KT - 1) / KB_KT * KB_KT;
+  const int64_t n_c = has_gc ? Nc : 0;   // without g_c the constraint part of every border row is zero: the product skips it
+  const int chunks = (int)((Nz + n_c + chunk - 1) / chunk);
+  const size_t rows = (size_t)B * (size_t)nb;
+  auto grow = [&](DevBuf<double>& buf, size_t need, const char* name, const std::string& shape) {
+    return grow_buf(buf, need, ("dto_kkt_border_factor: hipMalloc of " + std::string(name) + " (" + std::to_string(need * sizeof(double)) +
+                                " bytes: " + shape + ")").c_str());
+  };
+  const std::string panel = std::to_string(B) + " instances x " + std::to_string(nb) + " rows x " + std::to_string(N) + " doubles";
+  if ((rc = grow(W.g, rows * (size_t)N, "the border panel", panel))) return rc;
+  if ((rc = grow(W.y, rows * (size_t)N, "K^-1 G'", panel))) return rc;
+  if ((rc = grow(W.part, (size_t)B * (size_t)chunks * 256, "the partial products",
+                 std::to_string(B) + " instances x " + std::to_string(chunks) + " chunks x 256 doubles"))) return rc;
+  if ((rc = grow(W.lu, (size_t)B * 256, "the LU of the Schur complement", std::to_string(B) + " instances x 256 doubles"))) return rc;
+  if ((rc = grow(W.yw, (size_t)B * 16, "the border unknowns", std::to_string(B) + " instances x 16 doubles"))) return rc;
+  if ((rc = grow(W.v0, (size_t)B * (size_t)N, "K^-1 r", std::to_string(B) + " instances x " + std::to_string(N) + " doubles"))) return rc;
+  if ((rc = grow(W.csym, (size_t)B * 256, "the symmetric part of C", std::to_string(B) + " instances x 256 doubles"))) return rc;
+  if ((rc = grow(W.tpart, (size_t)B * (size_t)chunks * 16, "the partial products of G v",
+                 std::to_string(B) + " instances x " + std::to_string(chunks) + " chunks x 16 doubles"))) return rc;
+  if (const hipError_t e = W.iw.grow((size_t)B * 18); e != hipSuccess)
+    return hip_fail(e, ("dto_kkt_border_factor: hipMalloc of pivots and flags (" + std::to_string((size_t)B * 18 * sizeof(int)) + " bytes)").c_str());
+  P.B = B; P.chunk = chunk; P.chunks = chunks; P.n_c = n_c;
+  return DTO_OK;
+}
+static int border_finish(dto_problem* h, Problem* p, const BorderPlan& P, int64_t nb, const double* c, int64_t ldc, int32_t* schur_negdef,
+                         int32_t* schur_singular, double* skeep, hipStream_t st) {
+  KktBorder& W = *p->kkt_border;
+  const int64_t Nz = p->L.Nz, Nc = kkt_rows(p), N = Nz + Nc, B = P.B;
+  int rc;
+  if ((rc = dto_kkt_solve_multi(h, nb, W.g, N, W.g + Nz, N, W.y, N, W.y + Nz, N, (void*)st))) return rc;
+  int* piv = W.iw;
+  int* flags = W.iw + (size_t)B * 16;
+  hipLaunchKernelGGL(k_border_gram, dim3((unsigned)(B * P.chunks)), dim3(KB_THREADS), 0, st, (int)nb, Nz, P.n_c, P.chunk, P.chunks,
+                     (const double*)W.g, N, (const double*)(W.g + Nz), N, (const double*)W.y, N, (const double*)(W.y + Nz), N, W.part);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_border_schur, dim3((unsigned)B), dim3(64), 0, st, B, (int)nb, P.chunks, (const double*)W.part, c, ldc, W.lu, piv, flags,
+                     (double*)W.csym, skeep);
+  HIP_TRY(hipGetLastError());
+  // the panel and c have been consumed when this returns (and the flags are there)
+  std::vector<int> fl(2 * (size_t)B);
+  if (schur_negdef || schur_singular) HIP_TRY(hipMemcpyAsync(fl.data(), flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < B; ++i) {
+    if (schur_negdef) schur_negdef[i] = fl[(size_t)i];
+    if (schur_singular) schur_singular[i] = fl[(size_t)(B + i)];
+  }
+  W.nb = (int)nb; W.B = B;
+  W.chunk = P.chunk; W.chunks = P.chunks; W.n_c = P.n_c;
+  W.valid = true;
+  return DTO_OK;
+}
+// eigenvalue signs of a small symmetric matrix A (n x n, n <= 16, row stride 16) by cyclic Jacobi: the number of negative
+// eigenvalues; tiny = one of them is within 1e-13 of the largest entry of zero (the rule of the CPU port's limited-memory mode)
+static int small_inertia(const double* A, int n, bool& tiny) {
+  double M[16][16];
+  double scale = 0.0;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) { M[i][j] = A[i * 16 + j]; scale = std::max(scale, std::fabs(M[i][j])); }
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0;
+    for (int i = 0; i < n; ++i) for (int j = 0; j < i; ++j) off += M[i][j] * M[i][j];
+    if (off <= 1e-30 * scale * scale) break;
+    for (int a = 0; a < n; ++a)
+      for (int q = a + 1; q < n; ++q) {
+        if (std::fabs(M[a][q]) < 1e-300) continue;
+        const double th = (M[q][q] - M[a][a]) / (2.0 * M[a][q]);
+        const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0)), c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < n; ++k) { const double u = M[k][a], v = M[k][q]; M[k][a] = c * u - sn * v; M[k][q] = sn * u + c * v; }
+        for (int k = 0; k < n; ++k) { const double u = M[a][k], v = M[q][k]; M[a][k] = c * u - sn * v; M[q][k] = sn * u + c * v; }
+      }
+  }
+  int neg = 0;
+  tiny = false;
+  for (int i = 0; i < n; ++i) { if (M[i][i] < 0.0) ++neg; if (!(std::fabs(M[i][i]) > 1e-13 * scale)) tiny = true; }
+  return neg;
 }
 
 }  // namespace dto
@@ -3802,8 +4021,16 @@ int dto_solver_repack(dto_problem* h, int* num_running, void* stream) {
 int dto_solve_batch(dto_problem* h, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                     double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations) {
   Problem* p = reinterpret_cast<Problem*>(h);
-  // (the tile and the bordered paths have no limited-memory mode: they run the exact second derivatives of the traced
-  //  expressions whatever dto_options.hessian_approximation asks for, and dto_solver_hessian_mode reports it -- ADVICE r5)
+  // (the stepwise tile solver and the bordered paths with general rows have no limited-memory mode: they run the exact second
+  //  derivatives of the traced expressions whatever dto_options.hessian_approximation asks for, and dto_solver_hessian_mode
+  //  reports it -- ADVICE r5)
+  if (p && b && b->x && x_out && p->vt->launch_wide && p->L.Ngen == 0 && opt && opt->hessian_approximation == DTO_HESSIAN_LBFGS) {
+    // tile path, limited-memory mode: the host-driven bordered loop with the compact L-BFGS matrix as its border (no general rows).
+    // The stepwise state of the handle (dto_solver_begin ...) is not touched; the factor storage is taken, as by every solve
+    int rc = dto::general_solve_batch(p, opt, b, x_out, ldxo, mu_out, ldmuo, status, iterations, true);
+    if (rc == DTO_OK) p->hessian_mode_last = DTO_HESSIAN_LBFGS;
+    return rc;
+  }
   if (p && b && b->x && x_out && p->vt->launch_wide && p->L.Ngen == 0) {
     // tile path: begin + run on the state of the handle, which stays allocated for dto_solver_begin_warm / dto_solver_shift
     int rc = dto::wide_begin(p, opt, b, false, 0.0);
@@ -3898,6 +4125,17 @@ int dto_kkt_assemble(dto_problem* h, const dto_batch* b, const dto_kkt_system* s
   S.assembled = true;
   S.begun = false;
   return DTO_OK;
+}
+
+int dto_kkt_assemble_first_order(dto_problem* h, const dto_batch* b, const dto_kkt_system* sys) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p || !b || !b->x || !sys) return set_error(DTO_ERR_INVALID, "null argument");
+  if (!p->vt->launch_wide)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_assemble_first_order: tile path only (the lane-per-instance path keeps no assembled system: "
+                                          "its solver runs the limited-memory mode inside its sweeps)");
+  if (b->ldx < p->L.Nz) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if ((sys->sigma_x && sys->ldsx < p->L.Nz) || (sys->sigma_c && sys->ldsc < p->L.Nc)) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  return dto::wide_kkt_assemble(p, b, sys, true);
 }
 
 int dto_kkt_factor(dto_problem* h, int32_t* inertia_ok, int32_t* num_negative, void* stream) {
@@ -4026,39 +4264,11 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
   if (ldgx < Nz || (g_c && ldgc < p->L.Nc) || (c && ldc < nb * nb)) return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if (wide && !p->wide_kkt->factored)
     return set_error(DTO_ERR_INVALID, "dto_kkt_factor has not been called (or dto_kkt_step_batch / the solver has used the factor storage since)");
-  const int64_t B = wide ? p->wide_kkt->B : p->solver->B;
-  if (!p->kkt_border) p->kkt_border = new dto::KktBorder();
+  dto::BorderPlan P;
+  if ((rc = dto::border_prepare(p, nb, g_c != nullptr, P))) return rc;
   dto::KktBorder& W = *p->kkt_border;
-  W.valid = false;
-  // doubles of k per workgroup of k_border_gram, rounded up to the slab; read at every call so that a test can force several
-  // chunks on a small system (the sums of a result depend on it, nothing else does)
-  int64_t chunk = dto::KB_CHUNK_DEFAULT;
-  if (const char* e = getenv("DTO_BORDER_GRAM_CHUNK")) {
-    const long long v = atoll(e);
-    if (v > 0) chunk = std::min<long long>(v, (long long)1 << 40);
-  }
-  chunk = (chunk + dto::KB_KT - 1) / dto::KB_KT * dto::KB_KT;
-  const int64_t n_c = g_c ? Nc : 0;   // without g_c the constraint part of every border row is zero: the product skips it
-  const int chunks = (int)((Nz + n_c + chunk - 1) / chunk);
-  const size_t rows = (size_t)B * (size_t)nb;
-  auto grow = [&](dto::DevBuf<double>& buf, size_t need, const char* name, const std::string& shape) {
-    return dto::grow_buf(buf, need, ("dto_kkt_border_factor: hipMalloc of " + std::string(name) + " (" + std::to_string(need * sizeof(double)) +
-                                               " bytes: " + shape + ")").c_str());
-  };
-  const std::string panel = std::to_string(B) + " instances x " + std::to_string(nb) + " rows x " + std::to_string(N) + " doubles";
-  if ((rc = grow(W.g, rows * (size_t)N, "the border panel", panel))) return rc;
-  if ((rc = grow(W.y, rows * (size_t)N, "K^-1 G'", panel))) return rc;
-  if ((rc = grow(W.part, (size_t)B * (size_t)chunks * 256, "the partial products",
-                 std::to_string(B) + " instances x " + std::to_string(chunks) + " chunks x 256 doubles"))) return rc;
-  if ((rc = grow(W.lu, (size_t)B * 256, "the LU of the Schur complement", std::to_string(B) + " instances x 256 doubles"))) return rc;
-  if ((rc = grow(W.yw, (size_t)B * 16, "the border unknowns", std::to_string(B) + " instances x 16 doubles"))) return rc;
-  if ((rc = grow(W.v0, (size_t)B * (size_t)N, "K^-1 r", std::to_string(B) + " instances x " + std::to_string(N) + " doubles"))) return rc;
-  if ((rc = grow(W.csym, (size_t)B * 256, "the symmetric part of C", std::to_string(B) + " instances x 256 doubles"))) return rc;
-  if ((rc = grow(W.tpart, (size_t)B * (size_t)chunks * 16, "the partial products of G v",
-                 std::to_string(B) + " instances x " + std::to_string(chunks) + " chunks x 16 doubles"))) return rc;
-  if (const hipError_t e = W.iw.grow((size_t)B * 18); e != hipSuccess)
-    return dto::hip_fail(e, ("dto_kkt_border_factor: hipMalloc of pivots and flags (" + std::to_string((size_t)B * 18 * sizeof(int)) + " bytes)").c_str());
   hipStream_t st = (hipStream_t)stream;
+  const size_t rows = (size_t)P.B * (size_t)nb;
   // the panel of right-hand sides: row b * nb + j = [g_x row; g_c row or zeros]
   const size_t pitch = (size_t)N * sizeof(double);
   HIP_TRY(hipMemcpy2DAsync(W.g, pitch, g_x, (size_t)ldgx * sizeof(double), (size_t)Nz * sizeof(double), rows, hipMemcpyDeviceToDevice, st));
@@ -4066,26 +4276,75 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
     if (g_c) HIP_TRY(hipMemcpy2DAsync(W.g + Nz, pitch, g_c, (size_t)ldgc * sizeof(double), (size_t)Nc * sizeof(double), rows, hipMemcpyDeviceToDevice, st));
     else HIP_TRY(hipMemset2DAsync(W.g + Nz, pitch, 0, (size_t)Nc * sizeof(double), rows, st));
   }
-  if ((rc = dto_kkt_solve_multi(h, nb, W.g, N, W.g + Nz, N, W.y, N, W.y + Nz, N, stream))) return rc;
-  int* piv = W.iw;
-  int* flags = W.iw + (size_t)B * 16;
-  hipLaunchKernelGGL(dto::k_border_gram, dim3((unsigned)(B * chunks)), dim3(dto::KB_THREADS), 0, st, (int)nb, Nz, n_c, chunk, chunks,
-                     (const double*)W.g, N, (const double*)(W.g + Nz), N, (const double*)W.y, N, (const double*)(W.y + Nz), N, W.part);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dto::k_border_schur, dim3((unsigned)B), dim3(64), 0, st, B, (int)nb, chunks, (const double*)W.part, c, ldc, W.lu, piv, flags,
-                     (double*)W.csym);
-  HIP_TRY(hipGetLastError());
-  // g_x / g_c / c have been consumed when this returns (and the flags are there)
-  std::vector<int> fl(2 * (size_t)B);
-  if (schur_negdef || schur_singular) HIP_TRY(hipMemcpyAsync(fl.data(), flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  return dto::border_finish(h, p, P, nb, c, ldc, schur_negdef, schur_singular, nullptr, st);
+}
+
+// The compact limited-memory BFGS matrix as the border of the factorised system (dto_border_kernels.hpp: k_lbfgs_panel, k_lbfgs_c):
+// the panel [sigma S; Y] and M are formed on the device, then everything dto_kkt_border_factor runs.  The eigenvalue signs of M and
+// of the Schur complement come from cyclic Jacobi on the host, over the copies k_border_schur keeps (16 x 16 per instance).
+int dto_kkt_lbfgs_border(dto_problem* h, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy, const int32_t* npairs,
+                         const double* sigma, int32_t* inertia_ok, int32_t* schur_singular, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p) return set_error(DTO_ERR_INVALID, "null argument");
+  int rc = p->ensure_device();
+  if (rc) return rc;
+  if (!p->vt->launch_wide)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_lbfgs_border: tile path only (the lane-per-instance solver carries its limited-memory "
+                                          "matrix inside its sweeps)");
+  if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
+  if (m < 1) return set_error(DTO_ERR_INVALID, "dto_kkt_lbfgs_border: m < 1");
+  if (2 * m > dto::KB_MAX) return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_lbfgs_border: more than 8 pairs (16 border rows, one panel of right-hand sides)");
+  if (!s || !y || !sigma) return set_error(DTO_ERR_INVALID, "null argument");
+  const int64_t Nz = p->L.Nz, Nc = dto::kkt_rows(p), N = Nz + Nc, nb = 2 * m;
+  if (lds < Nz || ldy < Nz) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (!p->wide_kkt->factored)
+    return set_error(DTO_ERR_INVALID, "dto_kkt_factor has not been called (or dto_kkt_step_batch / the solver has used the factor storage since)");
+  const int64_t B = p->wide_kkt->B;
+  std::vector<int> hnp((size_t)B);
+  std::vector<double> hsig((size_t)B);
   for (int64_t i = 0; i < B; ++i) {
-    if (schur_negdef) schur_negdef[i] = fl[(size_t)i];
-    if (schur_singular) schur_singular[i] = fl[(size_t)(B + i)];
+    const int64_t np = npairs ? npairs[i] : m;
+    if (np < 0 || np > m) return set_error(DTO_ERR_INVALID, "dto_kkt_lbfgs_border: npairs outside 0..m");
+    if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i])) return set_error(DTO_ERR_INVALID, "dto_kkt_lbfgs_border: sigma must be positive and finite");
+    hnp[(size_t)i] = (int)np; hsig[(size_t)i] = sigma[i];
   }
-  W.nb = (int)nb; W.B = B;
-  W.chunk = chunk; W.chunks = chunks; W.n_c = n_c;
-  W.valid = true;
+  dto::BorderPlan P;
+  if ((rc = dto::border_prepare(p, nb, false, P))) return rc;
+  dto::KktBorder& W = *p->kkt_border;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = dto::grow_buf(W.qc, (size_t)B * 256, "dto_kkt_lbfgs_border: hipMalloc of the compact matrix"))) return rc;
+  if ((rc = dto::grow_buf(W.skeep, (size_t)B * 256, "dto_kkt_lbfgs_border: hipMalloc of the kept Schur complement"))) return rc;
+  if ((rc = dto::grow_buf(W.qsig, (size_t)B, "dto_kkt_lbfgs_border: hipMalloc of sigma"))) return rc;
+  HIP_TRY(W.qnp.grow((size_t)B));
+  HIP_TRY(hipMemcpyAsync(W.qnp, hnp.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(W.qsig, hsig.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  {
+    const size_t n = (size_t)B * (size_t)m * (size_t)Nz;
+    hipLaunchKernelGGL(dto::k_lbfgs_panel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, (int)m, Nz, s, lds, y, ldy, (const int*)W.qnp,
+                       (const double*)W.qsig, (double*)W.g, N);
+    HIP_TRY(hipGetLastError());
+  }
+  if (Nc > 0) HIP_TRY(hipMemset2DAsync(W.g + Nz, (size_t)N * sizeof(double), 0, (size_t)Nc * sizeof(double), (size_t)B * (size_t)nb, st));
+  // M from ONE Gram pass over the history: the panel as both operands (the partials are consumed by k_lbfgs_c before the Schur
+  // complement's own Gram pass writes them again, on the same stream)
+  hipLaunchKernelGGL(dto::k_border_gram, dim3((unsigned)(B * P.chunks)), dim3(dto::KB_THREADS), 0, st, (int)nb, Nz, (int64_t)0, P.chunk, P.chunks,
+                     (const double*)W.g, N, (const double*)nullptr, (int64_t)0, (const double*)W.g, N, (const double*)nullptr, (int64_t)0, (double*)W.part);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dto::k_lbfgs_c, dim3((unsigned)B), dim3(64), 0, st, (int)m, P.chunks, (const double*)W.part, (const int*)W.qnp,
+                     (const double*)W.qsig, (double*)W.qc);
+  HIP_TRY(hipGetLastError());
+  if ((rc = dto::border_finish(h, p, P, nb, W.qc, nb * nb, nullptr, schur_singular, W.skeep, st))) return rc;
+  if (inertia_ok) {
+    std::vector<double> hm((size_t)B * 256), hs((size_t)B * 256);
+    HIP_TRY(hipMemcpyAsync(hm.data(), W.csym, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hs.data(), W.skeep, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < B; ++i) {
+      bool tiny_m = false, tiny_s = false;
+      const int neg_m = dto::small_inertia(&hm[(size_t)i * 256], (int)nb, tiny_m), neg_s = dto::small_inertia(&hs[(size_t)i * 256], (int)nb, tiny_s);
+      inertia_ok[i] = (neg_m == neg_s && !tiny_m && !tiny_s) ? 1 : 0;
+    }
+  }
   return DTO_OK;
 }
 

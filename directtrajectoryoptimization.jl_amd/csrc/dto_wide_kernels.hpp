@@ -81,6 +81,9 @@ struct dto_wide_args {
   double* ws;                           // [B][T][multi_ws_stage] intermediates of one block (bx~, bd^, bu^ panels)
   // ---- K v (DTO_WIDE_KMUL): v travels in rhs_x / rhs_c, the product in dz / dmu, sigma_x / sigma_c as for DTO_WIDE_FACTOR
   int kmul_s;                           // stages per workgroup (0: DTO_WIDE_KMUL_S); 0 everywhere else
+  // ---- first-order system (dto_kkt_assemble_first_order): W = 0 in DTO_WIDE_FACTOR and DTO_WIDE_KMUL -- no second derivative of a
+  //      cost or a dynamics function is evaluated, their entries are zeros; 0 everywhere else
+  int first_order;
 };
 // stats: 0 f (barrier terms excluded), 1 theta_1, 2 theta_inf, 3 dual infeasibility, 4 grad phi' dz, 5 sum |lam|, 6/7 scratch,
 // 8 alpha_pmax, 9 alpha_dmax, 10 max s z, 11 max 1 / (s z), 12 sum z, 13 sum log s  (8..13 only with bounds)
@@ -959,12 +962,22 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
           DY::jac_var(xv, sc, yv, wp, jvv);
         } else if (w == 2) {
           if constexpr (DY::NH > 0) {
-            DY::hess(xv, sc, yv, wp, lamv, hv);
-            if (gam != 1.0 && l < DY::NH) hv[l] *= gam;
+            if (LIN && a.first_order) {   // (wave-uniform: the scatter below adds zeros)
+              for (int i = l; i < DY::NH; i += 64) hv[i] = 0.0;
+            } else {
+              DY::hess(xv, sc, yv, wp, lamv, hv);
+              if (gam != 1.0 && l < DY::NH) hv[l] *= gam;
+            }
           }
         } else {
           CO::grad(xv, sc, wp, gc);
-          if constexpr (CO::SNH > 0) CO::shess(xv, sc, wp, chv);
+          if constexpr (CO::SNH > 0) {
+            if (LIN && a.first_order) {
+              for (int i = l; i < CO::SNH; i += 64) chv[i] = 0.0;
+            } else {
+              CO::shess(xv, sc, wp, chv);
+            }
+          }
           if (a.stats) {
             CO::eval(xv, sc, wp, stat + 6);
             if (l == 0) stat[0] += stat[6];
@@ -1370,7 +1383,13 @@ __global__ __launch_bounds__(WG) void k_wide_step(dto_wide_args a) {
         __syncthreads();
         if (w == 0) {
           CO::grad(xv, sc, wp, gc);
-          if constexpr (CO::SNH > 0) CO::shess(xv, sc, wp, chv);
+          if constexpr (CO::SNH > 0) {
+            if (LIN && a.first_order) {
+              for (int i = l; i < CO::SNH; i += 64) chv[i] = 0.0;
+            } else {
+              CO::shess(xv, sc, wp, chv);
+            }
+          }
           if (a.stats) {
             CO::eval(xv, sc, wp, stat + 6);
             if (l == 0) stat[0] += stat[6];
@@ -2926,9 +2945,21 @@ __global__ __launch_bounds__(WG) void k_wide_kmul(dto_wide_args a) {
         if (w == 1) {
           DY::jac_var(xv, sc, yv, wp, jvv);
         } else if (w == 2) {
-          if constexpr (DY::NH > 0) DY::hess(xv, sc, yv, wp, lamv, hv);
+          if constexpr (DY::NH > 0) {
+            if (a.first_order) {   // (wave-uniform: every scatter of hv below adds zeros)
+              for (int i = l; i < DY::NH; i += 64) hv[i] = 0.0;
+            } else {
+              DY::hess(xv, sc, yv, wp, lamv, hv);
+            }
+          }
         } else if (w == 3) {
-          if constexpr (CO::SNH > 0) CO::shess(xv, sc, wp, chv);
+          if constexpr (CO::SNH > 0) {
+            if (a.first_order) {
+              for (int i = l; i < CO::SNH; i += 64) chv[i] = 0.0;
+            } else {
+              CO::shess(xv, sc, wp, chv);
+            }
+          }
         }
         lds_barrier();
         // ---- variable Jacobian entries, cost Hessian; then the dynamics Hessian (phase 3)
@@ -3030,7 +3061,13 @@ __global__ __launch_bounds__(WG) void k_wide_kmul(dto_wide_args a) {
         }
         lds_barrier();
         if (w == 0) {
-          if constexpr (CO::SNH > 0) CO::shess(xv, sc, wp, chv);
+          if constexpr (CO::SNH > 0) {
+            if (a.first_order) {
+              for (int i = l; i < CO::SNH; i += 64) chv[i] = 0.0;
+            } else {
+              CO::shess(xv, sc, wp, chv);
+            }
+          }
         }
         lds_barrier();
         if constexpr (CO::SNH > 0) {

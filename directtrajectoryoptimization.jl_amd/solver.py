@@ -54,6 +54,10 @@ class Options:
     # multi-knot GeneralConstraint rows) exact second derivatives derived from the traced expressions with a one-time
     # HessianModeNotice.  "exact": those second derivatives, no notice (the fastest mode here: they cost nothing extra);
     # "lbfgs": also for a problem WITH Hessians; "sr1": per-stage SR1 blocks (Solver.hessian_mode reports what runs).
+    # "limited-memory" (Ipopt's own spelling): L-BFGS on whichever solver path runs the problem -- "lbfgs" on the lane-per-instance
+    # path, and on the tile path (17 .. 64 states) without GeneralConstraint rows left on the border the compact matrix as a border
+    # of the first-order system (solve / solve_batch; the stepwise begin_batch / iterate_batch keep the exact Hessian there and
+    # hessian_mode_last() says so).  With such rows it is a ValueError: that path has no limited-memory mode.
     hessian_approximation: str = "auto"
     # not reference fields either (dto_options.line_search / penalty_switch_theta, include/dto.h): "penalty-filter" chooses the
     # step size on the l1 exact-penalty function while max |c_i| > penalty_switch_theta and hands over to Ipopt's filter then;
@@ -389,7 +393,8 @@ def _notice_default_mode():
         warnings.warn("evaluate_hessian=false on a problem with more than 16 states or with multi-knot GeneralConstraint rows: the GPU "
                       "solver differentiates the traced expressions twice and iterates with the exact Hessian of the Lagrangian (the "
                       "reference leaves Ipopt on its limited-memory quasi-Newton Hessian here, and so does this solver on smaller "
-                      "problems); Options(hessian_approximation='exact') silences this notice",
+                      "problems); Options(hessian_approximation='exact') silences this notice "
+                      "(hessian_approximation='limited-memory' runs L-BFGS on 17 .. 64 states too, without GeneralConstraint rows)",
                       HessianModeNotice, stacklevel=3)
 
 
@@ -414,14 +419,14 @@ class Solver:
         self.general_rows_path = None        # "accumulators" | "border" | "folded" | None: how GeneralConstraint rows are solved
         s_dyn, s_obj, s_con, s_eh, changed = list(dynamics), list(objective), list(constraints), bool(evaluate_hessian), False
         ha = self.options.hessian_approximation
-        if ha not in ("auto", "exact", "sr1", "lbfgs"):
-            raise ValueError("Options.hessian_approximation must be 'auto', 'exact', 'lbfgs' or 'sr1'")
+        if ha not in ("auto", "exact", "sr1", "lbfgs", "limited-memory"):
+            raise ValueError("Options.hessian_approximation must be 'auto', 'exact', 'lbfgs', 'limited-memory' or 'sr1'")
         # How the solver gets its Hessian of the Lagrangian (reported: Solver.hessian_mode).  evaluate_hessian=False is the
         # reference's default (src/solver.jl:7) and leaves Ipopt on its limited-memory BFGS: "auto" does the same ("lbfgs",
         # dto_options.hessian_approximation = DTO_HESSIAN_LBFGS) wherever the lane-per-instance solver path runs the problem; the
         # tile path (17 .. 64 states), multi-knot GeneralConstraint rows and user-Jacobian dynamics keep round 4's substitutes
         # (exact second derivatives of the traced expressions, announced once; per-stage SR1 blocks).
-        want_lbfgs = (ha == "lbfgs") or (ha == "auto" and not s_eh)
+        want_lbfgs = ha in ("lbfgs", "limited-memory") or (ha == "auto" and not s_eh)
         if ha == "lbfgs" and s_eh:
             pass   # asked for explicitly on a problem that has Hessians: the approximation is used all the same
         self.hessian_mode = "exact" if (s_eh and not want_lbfgs) else ("sr1" if ha == "sr1" else ("lbfgs" if want_lbfgs else "exact-from-trace"))
@@ -529,11 +534,17 @@ class Solver:
             traced = s_eh                        # (user-Jacobian dynamics cannot be differentiated: their plugin carries SR1 blocks)
             if not traced:
                 # an explicit request that cannot be honoured is an error like the other ones below; only "auto" falls back
-                if ha == "lbfgs":
-                    raise ValueError("Options(hessian_approximation='lbfgs'): dynamics with a user-provided Jacobian (src/dynamics.jl:59-101) "
+                if ha in ("lbfgs", "limited-memory"):
+                    raise ValueError(f"Options(hessian_approximation='{ha}'): dynamics with a user-provided Jacobian (src/dynamics.jl:59-101) "
                                      "have no traced expression to build the limited-memory border from; use 'sr1' or 'auto'")
                 self.hessian_mode = "sr1"
+            elif ha == "limited-memory" and gen is None:
+                pass   # tile path without general rows: dto_solve_batch runs the compact matrix as a border (csrc/dto_solver.cpp)
             elif gen is not None or wide_embedded or max(d.num_state for d in s_dyn) >= 17:
+                if ha == "limited-memory":
+                    raise ValueError(f"Options(hessian_approximation='limited-memory'): the {gen.num_constraint} GeneralConstraint row(s) "
+                                     "that couple several knots are solved through the border, and the bordered path has no "
+                                     "limited-memory mode beside them; use 'exact' or 'auto'")
                 if ha == "lbfgs":
                     raise ValueError("Options(hessian_approximation='lbfgs'): the limited-memory mode runs on the lane-per-instance "
                                      "solver path (at most 16 states, no GeneralConstraint rows over several knots)")
@@ -785,6 +796,58 @@ class Solver:
         sysd.delta_w, sysd.delta_c = float(delta_w), float(delta_c)
         capi.check(self._solve_nlp._lib.dto_kkt_assemble(self._solve_nlp._h, C.byref(b), C.byref(sysd)))
         self._B = B
+
+    def kkt_assemble_first_order(self, x_ptr, B, ldx, delta_w, delta_c, sigma_x_ptr=0, ldsx=0, sigma_c_ptr=0, ldsc=0, stream=0,
+                                 params_ptr=0, ldp=0, mu_ptr=0, ldmu=0):
+        """kkt_assemble with W = 0 (include/dto.h: dto_kkt_assemble_first_order), tile path only: the first-order system
+        [[diag(sigma_x) + delta_w I, J'], [J, -diag(sigma_c) - delta_c I]] at x -- no second derivative is evaluated and no
+        multipliers are taken (mu_ptr / ldmu travel to dto_kkt_system.mu, which the call does not read).  Leaves the Solver in the state of kkt_assemble: kkt_factor, kkt_solve, kkt_solve_multi, kkt_multiply,
+        kkt_solve_refined and the kkt_border_* / kkt_lbfgs_border calls then act on this system until the next assemble of either
+        kind.  Arrays in the solver's layout, as for kkt_assemble.  The lane-per-instance path raises DTO_ERR_UNSUPPORTED."""
+        ptrs = (x_ptr, sigma_x_ptr, sigma_c_ptr, params_ptr, mu_ptr)
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in ptrs):
+            raise TypeError("kkt_assemble_first_order takes device pointers as integers (tensor.data_ptr())")
+        if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or B < 1:
+            raise ValueError("kkt_assemble_first_order: B is a positive integer")
+        b = self._solve_nlp._batch(x_ptr, B, ldx, stream, params_ptr, ldp)
+        sysd = capi.KktSystem()
+        sysd.mu, sysd.ldmu = mu_ptr or None, ldmu
+        sysd.sigma_x, sysd.ldsx = sigma_x_ptr or None, ldsx
+        sysd.sigma_c, sysd.ldsc = sigma_c_ptr or None, ldsc
+        sysd.delta_w, sysd.delta_c = float(delta_w), float(delta_c)
+        capi.check(self._solve_nlp._lib.dto_kkt_assemble_first_order(self._solve_nlp._h, C.byref(b), C.byref(sysd)))
+        self._B = B
+
+    def kkt_lbfgs_border(self, m, s_ptr, lds, y_ptr, ldy, sigma, npairs=None, stream=0):
+        """The compact L-BFGS matrix B = sigma I - W M^-1 W' as a border of 2 m rows on the system factorised last (include/dto.h:
+        dto_kkt_lbfgs_border), tile path only.  s_ptr / y_ptr: DEVICE [B * m][ld], pair j of instance b in row b * m + j, oldest
+        first, num_variables entries (solver layout); sigma: HOST, B positive numbers; npairs: HOST, B integers in 0..m, or None
+        for m everywhere.  THE CALLER puts sigma on the x-diagonal of the assembled system through sigma_x (kkt_assemble_first_order);
+        this call adds the low-rank part.  Afterwards kkt_border_solve with a zero rhs_b returns K^-1 r; kkt_border_multiply and
+        kkt_border_solve_refined work as for any border.  Returns (inertia_ok[B], singular[B]): the Schur complement has as many
+        negative eigenvalues as M and neither a numerically zero one; a zero pivot in its LU."""
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (m, s_ptr, y_ptr)):
+            raise TypeError("kkt_lbfgs_border takes m and device pointers as integers (tensor.data_ptr())")
+        B = getattr(self, "_B", 0) or 0
+        sig = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+        if sig.shape[0] != B:
+            raise ValueError(f"kkt_lbfgs_border: sigma has one entry per instance of the assembled batch ({B}), got {sig.shape[0]}")
+        if not np.all(np.isfinite(sig)) or not np.all(sig > 0.0):
+            raise ValueError("kkt_lbfgs_border: sigma must be positive and finite")
+        npp = None
+        if npairs is not None:
+            npp = np.ascontiguousarray(np.asarray(npairs).reshape(-1))
+            if npp.shape[0] != B or not np.issubdtype(npp.dtype, np.integer) or np.any(npp < 0) or np.any(npp > m):
+                raise ValueError(f"kkt_lbfgs_border: npairs has one integer in 0..m per instance of the assembled batch ({B})")
+            npp = npp.astype(np.int32)
+        if s_ptr and s_ptr == y_ptr:
+            raise ValueError("kkt_lbfgs_border: s and y are two arrays")
+        ok, singular = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        capi.check(self._solve_nlp._lib.dto_kkt_lbfgs_border(self._solve_nlp._h, int(m), s_ptr or None, lds, y_ptr or None, ldy,
+                                                             npp.ctypes.data_as(capi.c_int32_p) if npp is not None else None,
+                                                             sig.ctypes.data_as(capi.c_double_p), ok.ctypes.data_as(capi.c_int32_p),
+                                                             singular.ctypes.data_as(capi.c_int32_p), stream or None))
+        return ok, singular
 
     def kkt_factor(self, stream=0):
         """Returns (inertia_ok[B], num_negative[B])."""

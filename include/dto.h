@@ -194,8 +194,12 @@ typedef struct dto_options {
    * DTO_HESSIAN_LBFGS: Ipopt's hessian_approximation = limited-memory, i.e. what the reference runs when a problem is built
    * with evaluate_hessian = false (src/solver.jl:7, its default and its own acrobot / car examples): compact L-BFGS, history 6,
    * sigma = s'y / s's, updates skipped without curvature -- no second derivatives are evaluated.  Lane-per-instance solver
-   * path.  Where the mode does not exist the library says what it runs instead (dto_solver_hessian_mode): a model plugin built
-   * without Hessians (evaluate_hessian = 0 in its generator) keeps per-stage SR1 blocks; the tile (17 .. 64 states) and the
+   * path, and dto_solve_batch / dto_solve on the tile path (17 .. 64 states) without GeneralConstraint rows: there the compact matrix
+   * is a border of 12 rows on a first-order factorisation (dto_kkt_assemble_first_order, dto_kkt_lbfgs_border) inside the
+   * host-driven bordered loop.  Where the mode does not exist the library says what it runs instead (dto_solver_hessian_mode): a
+   * model plugin built without Hessians (evaluate_hessian = 0 in its generator) keeps per-stage SR1 blocks; the STEPWISE entry
+   * points of the tile path (dto_solver_begin / begin_warm / iterate / run / shift) keep their exact-Hessian state and report
+   * DTO_HESSIAN_EXACT whatever is asked for -- only dto_solve_batch / dto_solve run the limited-memory mode there -- and the
    * bordered (multi-knot GeneralConstraint) paths use the exact second derivatives of the traced expressions. */
   int hessian_approximation;         /* DTO_HESSIAN_EXACT */
   /* ABI 4: passes of iterative refinement per KKT step (0 = none).  One pass: the residual r = b - K v of the step just computed,
@@ -298,6 +302,17 @@ int dto_kkt_multiply(dto_problem* p, const double* v_x, int64_t ldvx, const doub
                      int64_t ldox, double* out_c, int64_t ldoc, void* stream);
 int dto_kkt_solve_refined(dto_problem* p, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
                           double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc, double* resid, void* stream);
+/* dto_kkt_assemble with W = 0 (tile path): the first-order system
+ *     K0 = [ diag(sigma_x) + delta_w I    J(x)'                      ]
+ *          [ J(x)                         -diag(sigma_c) - delta_c I ]
+ * No second derivative of a cost or a dynamics function is evaluated; sys->mu is not read and may be NULL.  The handle is in the
+ * state dto_kkt_assemble leaves it in, until the next assemble of either kind: dto_kkt_factor, _solve, _solve_multi, _multiply,
+ * _solve_refined and the dto_kkt_border_* / dto_kkt_lbfgs_border calls then act on K0.  A caller with a quasi-Newton matrix of
+ * its own puts the scalar part on the diagonal through sigma_x and the low-rank part on the border.  Every other rule is
+ * dto_kkt_assemble's: stage Constraint rows are DTO_ERR_UNSUPPORTED, with GeneralConstraint rows K0 is the stage part, a leading
+ * dimension below its row length is DTO_ERR_INVALID, a refused call writes nothing.  Lane-per-instance path: DTO_ERR_UNSUPPORTED
+ * ("tile path only", as dto_kkt_multiply). */
+int dto_kkt_assemble_first_order(dto_problem* p, const dto_batch* b, const dto_kkt_system* sys);
 /* Bordered solves against the factor of dto_kkt_factor.  For every instance, with K the matrix of dto_kkt_assemble
  * (dimension N = num_variables + num_constraint):
  *     [ K   G' ] [ v ]   [ r ]        G: nb x N (border rows, 1 <= nb <= 16)
@@ -374,6 +389,28 @@ int dto_kkt_border_multiply(dto_problem* p, const double* v_x, int64_t ldvx, con
 int dto_kkt_border_solve_refined(dto_problem* p, int passes, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc,
                                  const double* rhs_b, int64_t ldrb, double* sol_x, int64_t ldsx, double* sol_c, int64_t ldsc,
                                  double* sol_b, int64_t ldsb, double* resid, void* stream);
+/* The compact limited-memory BFGS matrix as a border (tile path).  With the pairs (s_j, y_j), oldest first,
+ *     B  = sigma I - W M^-1 W',   W = [sigma S, Y],   M = [[sigma S'S, L], [L', -D]]   (L, D: strictly lower part / diagonal of S'Y)
+ *     K  = K0 - U M^-1 U',  U = [W; 0]:       K v = b   <=>   [K0 U; U' M] [v; w] = [b; 0]
+ * which is dto_kkt_border_factor's system with G = U' (rows sigma s_j, then y_j; zero on the constraint side), C = M.  The call
+ * forms the panel and M on the device (M from one Gram pass over the history) and then runs what dto_kkt_border_factor runs;
+ * afterwards dto_kkt_border_solve with rhs_b = 0 returns K^-1 r, and dto_kkt_border_multiply / _solve_refined work on the bordered
+ * matrix as for any border (2 m border rows).
+ * It needs a factorised system (dto_kkt_assemble_first_order, or dto_kkt_assemble, then dto_kkt_factor).  THE CALLER puts sigma on
+ * the x-diagonal of that system through dto_kkt_system.sigma_x, beside whatever else it adds there: this call adds only the
+ * low-rank part.
+ * s, y: DEVICE [B * m][ld], num_variables entries per row, pair j of instance b in row b * m + j.  npairs: HOST [B] or NULL (m
+ * everywhere): instance b uses its first npairs[b] pairs; the rows of the others are zero in the panel and their diagonal entries
+ * of M are +1 (S block) and -1 (Y block), so the Schur complement stays regular and the expected inertia does not change.
+ * sigma: HOST [B], positive.  inertia_ok (HOST [B], may be NULL): 1 when the Schur complement M - U' K0^-1 U has exactly as many
+ * negative eigenvalues as M and neither has a numerically zero one (signs from cyclic Jacobi, zero = within 1e-13 of the largest
+ * entry) -- with K0 of the right inertia, K then has it too.  schur_singular (HOST [B], may be NULL): as dto_kkt_border_factor.
+ * Errors: m < 1, a null s, y or sigma, npairs outside 0..m, a sigma that is not positive and finite, a leading dimension below
+ * num_variables: DTO_ERR_INVALID; 2 m > 16: DTO_ERR_UNSUPPORTED (one panel); no assembled or factorised system: the messages of
+ * dto_kkt_border_factor; lane-per-instance path: DTO_ERR_UNSUPPORTED ("tile path only").  A refused call writes nothing.  Results are
+ * bit-identical from run to run (no atomic sums; both Gram passes are summed in the chunks of dto_kkt_border_factor). */
+int dto_kkt_lbfgs_border(dto_problem* p, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy, const int32_t* npairs,
+                         const double* sigma, int32_t* inertia_ok, int32_t* schur_singular, void* stream);
 
 /* Batched interior-point solve, one independent NLP per instance, same structure, different guesses.
  * x0: DEVICE [B][ldx] initial guesses (what initialize_states!/initialize_controls! set,
@@ -400,7 +437,12 @@ int dto_kkt_border_solve_refined(dto_problem* p, int passes, const double* rhs_x
  *   panel substitution for all n_g rows and one bordered solve per step (dto_kkt_border_factor / dto_kkt_border_solve inside); at
  *   most 16 general rows (more: DTO_ERR_UNSUPPORTED), no stage rows.  dto_solve_batch, dto_solve and dto_kkt_step_batch take such a
  *   problem; dto_solver_begin / begin_warm / iterate / run / shift and dto_solver_set_bounds return DTO_ERR_UNSUPPORTED for it
- *   (cold starts only, the problem's shared bounds).  dto_solver_hessian_mode reports DTO_HESSIAN_EXACT, kkt_refinement is ignored. */
+ *   (cold starts only, the problem's shared bounds).  dto_solver_hessian_mode reports DTO_HESSIAN_EXACT, kkt_refinement is ignored;
+ * - tile path WITHOUT general rows and dto_options.hessian_approximation = DTO_HESSIAN_LBFGS: the same host-driven loop with zero
+ *   general rows, its step a first-order factorisation with the compact L-BFGS matrix (history 6) as a border of 12 rows; the history
+ *   lives on the device, 12 x num_variables doubles per instance (the size is reported if the allocation fails).  The problem's
+ *   shared bounds, shared or per-instance parameters, filter line search (no penalty phase), cold starts only.
+ *   dto_solver_hessian_mode reports DTO_HESSIAN_LBFGS after such a solve. */
 int dto_solve_batch(dto_problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                     double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 
