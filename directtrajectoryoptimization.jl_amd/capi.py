@@ -128,6 +128,8 @@ def lib() -> C.CDLL:
         "dto_kkt_assemble": [vp, C.POINTER(Batch), C.POINTER(KktSystem)],
         "dto_kkt_assemble_first_order": [vp, C.POINTER(Batch), C.POINTER(KktSystem)],
         "dto_kkt_lbfgs_border": [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, c_int32_p, c_double_p, c_int32_p, c_int32_p, vp],
+        "dto_kkt_lbfgs_border_rows": [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, c_int32_p, c_double_p, C.c_int64, vp, C.c_int64, vp,
+                                      C.c_int64, vp, C.c_int64, c_int32_p, c_int32_p, vp],
         "dto_kkt_factor": [vp, c_int32_p, c_int32_p, vp],
         "dto_kkt_solve": [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp],
         "dto_kkt_solve_multi": [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp],

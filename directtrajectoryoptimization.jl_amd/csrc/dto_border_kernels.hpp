@@ -299,21 +299,46 @@ static __global__ __launch_bounds__(64) void k_border_mul_fin(int nb, int chunks
 // ---- the compact limited-memory BFGS matrix as a border (dto_kkt_lbfgs_border; dto_kkt_kernels.hpp, "limited-memory BFGS"):
 //          B = sigma I - W M^-1 W',  W = [sigma S, Y],  M = [[sigma S'S, L], [L', -D]]   (L, D: strictly lower part / diagonal of S'Y)
 //      so K0 - [W; 0] M^-1 [W; 0]' is the Schur complement of the bordered matrix [K0 U; U' M] with U' = the panel below.
-// The panel of instance b: rows 0 .. m-1 = sigma_b s_j, rows m .. 2m-1 = y_j (pair j = row b * m + j of s and y, oldest first), the
-// rows of the pairs j >= npairs[b] zeros.  One thread per entry of the variables' part; the constraint part is cleared by the caller.
-static __global__ void k_lbfgs_panel(int64_t B, int m, int64_t Nz, const double* s, int64_t lds, const double* y, int64_t ldy,
+// The panel of instance b (nb rows, nb >= 2 m: dto_kkt_lbfgs_border_rows keeps the caller's rows behind the history): rows 0 .. m-1 =
+// sigma_b s_j, rows m .. 2m-1 = y_j (pair j = row b * m + j of s and y, oldest first), the rows of the pairs j >= npairs[b] zeros.
+// One thread per entry of the variables' part; the constraint part is cleared by the caller.
+static __global__ void k_lbfgs_panel(int64_t B, int m, int nb, int64_t Nz, const double* s, int64_t lds, const double* y, int64_t ldy,
                                      const int* npairs, const double* sigma, double* g, int64_t ldg) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * m * Nz) return;
   const int64_t row = idx / Nz, k = idx - row * Nz, b = row / m;
   const int j = (int)(row - b * m);
   const bool have = j < npairs[b];
-  g[(b * 2 * m + j) * ldg + k] = have ? sigma[b] * s[row * lds + k] : 0.0;
-  g[(b * 2 * m + m + j) * ldg + k] = have ? y[row * ldy + k] : 0.0;
+  g[(b * nb + j) * ldg + k] = have ? sigma[b] * s[row * lds + k] : 0.0;
+  g[(b * nb + m + j) * ldg + k] = have ? y[row * ldy + k] : 0.0;
+}
+// The caller's nr rows behind the 2 m history rows of every instance (dto_kkt_lbfgs_border_rows): row j of instance b is row
+// b * nr + j of (g_x, g_c) and becomes row b * nb + (nb - nr) + j of the panel g (pitch ldg, Nz + Nc entries).  One thread per
+// (instance, column): it writes its column of all nr rows, on the variable side and on the constraint side (zeros without g_c), so
+// EVERY entry of those rows is written and nothing is summed.
+static __global__ void k_lbfgs_rows(int64_t B, int nb, int nr, int64_t Nz, int64_t Nc, const double* g_x, int64_t ldgx, const double* g_c,
+                                    int64_t ldgc, double* g, int64_t ldg) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t N = Nz + Nc;
+  if (idx >= B * N) return;
+  const int64_t b = idx / N, k = idx - b * N;
+  for (int j = 0; j < nr; ++j) {
+    const int64_t src = b * nr + j;
+    const double v = k < Nz ? g_x[src * ldgx + k] : (g_c ? g_c[src * ldgc + (k - Nz)] : 0.0);
+    g[(b * nb + (nb - nr) + j) * ldg + k] = v;
+  }
 }
 // M of instance b from the Gram matrix of its panel (the partials of k_border_gram with the panel as both operands, summed in chunk
-// order): P = [[sigma^2 S'S, sigma S'Y], [sigma Y'S, Y'Y]].  c [B][4 m m], row-major.  A pair the instance does not have gets +1 on
-// the diagonal of the S block and -1 on that of the Y block: the Schur complement stays regular and keeps its inertia.
+// order): P = [[sigma^2 S'S, sigma S'Y], [sigma Y'S, Y'Y]].  A pair the instance does not have gets +1 on the diagonal of the S block
+// and -1 on that of the Y block: the Schur complement stays regular and keeps its inertia.  lbfgs_m_entry: entry (a, q) of M,
+// a, q < 2 m, from P (stride 16).
+__device__ __forceinline__ double lbfgs_m_entry(const double* P, int m, int np, double sg, int a, int q) {
+  if (a < m && q < m) return (a < np && q < np) ? 0.5 * (P[a * 16 + q] + P[q * 16 + a]) / sg : (a == q ? 1.0 : 0.0);
+  if (a >= m && q >= m) return a != q ? 0.0 : (a - m < np ? -P[(a - m) * 16 + a] / sg : -1.0);
+  const int si = a < m ? a : q, yj = (a < m ? q : a) - m;   // the entry s_si' y_yj of L (or of L')
+  return (si > yj && si < np) ? P[si * 16 + m + yj] / sg : 0.0;
+}
+// c [B][4 m m], row-major.
 static __global__ __launch_bounds__(64) void k_lbfgs_c(int m, int chunks, const double* part, const int* npairs, const double* sigma, double* c) {
   __shared__ double P[256];
   const int64_t b = blockIdx.x;
@@ -328,15 +353,31 @@ static __global__ __launch_bounds__(64) void k_lbfgs_c(int m, int chunks, const 
   __syncthreads();
   for (int i = l; i < nb * nb; i += 64) {
     const int a = i / nb, q = i - a * nb;
-    double v;
-    if (a < m && q < m) {
-      v = (a < np && q < np) ? 0.5 * (P[a * 16 + q] + P[q * 16 + a]) / sg : (a == q ? 1.0 : 0.0);
-    } else if (a >= m && q >= m) {
-      v = a != q ? 0.0 : (a - m < np ? -P[(a - m) * 16 + a] / sg : -1.0);
-    } else {
-      const int si = a < m ? a : q, yj = (a < m ? q : a) - m;   // the entry s_si' y_yj of L (or of L')
-      v = (si > yj && si < np) ? P[si * 16 + m + yj] / sg : 0.0;
-    }
+    c[b * nb * nb + i] = lbfgs_m_entry(P, m, np, sg, a, q);
+  }
+}
+// The same with the caller's nr rows behind the history (dto_kkt_lbfgs_border_rows; the Gram pass ran over all nb = 2 m + nr rows of
+// the panel, only its 2 m x 2 m corner is read: an entry of P is the sum over k of ONE product, so that corner has the bits it has
+// without the rows): c [B][nb * nb], row-major = blkdiag(M, C) -- M top-left, the caller's cr ([B][ldcr], nr x nr row-major) bottom-right,
+// zeros between.
+static __global__ __launch_bounds__(64) void k_lbfgs_c_rows(int m, int nr, int chunks, const double* part, const int* npairs, const double* sigma,
+                                                            const double* cr, int64_t ldcr, double* c) {
+  __shared__ double P[256];
+  const int64_t b = blockIdx.x;
+  const int l = threadIdx.x, nm = 2 * m, nb = nm + nr, np = npairs[b];
+  const double sg = sigma[b];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    double acc = 0.0;
+    for (int ch = 0; ch < chunks; ++ch) acc += part[(b * chunks + ch) * 256 + l + 64 * e];
+    P[l + 64 * e] = acc;
+  }
+  __syncthreads();
+  for (int i = l; i < nb * nb; i += 64) {
+    const int a = i / nb, q = i - a * nb;
+    double v = 0.0;
+    if (a < nm && q < nm) v = lbfgs_m_entry(P, m, np, sg, a, q);
+    else if (a >= nm && q >= nm) v = cr[b * ldcr + (a - nm) * nr + (q - nm)];
     c[b * nb * nb + i] = v;
   }
 }

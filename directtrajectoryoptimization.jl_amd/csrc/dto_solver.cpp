@@ -2007,7 +2007,7 @@ struct BorderStats {
   const double *d_grad = nullptr, *d_c = nullptr, *d_rx = nullptr;
   const double* d_J = nullptr;   // (tile path) the Jacobian values of the point, COO order, [B][nnzJ]
   bool reuse_point = false;   // in: the point did not move since the last call (another delta_w attempt): keep J, c, grad f, r_x, G
-  struct QnHistory* qn = nullptr;   // in (tile path, no general rows): the limited-memory mode -- the step is the compact L-BFGS one
+  struct QnHistory* qn = nullptr;   // in (tile path, at most four general rows): the limited-memory mode -- the step is the compact L-BFGS one
 };
 
 // ---- limited-memory mode of the bordered loop on the tile path: the secant pairs of every instance on the device, the rules of
@@ -2364,7 +2364,8 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
   const BorderBar bar = barp ? *barp : BorderBar();   // (no bounds: all NULL, the kernels take their old branches)
   QnHistory* qn = stats ? stats->qn : nullptr;
-  if (qn && ng != 0) return set_error(DTO_ERR_UNSUPPORTED, "limited-memory mode beside GeneralConstraint rows on the tile border");
+  if (qn && 2 * QnHistory::M + ng > KB_MAX)
+    return set_error(DTO_ERR_UNSUPPORTED, "limited-memory mode beside more than four GeneralConstraint rows on the tile border (12 + n_g rows, one panel)");
   int rc = p->ensure_device();
   if (rc) return rc;
   if ((rc = ensure_border_csc(p))) return rc;
@@ -2406,7 +2407,18 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
   DRC(wide_kkt_assemble(p, b, &sys, qn != nullptr));
   std::vector<int32_t> iok((size_t)B, 1), negdef((size_t)B, 1), sing((size_t)B, 0);
   DRC(wide_kkt_factor(p, iok.data(), nullptr, st));
-  if (qn) {
+  if (qn && ng > 0) {
+    // both borders in one panel: [sigma S; Y; G] with blkdiag(M, C) -- the right-hand side of the compact part is zero, that of the
+    // rows is theirs; the rows' part of the border unknowns is the step of their multipliers.  negdef carries inertia_ok
+    constexpr int64_t QM2 = 2 * QnHistory::M;
+    DRC(dto_kkt_lbfgs_border_rows(h, QnHistory::M, qn->S, Nz, qn->Y, Nz, qn->npairs.data(), qn->sigma.data(), ng, dPanel, Nz, nullptr, 0, dCb, ng * ng,
+                                  negdef.data(), sing.data(), (void*)st));
+    HIP_TRY(hipMemcpy2DAsync((double*)qn->rb + QM2, 16 * sizeof(double), dRhsb, (size_t)ng * sizeof(double), (size_t)ng * sizeof(double), (size_t)B,
+                             hipMemcpyDeviceToDevice, st));
+    DRC(dto_kkt_border_solve(h, dRhsx, Nz, dRhsc, Nc, qn->rb, 16, dx, lddx, dmu, lddmu, qn->sb, 16, (void*)st));
+    HIP_TRY(hipMemcpy2DAsync(dmu + Ns, (size_t)lddmu * sizeof(double), (const double*)qn->sb + QM2, 16 * sizeof(double), (size_t)ng * sizeof(double),
+                             (size_t)B, hipMemcpyDeviceToDevice, st));
+  } else if (qn) {
     // K0 = first-order system + (sigma + delta_w) I, the compact matrix as a border of 2 M rows; negdef carries inertia_ok
     DRC(dto_kkt_lbfgs_border(h, QnHistory::M, qn->S, Nz, qn->Y, Nz, qn->npairs.data(), qn->sigma.data(), negdef.data(), sing.data(), (void*)st));
     DRC(dto_kkt_border_solve(h, dRhsx, Nz, dRhsc, Nc, qn->rb, 16, dx, lddx, dmu, lddmu, qn->sb, 16, (void*)st));
@@ -2604,9 +2616,10 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
   if (rc) return rc;
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc;
-  // lbfgs: the limited-memory mode of the tile path (no general rows: the 12 border rows are the compact matrix).  Everything below is
-  // the loop as it stands for zero general rows; the step (bordered_step_tile) and the secant pairs after it are what differ
-  if (lbfgs && (!p->vt->launch_wide || L.Ngen != 0)) return set_error(DTO_ERR_UNSUPPORTED, "limited-memory bordered loop: tile path without GeneralConstraint rows");
+  // lbfgs: the limited-memory mode of the tile path (12 border rows are the compact matrix, up to four general rows share its panel).
+  // Everything below is the loop as it stands; the step (bordered_step_tile) and the secant pairs after it are what differ
+  if (lbfgs && (!p->vt->launch_wide || 2 * QnHistory::M + L.Ngen > KB_MAX))
+    return set_error(DTO_ERR_UNSUPPORTED, "limited-memory bordered loop: tile path with at most four GeneralConstraint rows");
   if (lbfgs && b->B < 1) return set_error(DTO_ERR_INVALID, "empty batch");
   if (lbfgs && (b->ldx < Nz || ldxo < Nz || (mu_out && ldmuo < Nc))) return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if (lbfgs && L.Nstage != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows, GeneralConstraint rows and bounds only");
@@ -4021,11 +4034,13 @@ int dto_solver_repack(dto_problem* h, int* num_running, void* stream) {
 int dto_solve_batch(dto_problem* h, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                     double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations) {
   Problem* p = reinterpret_cast<Problem*>(h);
-  // (the stepwise tile solver and the bordered paths with general rows have no limited-memory mode: they run the exact second
-  //  derivatives of the traced expressions whatever dto_options.hessian_approximation asks for, and dto_solver_hessian_mode
+  // (the stepwise tile solver, the lane path's border and a tile border of more than four general rows have no limited-memory mode:
+  //  they run the exact second derivatives of the traced expressions whatever dto_options.hessian_approximation asks for, and dto_solver_hessian_mode
   //  reports it -- ADVICE r5)
-  if (p && b && b->x && x_out && p->vt->launch_wide && p->L.Ngen == 0 && opt && opt->hessian_approximation == DTO_HESSIAN_LBFGS) {
-    // tile path, limited-memory mode: the host-driven bordered loop with the compact L-BFGS matrix as its border (no general rows).
+  if (p && b && b->x && x_out && p->vt->launch_wide && 2 * dto::QnHistory::M + p->L.Ngen <= dto::KB_MAX && opt &&
+      opt->hessian_approximation == DTO_HESSIAN_LBFGS) {
+    // tile path, limited-memory mode: the host-driven bordered loop with the compact L-BFGS matrix as its border, beside at most four
+    // general rows in the same panel (more of them: the exact substitute below).
     // The stepwise state of the handle (dto_solver_begin ...) is not touched; the factor storage is taken, as by every solve
     int rc = dto::general_solve_batch(p, opt, b, x_out, ldxo, mu_out, ldmuo, status, iterations, true);
     if (rc == DTO_OK) p->hessian_mode_last = DTO_HESSIAN_LBFGS;
@@ -4282,21 +4297,29 @@ int dto_kkt_border_factor(dto_problem* h, int64_t nb, const double* g_x, int64_t
 // The compact limited-memory BFGS matrix as the border of the factorised system (dto_border_kernels.hpp: k_lbfgs_panel, k_lbfgs_c):
 // the panel [sigma S; Y] and M are formed on the device, then everything dto_kkt_border_factor runs.  The eigenvalue signs of M and
 // of the Schur complement come from cyclic Jacobi on the host, over the copies k_border_schur keeps (16 x 16 per instance).
-int dto_kkt_lbfgs_border(dto_problem* h, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy, const int32_t* npairs,
-                         const double* sigma, int32_t* inertia_ok, int32_t* schur_singular, void* stream) {
+// nr > 0 (dto_kkt_lbfgs_border_rows): the caller's rows join the panel behind the history (k_lbfgs_rows) and their block C the
+// diagonal block behind M (k_lbfgs_c_rows); nr == 0 launches exactly what dto_kkt_lbfgs_border launched before there were rows.
+static int lbfgs_border(dto_problem* h, const char* who, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy,
+                        const int32_t* npairs, const double* sigma, int64_t nr, const double* g_x, int64_t ldgx, const double* g_c, int64_t ldgc,
+                        const double* c, int64_t ldc, int32_t* inertia_ok, int32_t* schur_singular, void* stream) {
   Problem* p = reinterpret_cast<Problem*>(h);
+  const std::string w = who;
   if (!p) return set_error(DTO_ERR_INVALID, "null argument");
   int rc = p->ensure_device();
   if (rc) return rc;
   if (!p->vt->launch_wide)
-    return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_lbfgs_border: tile path only (the lane-per-instance solver carries its limited-memory "
-                                          "matrix inside its sweeps)");
+    return set_error(DTO_ERR_UNSUPPORTED, (w + ": tile path only (the lane-per-instance solver carries its limited-memory "
+                                               "matrix inside its sweeps)").c_str());
   if (!p->wide_kkt || !p->wide_kkt->assembled) return set_error(DTO_ERR_INVALID, "dto_kkt_assemble has not been called");
-  if (m < 1) return set_error(DTO_ERR_INVALID, "dto_kkt_lbfgs_border: m < 1");
-  if (2 * m > dto::KB_MAX) return set_error(DTO_ERR_UNSUPPORTED, "dto_kkt_lbfgs_border: more than 8 pairs (16 border rows, one panel of right-hand sides)");
-  if (!s || !y || !sigma) return set_error(DTO_ERR_INVALID, "null argument");
-  const int64_t Nz = p->L.Nz, Nc = dto::kkt_rows(p), N = Nz + Nc, nb = 2 * m;
-  if (lds < Nz || ldy < Nz) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (m < 1) return set_error(DTO_ERR_INVALID, (w + ": m < 1").c_str());
+  if (nr < 0) return set_error(DTO_ERR_INVALID, (w + ": nr < 0").c_str());
+  if (2 * m > dto::KB_MAX) return set_error(DTO_ERR_UNSUPPORTED, (w + ": more than 8 pairs (16 border rows, one panel of right-hand sides)").c_str());
+  if (2 * m + nr > dto::KB_MAX)
+    return set_error(DTO_ERR_UNSUPPORTED, (w + ": 2 m + nr > 16 border rows (one panel of right-hand sides)").c_str());
+  if (!s || !y || !sigma || (nr > 0 && (!g_x || !c))) return set_error(DTO_ERR_INVALID, "null argument");
+  const int64_t Nz = p->L.Nz, Nc = dto::kkt_rows(p), N = Nz + Nc, nb = 2 * m + nr;
+  if (lds < Nz || ldy < Nz || (nr > 0 && (ldgx < Nz || (g_c && ldgc < p->L.Nc) || ldc < nr * nr)))
+    return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if (!p->wide_kkt->factored)
     return set_error(DTO_ERR_INVALID, "dto_kkt_factor has not been called (or dto_kkt_step_batch / the solver has used the factor storage since)");
   const int64_t B = p->wide_kkt->B;
@@ -4304,12 +4327,13 @@ int dto_kkt_lbfgs_border(dto_problem* h, int64_t m, const double* s, int64_t lds
   std::vector<double> hsig((size_t)B);
   for (int64_t i = 0; i < B; ++i) {
     const int64_t np = npairs ? npairs[i] : m;
-    if (np < 0 || np > m) return set_error(DTO_ERR_INVALID, "dto_kkt_lbfgs_border: npairs outside 0..m");
-    if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i])) return set_error(DTO_ERR_INVALID, "dto_kkt_lbfgs_border: sigma must be positive and finite");
+    if (np < 0 || np > m) return set_error(DTO_ERR_INVALID, (w + ": npairs outside 0..m").c_str());
+    if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i])) return set_error(DTO_ERR_INVALID, (w + ": sigma must be positive and finite").c_str());
     hnp[(size_t)i] = (int)np; hsig[(size_t)i] = sigma[i];
   }
+  const bool has_gc = nr > 0 && g_c != nullptr;
   dto::BorderPlan P;
-  if ((rc = dto::border_prepare(p, nb, false, P))) return rc;
+  if ((rc = dto::border_prepare(p, nb, has_gc, P))) return rc;
   dto::KktBorder& W = *p->kkt_border;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = dto::grow_buf(W.qc, (size_t)B * 256, "dto_kkt_lbfgs_border: hipMalloc of the compact matrix"))) return rc;
@@ -4320,32 +4344,61 @@ int dto_kkt_lbfgs_border(dto_problem* h, int64_t m, const double* s, int64_t lds
   HIP_TRY(hipMemcpyAsync(W.qsig, hsig.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
   {
     const size_t n = (size_t)B * (size_t)m * (size_t)Nz;
-    hipLaunchKernelGGL(dto::k_lbfgs_panel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, (int)m, Nz, s, lds, y, ldy, (const int*)W.qnp,
-                       (const double*)W.qsig, (double*)W.g, N);
+    hipLaunchKernelGGL(dto::k_lbfgs_panel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, (int)m, (int)nb, Nz, s, lds, y, ldy,
+                       (const int*)W.qnp, (const double*)W.qsig, (double*)W.g, N);
     HIP_TRY(hipGetLastError());
   }
+  // (the constraint side of the history rows is zero; with rows this clears theirs too, and k_lbfgs_rows writes it again)
   if (Nc > 0) HIP_TRY(hipMemset2DAsync(W.g + Nz, (size_t)N * sizeof(double), 0, (size_t)Nc * sizeof(double), (size_t)B * (size_t)nb, st));
+  if (nr > 0) {
+    const size_t n = (size_t)B * (size_t)N;
+    hipLaunchKernelGGL(dto::k_lbfgs_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, (int)nb, (int)nr, Nz, Nc, g_x, ldgx, g_c, ldgc,
+                       (double*)W.g, N);
+    HIP_TRY(hipGetLastError());
+  }
   // M from ONE Gram pass over the history: the panel as both operands (the partials are consumed by k_lbfgs_c before the Schur
-  // complement's own Gram pass writes them again, on the same stream)
+  // complement's own Gram pass writes them again, on the same stream).  The pass covers the variables' part only -- the history is
+  // zero beyond it -- in the chunks of the plan: a chunk that lies beyond it adds zeros.  With rows it runs over all nb rows and
+  // k_lbfgs_c_rows reads the history's corner
   hipLaunchKernelGGL(dto::k_border_gram, dim3((unsigned)(B * P.chunks)), dim3(dto::KB_THREADS), 0, st, (int)nb, Nz, (int64_t)0, P.chunk, P.chunks,
                      (const double*)W.g, N, (const double*)nullptr, (int64_t)0, (const double*)W.g, N, (const double*)nullptr, (int64_t)0, (double*)W.part);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(dto::k_lbfgs_c, dim3((unsigned)B), dim3(64), 0, st, (int)m, P.chunks, (const double*)W.part, (const int*)W.qnp,
-                     (const double*)W.qsig, (double*)W.qc);
+  if (nr > 0)
+    hipLaunchKernelGGL(dto::k_lbfgs_c_rows, dim3((unsigned)B), dim3(64), 0, st, (int)m, (int)nr, P.chunks, (const double*)W.part, (const int*)W.qnp,
+                       (const double*)W.qsig, c, ldc, (double*)W.qc);
+  else
+    hipLaunchKernelGGL(dto::k_lbfgs_c, dim3((unsigned)B), dim3(64), 0, st, (int)m, P.chunks, (const double*)W.part, (const int*)W.qnp,
+                       (const double*)W.qsig, (double*)W.qc);
   HIP_TRY(hipGetLastError());
   if ((rc = dto::border_finish(h, p, P, nb, W.qc, nb * nb, nullptr, schur_singular, W.skeep, st))) return rc;
   if (inertia_ok) {
+    // In(K0) + In(Schur) = In(blkdiag(M, C)) + In of the bordered K: with K0 at (Nz, Ns) the bordered K = K0 - U M^-1 U' has
+    // (Nz, Ns + nr) exactly when the Schur complement has neg(M) + nr negative eigenvalues.  M is the top-left 2 m x 2 m of the
+    // kept sym(blkdiag(M, C)); C is not looked at on its own (it is 0 for an equality row with delta_c = 0)
     std::vector<double> hm((size_t)B * 256), hs((size_t)B * 256);
     HIP_TRY(hipMemcpyAsync(hm.data(), W.csym, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(hs.data(), W.skeep, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < B; ++i) {
       bool tiny_m = false, tiny_s = false;
-      const int neg_m = dto::small_inertia(&hm[(size_t)i * 256], (int)nb, tiny_m), neg_s = dto::small_inertia(&hs[(size_t)i * 256], (int)nb, tiny_s);
-      inertia_ok[i] = (neg_m == neg_s && !tiny_m && !tiny_s) ? 1 : 0;
+      const int neg_m = dto::small_inertia(&hm[(size_t)i * 256], (int)(2 * m), tiny_m), neg_s = dto::small_inertia(&hs[(size_t)i * 256], (int)nb, tiny_s);
+      inertia_ok[i] = (neg_m + (int)nr == neg_s && !tiny_m && !tiny_s) ? 1 : 0;
     }
   }
   return DTO_OK;
+}
+
+int dto_kkt_lbfgs_border(dto_problem* h, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy, const int32_t* npairs,
+                         const double* sigma, int32_t* inertia_ok, int32_t* schur_singular, void* stream) {
+  return lbfgs_border(h, "dto_kkt_lbfgs_border", m, s, lds, y, ldy, npairs, sigma, 0, nullptr, 0, nullptr, 0, nullptr, 0, inertia_ok, schur_singular,
+                      stream);
+}
+
+int dto_kkt_lbfgs_border_rows(dto_problem* h, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy, const int32_t* npairs,
+                              const double* sigma, int64_t nr, const double* g_x, int64_t ldgx, const double* g_c, int64_t ldgc, const double* c,
+                              int64_t ldc, int32_t* inertia_ok, int32_t* schur_singular, void* stream) {
+  return lbfgs_border(h, "dto_kkt_lbfgs_border_rows", m, s, lds, y, ldy, npairs, sigma, nr, g_x, ldgx, g_c, ldgc, c, ldc, inertia_ok, schur_singular,
+                      stream);
 }
 
 int dto_kkt_border_solve(dto_problem* h, const double* rhs_x, int64_t ldrx, const double* rhs_c, int64_t ldrc, const double* rhs_b,

@@ -57,6 +57,17 @@ def tile_border_solvers():
         out.append(solver(f"acrobot_padded_g_m{m}", [(2, 5, 0.2), (3, 6, 0.1, False, "product")], T=6, m=m))
     for count in (16, 17):
         out.append(solver(f"acrobot_padded_g{count}", [(a, b, 0.1 * (j + 1)) for j, (a, b) in enumerate(pairs(count, 8))], T=8))
+    # one row more than the limited-memory mode takes beside its compact matrix (tests/test_wide_lbfgs_rows_cpu.py)
+    out.append(solver("acrobot_padded_g5", [(a, b, 0.1 * (j + 1)) for j, (a, b) in enumerate(pairs(5, 6))], T=6))
+    # ... and the reference's default build (no Hessians) of the two-row problem: its callbacks plugin ("auto" keeps the exact substitute)
+    import warnings
+    from .solver import HessianModeNotice
+    p0 = P.build_acrobot_padded(T=6, general_row=[(2, 5, 0.2), (3, 6, 0.1, False, "product")], evaluate_hessian=False)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", HessianModeNotice)
+        Solver(p0["dynamics"], p0["objective"], p0["constraints"], p0["bounds"], evaluate_hessian=False,
+               general_constraint=p0["general_constraint"], name="acrobot_padded_g_m1")
+    out.append("acrobot_padded_g_m1")
     for row in ((10, 20, tot["sum"]), (10, 20, tot["product"], False, "product"), (10, 20, tot["sum<=0"], True)):
         out.append(solver("acrobot_padded_g", [row], T=30, target=0.5, terminal="physical"))
     out.append(solver("acrobot24gp", [(10, 20, tot["product24"], False, "product")], T=30, n=24, target=0.4, terminal="physical"))

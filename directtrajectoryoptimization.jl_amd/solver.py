@@ -55,9 +55,10 @@ class Options:
     # HessianModeNotice.  "exact": those second derivatives, no notice (the fastest mode here: they cost nothing extra);
     # "lbfgs": also for a problem WITH Hessians; "sr1": per-stage SR1 blocks (Solver.hessian_mode reports what runs).
     # "limited-memory" (Ipopt's own spelling): L-BFGS on whichever solver path runs the problem -- "lbfgs" on the lane-per-instance
-    # path, and on the tile path (17 .. 64 states) without GeneralConstraint rows left on the border the compact matrix as a border
-    # of the first-order system (solve / solve_batch; the stepwise begin_batch / iterate_batch keep the exact Hessian there and
-    # hessian_mode_last() says so).  With such rows it is a ValueError: that path has no limited-memory mode.
+    # path, and on the tile path (17 .. 64 states) the compact matrix as a border of the first-order system, beside at most four
+    # coupling GeneralConstraint rows left on the border (solve / solve_batch; the stepwise begin_batch / iterate_batch keep the
+    # exact Hessian there and hessian_mode_last() says so).  With five or more such rows on the tile path, or any on the border of
+    # the lane-per-instance path, it is a ValueError: there is no limited-memory mode beside them.
     hessian_approximation: str = "auto"
     # not reference fields either (dto_options.line_search / penalty_switch_theta, include/dto.h): "penalty-filter" chooses the
     # step size on the l1 exact-penalty function while max |c_i| > penalty_switch_theta and hands over to Ipopt's filter then;
@@ -354,6 +355,11 @@ class NLPData:
                                                       out_ptr, ldo, stream or None))
 
 
+# coupling rows the limited-memory mode of the tile path takes beside the 12 rows of its compact matrix (one panel of 16:
+# csrc/dto_solver.cpp, QnHistory::M and KB_MAX)
+TILE_LBFGS_MAX_ROWS = 4
+
+
 def _c_options(o: "Options", check_every: int = 10, lbfgs: bool = False) -> "capi.COptions":
     c = capi.COptions()
     capi.check(capi.lib().dto_options_default(C.byref(c)))
@@ -394,7 +400,7 @@ def _notice_default_mode():
                       "solver differentiates the traced expressions twice and iterates with the exact Hessian of the Lagrangian (the "
                       "reference leaves Ipopt on its limited-memory quasi-Newton Hessian here, and so does this solver on smaller "
                       "problems); Options(hessian_approximation='exact') silences this notice "
-                      "(hessian_approximation='limited-memory' runs L-BFGS on 17 .. 64 states too, without GeneralConstraint rows)",
+                      "(hessian_approximation='limited-memory' runs L-BFGS on 17 .. 64 states too, beside at most four coupling GeneralConstraint rows)",
                       HessianModeNotice, stacklevel=3)
 
 
@@ -540,6 +546,12 @@ class Solver:
                 self.hessian_mode = "sr1"
             elif ha == "limited-memory" and gen is None:
                 pass   # tile path without general rows: dto_solve_batch runs the compact matrix as a border (csrc/dto_solver.cpp)
+            elif ha == "limited-memory" and (wide_embedded or max(d.num_state for d in s_dyn) == _WST):
+                # tile path with rows left on the border: they share the panel of 16 with the 12 rows of the compact matrix
+                if gen.num_constraint > TILE_LBFGS_MAX_ROWS:
+                    raise ValueError(f"Options(hessian_approximation='limited-memory'): {gen.num_constraint} GeneralConstraint rows are "
+                                     f"left on the border of the tile path, and its limited-memory mode takes at most {TILE_LBFGS_MAX_ROWS} "
+                                     "of them (12 rows of the compact matrix + the coupling rows in one panel of 16); use 'exact' or 'auto'")
             elif gen is not None or wide_embedded or max(d.num_state for d in s_dyn) >= 17:
                 if ha == "limited-memory":
                     raise ValueError(f"Options(hessian_approximation='limited-memory'): the {gen.num_constraint} GeneralConstraint row(s) "
@@ -847,6 +859,43 @@ class Solver:
                                                              npp.ctypes.data_as(capi.c_int32_p) if npp is not None else None,
                                                              sig.ctypes.data_as(capi.c_double_p), ok.ctypes.data_as(capi.c_int32_p),
                                                              singular.ctypes.data_as(capi.c_int32_p), stream or None))
+        return ok, singular
+
+    def kkt_lbfgs_border_rows(self, m, s_ptr, lds, y_ptr, ldy, sigma, nr, gx_ptr, ldgx, c_ptr, ldc, gc_ptr=0, ldgc=0, npairs=None, stream=0):
+        """kkt_lbfgs_border with nr rows of the caller's in the same border of 2 m + nr <= 16 rows (include/dto.h:
+        dto_kkt_lbfgs_border_rows), tile path only: the diagonal block is blkdiag(M, C).  gx_ptr / gc_ptr / c_ptr: DEVICE, layout of
+        kkt_border_factor with nb = nr (row j of instance b in row b * nr + j; gc_ptr = 0: zero on the constraint side; c [B][ldc],
+        nr x nr row-major); the other arguments as kkt_lbfgs_border.  Afterwards rhs_b / sol_b of kkt_border_solve, kkt_border_multiply
+        and kkt_border_solve_refined have 2 m + nr entries: the first 2 m belong to the compact part (right-hand side 0), the last nr
+        to the rows.  Returns (inertia_ok[B], singular[B]): the Schur complement has neg(M) + nr negative eigenvalues and neither it
+        nor M a numerically zero one; a zero pivot in its LU.  nr = 0 is kkt_lbfgs_border."""
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (m, s_ptr, y_ptr, nr, gx_ptr, c_ptr, gc_ptr)):
+            raise TypeError("kkt_lbfgs_border_rows takes m, nr and device pointers as integers (tensor.data_ptr())")
+        if nr < 0:
+            raise ValueError("kkt_lbfgs_border_rows: nr is a non-negative integer")
+        B = getattr(self, "_B", 0) or 0
+        sig = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+        if sig.shape[0] != B:
+            raise ValueError(f"kkt_lbfgs_border_rows: sigma has one entry per instance of the assembled batch ({B}), got {sig.shape[0]}")
+        if not np.all(np.isfinite(sig)) or not np.all(sig > 0.0):
+            raise ValueError("kkt_lbfgs_border_rows: sigma must be positive and finite")
+        npp = None
+        if npairs is not None:
+            npp = np.ascontiguousarray(np.asarray(npairs).reshape(-1))
+            if npp.shape[0] != B or not np.issubdtype(npp.dtype, np.integer) or np.any(npp < 0) or np.any(npp > m):
+                raise ValueError(f"kkt_lbfgs_border_rows: npairs has one integer in 0..m per instance of the assembled batch ({B})")
+            npp = npp.astype(np.int32)
+        if s_ptr and s_ptr == y_ptr:
+            raise ValueError("kkt_lbfgs_border_rows: s and y are two arrays")
+        if nr > 0 and (not gx_ptr or not c_ptr):
+            raise ValueError("kkt_lbfgs_border_rows: nr > 0 needs the rows (gx_ptr) and their block (c_ptr)")
+        ok, singular = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        capi.check(self._solve_nlp._lib.dto_kkt_lbfgs_border_rows(self._solve_nlp._h, int(m), s_ptr or None, lds, y_ptr or None, ldy,
+                                                                  npp.ctypes.data_as(capi.c_int32_p) if npp is not None else None,
+                                                                  sig.ctypes.data_as(capi.c_double_p), int(nr), gx_ptr or None, ldgx,
+                                                                  gc_ptr or None, ldgc, c_ptr or None, ldc,
+                                                                  ok.ctypes.data_as(capi.c_int32_p), singular.ctypes.data_as(capi.c_int32_p),
+                                                                  stream or None))
         return ok, singular
 
     def kkt_factor(self, stream=0):

@@ -194,13 +194,15 @@ typedef struct dto_options {
    * DTO_HESSIAN_LBFGS: Ipopt's hessian_approximation = limited-memory, i.e. what the reference runs when a problem is built
    * with evaluate_hessian = false (src/solver.jl:7, its default and its own acrobot / car examples): compact L-BFGS, history 6,
    * sigma = s'y / s's, updates skipped without curvature -- no second derivatives are evaluated.  Lane-per-instance solver
-   * path, and dto_solve_batch / dto_solve on the tile path (17 .. 64 states) without GeneralConstraint rows: there the compact matrix
-   * is a border of 12 rows on a first-order factorisation (dto_kkt_assemble_first_order, dto_kkt_lbfgs_border) inside the
-   * host-driven bordered loop.  Where the mode does not exist the library says what it runs instead (dto_solver_hessian_mode): a
+   * path, and dto_solve_batch / dto_solve on the tile path (17 .. 64 states): there the compact matrix is a border of 12 rows on a
+   * first-order factorisation (dto_kkt_assemble_first_order, dto_kkt_lbfgs_border) inside the host-driven bordered loop, with at
+   * most four coupling rows in limited-memory mode on the tile path (multi-knot GeneralConstraint rows share the panel of 16:
+   * dto_kkt_lbfgs_border_rows; with more than four the exact second derivatives run and are reported).  Where the mode does not exist the library says what it runs instead (dto_solver_hessian_mode): a
    * model plugin built without Hessians (evaluate_hessian = 0 in its generator) keeps per-stage SR1 blocks; the STEPWISE entry
    * points of the tile path (dto_solver_begin / begin_warm / iterate / run / shift) keep their exact-Hessian state and report
    * DTO_HESSIAN_EXACT whatever is asked for -- only dto_solve_batch / dto_solve run the limited-memory mode there -- and the
-   * bordered (multi-knot GeneralConstraint) paths use the exact second derivatives of the traced expressions. */
+   * bordered (multi-knot GeneralConstraint) path of the lane-per-instance solver uses the exact second derivatives of the traced
+   * expressions. */
   int hessian_approximation;         /* DTO_HESSIAN_EXACT */
   /* ABI 4: passes of iterative refinement per KKT step (0 = none).  One pass: the residual r = b - K v of the step just computed,
    * evaluated stage by stage from the code the sweeps factorise, one more factor + solve for K e = r, v := v + e.  Measured on the
@@ -411,6 +413,29 @@ int dto_kkt_border_solve_refined(dto_problem* p, int passes, const double* rhs_x
  * bit-identical from run to run (no atomic sums; both Gram passes are summed in the chunks of dto_kkt_border_factor). */
 int dto_kkt_lbfgs_border(dto_problem* p, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy, const int32_t* npairs,
                          const double* sigma, int32_t* inertia_ok, int32_t* schur_singular, void* stream);
+/* The same with nr rows of the caller's beside the compact matrix, in ONE border of nb = 2 m + nr rows (tile path):
+ *     [ K0   U    G' ] [ v ]   [ r ]      U' = [sigma S; Y] as above, G: the caller's rows (coupling constraints, say),
+ *     [ U'   M    0  ] [ w ] = [ 0 ]      the diagonal block blkdiag(M, C), C the caller's nr x nr block
+ *     [ G    0    C  ] [ y ]   [ t ]
+ * i.e. [K G'; G C] [v; y] = [r; t] with K = K0 - U M^-1 U'.  g_x / g_c / c: layout and meaning of dto_kkt_border_factor with nb = nr
+ * (row j of instance b is row b * nr + j; g_c may be NULL: zero on the constraint side; c is [B][ldc], nr x nr row-major, its
+ * symmetric part is used), DEVICE arrays.  One launch appends the rows to the panel behind the history rows, the layout step of M
+ * places C beside it; M has the bits dto_kkt_lbfgs_border gives it for the same history.  Afterwards dto_kkt_border_solve,
+ * dto_kkt_border_multiply and dto_kkt_border_solve_refined act on the bordered matrix with rhs_b / sol_b of nb entries: the first
+ * 2 m belong to the compact part (right-hand side 0), the last nr to the rows.
+ * inertia_ok (HOST [B], may be NULL): 1 exactly when the Schur complement blkdiag(M, C) - [U G']' K0^-1 [U G'] has neg(M) + nr negative
+ * eigenvalues and neither M nor the Schur complement a numerically zero one (the Jacobi and the 1e-13 rule of dto_kkt_lbfgs_border).
+ * Why: the whole matrix has inertia In(K0) + In(Schur) = In(M) + In([K G'; G C]); for K bordered by nr constraint rows to have
+ * (num_variables, Ns + nr) given K0 at (num_variables, Ns), the Schur complement needs pos(M) positive and neg(M) + nr negative
+ * eigenvalues.  C is not inspected on its own (it is 0 for an equality row with delta_c = 0).
+ * Errors: 2 m + nr > 16: DTO_ERR_UNSUPPORTED (one panel); nr < 0, a null g_x or c with nr > 0, ldgx < num_variables,
+ * ldgc < num_constraint (with g_c) or ldc < nr * nr: DTO_ERR_INVALID; everything else as dto_kkt_lbfgs_border.  A refused call writes
+ * nothing and launches nothing.  nr = 0 is dto_kkt_lbfgs_border, bit for bit.  No atomic sums: results are bit-identical from run to run. */
+int dto_kkt_lbfgs_border_rows(dto_problem* p, int64_t m, const double* s, int64_t lds, const double* y, int64_t ldy,
+                              const int32_t* npairs, const double* sigma,
+                              int64_t nr, const double* g_x, int64_t ldgx, const double* g_c, int64_t ldgc,
+                              const double* c, int64_t ldc,
+                              int32_t* inertia_ok, int32_t* schur_singular, void* stream);
 
 /* Batched interior-point solve, one independent NLP per instance, same structure, different guesses.
  * x0: DEVICE [B][ldx] initial guesses (what initialize_states!/initialize_controls! set,
@@ -424,7 +449,8 @@ int dto_kkt_lbfgs_border(dto_problem* p, int64_t m, const double* s, int64_t lds
  * GeneralConstraint whose rows couple several knots is solved through a border (general rows and the rows of stage Constraints
  * equalities or inequalities c <= 0, variables free, fixed or bounded on either side -- the problem's shared bounds, by a
  * primal-dual barrier whose bound multipliers are not returned; shared parameters or dto_batch.params, ldp < num_parameters being
- * DTO_ERR_INVALID before anything is written; no warm start, no limited-memory mode), the filter line-search loop around it
+ * DTO_ERR_INVALID before anything is written; no warm start; a limited-memory mode on the tile path only, last item below), the
+ * filter line-search loop around it
  * driven from the host (dto_kkt_step_batch on such a problem stays the plain Newton step of the bordered system: no barrier
  * terms of the bounds or of inequality rows in it).  All barrier kinds of an instance -- bounds, slacks of inequality general
  * rows, slacks of inequality stage rows -- share one barrier parameter; the multiplier of an inequality row comes back >= 0 in
@@ -437,12 +463,14 @@ int dto_kkt_lbfgs_border(dto_problem* p, int64_t m, const double* s, int64_t lds
  *   panel substitution for all n_g rows and one bordered solve per step (dto_kkt_border_factor / dto_kkt_border_solve inside); at
  *   most 16 general rows (more: DTO_ERR_UNSUPPORTED), no stage rows.  dto_solve_batch, dto_solve and dto_kkt_step_batch take such a
  *   problem; dto_solver_begin / begin_warm / iterate / run / shift and dto_solver_set_bounds return DTO_ERR_UNSUPPORTED for it
- *   (cold starts only, the problem's shared bounds).  dto_solver_hessian_mode reports DTO_HESSIAN_EXACT, kkt_refinement is ignored;
- * - tile path WITHOUT general rows and dto_options.hessian_approximation = DTO_HESSIAN_LBFGS: the same host-driven loop with zero
- *   general rows, its step a first-order factorisation with the compact L-BFGS matrix (history 6) as a border of 12 rows; the history
- *   lives on the device, 12 x num_variables doubles per instance (the size is reported if the allocation fails).  The problem's
- *   shared bounds, shared or per-instance parameters, filter line search (no penalty phase), cold starts only.
- *   dto_solver_hessian_mode reports DTO_HESSIAN_LBFGS after such a solve. */
+ *   (cold starts only, the problem's shared bounds).  dto_solver_hessian_mode reports DTO_HESSIAN_EXACT (with
+ *   DTO_HESSIAN_EXACT asked for, or more than four general rows), kkt_refinement is ignored;
+ * - tile path with dto_options.hessian_approximation = DTO_HESSIAN_LBFGS and at most four general rows (none included): the same
+ *   host-driven loop, its step a first-order factorisation with the compact L-BFGS matrix (history 6) as a border of 12 rows; the
+ *   general rows share that panel (12 + n_g <= 16: dto_kkt_lbfgs_border_rows), their multipliers enter the secant pairs.  The
+ *   history lives on the device, 12 x num_variables doubles per instance (the size is reported if the allocation fails).  The
+ *   problem's shared bounds, inequality general rows, shared or per-instance parameters, filter line search (no penalty phase), cold
+ *   starts only.  dto_solver_hessian_mode reports DTO_HESSIAN_LBFGS after such a solve. */
 int dto_solve_batch(dto_problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                     double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 

@@ -335,6 +335,71 @@ function kkt_border_solve_refined!(ev::GPUEvaluator, nb::Integer, rhs_x::Ptr{Flo
     return nothing
 end
 
+struct DtoKktSystem                 # include/dto.h: dto_kkt_system (DEVICE pointers)
+    mu::Ptr{Float64}
+    ldmu::Int64
+    sigma_x::Ptr{Float64}
+    ldsx::Int64
+    sigma_c::Ptr{Float64}
+    ldsc::Int64
+    delta_w::Float64
+    delta_c::Float64
+end
+
+"""
+    kkt_assemble_first_order!(ev, B, x, delta_w, delta_c; sigma_x = C_NULL, sigma_c = C_NULL)
+
+The first-order KKT system `[diag(sigma_x) + delta_w I, J'; J, -diag(sigma_c) - delta_c I]` at the points `x` (DEVICE,
+num_variables × B; `dto_kkt_assemble_first_order`, tile path: 17..64-state models): no second derivative is evaluated and no
+multipliers are read.  `sigma_x` / `sigma_c` are DEVICE arrays num_variables × B / num_constraint × B or `C_NULL`.  Factorise it
+with `dto_kkt_factor`; the `kkt_*` calls of this file then act on it.
+"""
+function kkt_assemble_first_order!(ev::GPUEvaluator, B::Integer, x::Ptr{Float64}, delta_w::Real, delta_c::Real;
+                                   sigma_x = Ptr{Float64}(C_NULL), sigma_c = Ptr{Float64}(C_NULL))
+    nz, nc = ev.num_variables, ev.num_constraint
+    batch = DtoBatch(B, x, nz, Ptr{Float64}(C_NULL), 0, C_NULL)
+    sys = DtoKktSystem(Ptr{Float64}(C_NULL), 0, sigma_x, nz, sigma_c, nc, Float64(delta_w), Float64(delta_c))
+    dto_check(ccall((:dto_kkt_assemble_first_order, libdto), Cint, (Ptr{Cvoid}, Ref{DtoBatch}, Ref{DtoKktSystem}), ev.handle, batch, sys))
+    return nothing
+end
+
+"""
+    kkt_lbfgs_border!(ev, m, B, s, y, sigma; npairs = nothing) -> (inertia_ok, singular)
+    kkt_lbfgs_border_rows!(ev, m, B, s, y, sigma, nr, g_x, g_c, c; npairs = nothing) -> (inertia_ok, singular)
+
+The compact limited-memory BFGS matrix `B = sigma I - W M⁻¹ W'` as a border of 2m rows on the system factorised last
+(`dto_kkt_lbfgs_border`, tile path), and the same with `nr` rows of the caller's in one border of 2m + nr ≤ 16 rows
+(`dto_kkt_lbfgs_border_rows`: the diagonal block is blkdiag(M, C)).  DEVICE arrays: `s` / `y` num_variables × (m·B), pair j of
+instance b in column b·m + j, oldest first; `g_x` num_variables × (nr·B), `g_c` num_constraint × (nr·B) or `C_NULL`, `c` (nr·nr) × B.
+HOST: `sigma` (B positive numbers, which THE CALLER also puts on the x-diagonal through `sigma_x` of the assemble call) and `npairs`
+(B integers in 0..m, or `nothing` for m everywhere).  Afterwards `kkt_border_solve!` with nb = 2m (+ nr) and zeros in the first 2m
+entries of `rhs_b` solves with the quasi-Newton matrix in place; the last nr entries belong to the rows.  Returns two host `Int32`
+vectors: the Schur complement has neg(M) (+ nr) negative eigenvalues and no numerically zero one; a zero pivot in its LU.
+"""
+function kkt_lbfgs_border!(ev::GPUEvaluator, m::Integer, B::Integer, s::Ptr{Float64}, y::Ptr{Float64}, sigma::Vector{Float64};
+                           npairs::Union{Vector{Int32}, Nothing} = nothing)
+    nz = ev.num_variables
+    ok, singular = Vector{Int32}(undef, B), Vector{Int32}(undef, B)
+    np = npairs === nothing ? C_NULL : npairs                     # (ccall converts either to Ptr{Int32})
+    dto_check(ccall((:dto_kkt_lbfgs_border, libdto), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}),
+                    ev.handle, m, s, nz, y, nz, np, sigma, ok, singular, C_NULL))
+    return ok, singular
+end
+
+function kkt_lbfgs_border_rows!(ev::GPUEvaluator, m::Integer, B::Integer, s::Ptr{Float64}, y::Ptr{Float64}, sigma::Vector{Float64},
+                                nr::Integer, g_x::Ptr{Float64}, g_c::Ptr{Float64}, c::Ptr{Float64};
+                                npairs::Union{Vector{Int32}, Nothing} = nothing)
+    nz, nc = ev.num_variables, ev.num_constraint
+    ok, singular = Vector{Int32}(undef, B), Vector{Int32}(undef, B)
+    np = npairs === nothing ? C_NULL : npairs                     # (ccall converts either to Ptr{Int32})
+    dto_check(ccall((:dto_kkt_lbfgs_border_rows, libdto), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}),
+                    ev.handle, m, s, nz, y, nz, np, sigma, nr, g_x, nz, g_c, nc, c, nr * nr, ok, singular, C_NULL))
+    return ok, singular
+end
+
 """
     set_bounds_batch!(ev, lower, upper)
     set_bounds_batch!(ev, nothing, nothing)

@@ -1,11 +1,15 @@
 """Limited-memory mode of the tile path: time of one outer iteration against the exact mode on the same tree, and of the compact
-border alone (dto_kkt_lbfgs_border).  For the record, no claim and no threshold.
+border alone (dto_kkt_lbfgs_border / dto_kkt_lbfgs_border_rows).  For the record, no claim and no threshold.
 
     python tools/wide_lbfgs_bench.py --T 16 --B 3 --iters 20
     python tools/wide_lbfgs_bench.py --T 2000 --B 8 --iters 10
+    python tools/wide_lbfgs_bench.py --T 16 --B 3 --iters 20 --general-row
 
-One JSON line: ms per outer iteration of solve_batch stopped at max_iter = iters in both modes (the second of two runs, so that
-allocations are paid), and ms per dto_kkt_lbfgs_border call with a full history of 6 pairs (median of `reps`)."""
+--general-row: the same problem with one coupling GeneralConstraint row, q1[T // 3] + q1[2 T // 3] = 0.2, left on the border -- the
+limited-memory mode then runs 13 border rows, the exact mode the row alone.
+
+One JSON line: ms per outer iteration of solve_batch stopped at max_iter = iters in both modes (after one run that pays the
+allocations: the median of `reps` runs), and ms per border call with a full history of 6 pairs (median of `reps`)."""
 import argparse
 import json
 import os
@@ -17,21 +21,33 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def general_row(T):
+    return (max(2, T // 3), 2 * T // 3, 0.2)
+
+
+def build(T, mode, iters, row):
+    import dto_amd
+    from dto_amd import problems as P
+    p = P.build_acrobot_padded(T=T, target=0.5, terminal="physical", **(dict(general_row=general_row(T)) if row else {}))
+    s = dto_amd.Solver(p["dynamics"], p["objective"], p["constraints"], p["bounds"], evaluate_hessian=True,
+                       general_constraint=p.get("general_constraint"), options=dto_amd.Options(hessian_approximation=mode, max_iter=iters),
+                       name="acrobot_padded_g" if row else "acrobot_padded")
+    return s, p
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=16)
     ap.add_argument("--B", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--general-row", action="store_true")
     a = ap.parse_args()
     import torch
     import dto_amd
-    from dto_amd import problems as P
-    out = dict(T=a.T, B=a.B, iters=a.iters)
-    p = P.build_acrobot_padded(T=a.T, target=0.5, terminal="physical")
+    out = dict(T=a.T, B=a.B, iters=a.iters, general_row=list(general_row(a.T)) if a.general_row else None)
     for mode in ("limited-memory", "exact"):
-        s = dto_amd.Solver(p["dynamics"], p["objective"], p["constraints"], p["bounds"], evaluate_hessian=True,
-                           options=dto_amd.Options(hessian_approximation=mode, max_iter=a.iters), name="acrobot_padded")
+        s, p = build(a.T, mode, a.iters, a.general_row)
         nz, nc = s.nlp.num_variables, s.nlp.num_constraint
         Z = np.zeros((a.B, nz))
         for b in range(a.B):
@@ -41,14 +57,14 @@ def main():
         z0 = torch.tensor(Z, device="cuda")
         zo = torch.empty((a.B, nz), device="cuda", dtype=torch.float64)
         lo = torch.empty((a.B, nc), device="cuda", dtype=torch.float64)
-        for _ in range(2):
+        ts = []
+        for _ in range(1 + a.reps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             status, iters = s.solve_batch(z0.data_ptr(), a.B, nz, zo.data_ptr(), nz, lo.data_ptr(), nc)
             torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-        out[mode] = dict(ms_per_iteration=1e3 * dt / max(1, int(np.max(iters))), iterations=[int(v) for v in iters],
-                         mode=s.hessian_mode_last())
+            ts.append(1e3 * (time.perf_counter() - t0) / max(1, int(np.max(iters))))
+        out[mode] = dict(ms_per_iteration=float(np.median(ts[1:])), iterations=[int(v) for v in iters], mode=s.hessian_mode_last())
         if mode == "limited-memory":
             rng = np.random.default_rng(0)
             S = torch.tensor(rng.standard_normal((a.B * 6, nz)), device="cuda")
@@ -56,13 +72,22 @@ def main():
             sx = torch.full((a.B, nz), 1.0, device="cuda", dtype=torch.float64)
             s.kkt_assemble_first_order(z0.data_ptr(), a.B, nz, 1.0, 1e-8, sigma_x_ptr=sx.data_ptr(), ldsx=nz)
             s.kkt_factor()
-            ts = []
-            for _ in range(a.reps):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                s.kkt_lbfgs_border(6, S.data_ptr(), nz, Y.data_ptr(), nz, [1.0] * a.B)
-                ts.append(1e3 * (time.perf_counter() - t0))
-            out["lbfgs_border_ms"] = float(np.median(ts))
+            ka, kb, _ = general_row(a.T)
+            G = torch.zeros((a.B, nz), device="cuda", dtype=torch.float64)
+            G[:, (ka - 1) * 65] = 1.0
+            G[:, (kb - 1) * 65] = 1.0
+            C = torch.full((a.B, 1), -1e-8, device="cuda", dtype=torch.float64)
+            calls = {"lbfgs_border_ms": lambda: s.kkt_lbfgs_border(6, S.data_ptr(), nz, Y.data_ptr(), nz, [1.0] * a.B),
+                     "lbfgs_border_rows_ms": lambda: s.kkt_lbfgs_border_rows(6, S.data_ptr(), nz, Y.data_ptr(), nz, [1.0] * a.B, 1, G.data_ptr(), nz,
+                                                                             C.data_ptr(), 1)}
+            for key, call in calls.items():
+                ts = []
+                for _ in range(1 + a.reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    call()
+                    ts.append(1e3 * (time.perf_counter() - t0))
+                out[key] = float(np.median(ts[1:]))
         s.close()
     print(json.dumps(out))
 
