@@ -609,6 +609,189 @@ static __global__ __launch_bounds__(64) void k_border_trial(const double* rows, 
   }
 }
 
+// ---- the bordered step of the solver on the lane path, device side (dto_solver.cpp: bordered_step_device; DTO_BORDER_HOST=1
+//      selects the host algebra of bordered_step_host instead).  Only the per-instance numbers the host-driven solve loop reads and
+//      B flags cross PCIe; the Jacobian, the n_g + 1 right-hand sides and solutions and the border algebra stay on the device.
+// General rows of the lane path's device border: the LDS arrays of k_border_solve.  A limit of its own -- KB_MAX is the rows of one
+// panel of right-hand sides on the tile path -- that happens to have the same value.
+constexpr int BORDER_MAX_NG = 16;
+
+// S y = r for the n x n Schur complement of a border, in place on the caller's storage (S: n * n row-major, r: n, L: n * n scratch
+// of the Cholesky factor; n <= BORDER_MAX_NG in the LDS arrays of k_border_solve, any n in the vectors of bordered_step_host).
+// Returns whether S is negative definite -- Cholesky of -S, symmetrised: the inertia of the bordered matrix is then (Nz, Nc) -- and
+// leaves y in r: Gaussian elimination with partial pivoting and back substitution, whatever the verdict.  An exactly zero pivot
+// makes the verdict false and its unknown zero.  One statement order for the device and the host: the two borders agree to the
+// last bit where their inputs do.
+__host__ __device__ __forceinline__ bool border_schur_solve(int ng, double* Sm, double* rg, double* Lc) {
+  bool negdef = true;
+  for (int a = 0; a < ng && negdef; ++a)
+    for (int q = 0; q <= a; ++q) {
+      double acc = -0.5 * (Sm[a * ng + q] + Sm[q * ng + a]);
+      for (int k = 0; k < q; ++k) acc -= Lc[a * ng + k] * Lc[q * ng + k];
+      if (a == q) { if (!(acc > 0.0)) { negdef = false; break; } Lc[a * ng + a] = sqrt(acc); }
+      else Lc[a * ng + q] = acc / Lc[q * ng + q];
+    }
+  for (int k = 0; k < ng; ++k) {
+    int piv = k;
+    for (int r = k + 1; r < ng; ++r) if (fabs(Sm[r * ng + k]) > fabs(Sm[piv * ng + k])) piv = r;
+    if (piv != k) {
+      for (int q = 0; q < ng; ++q) { const double t = Sm[k * ng + q]; Sm[k * ng + q] = Sm[piv * ng + q]; Sm[piv * ng + q] = t; }
+      const double t = rg[k]; rg[k] = rg[piv]; rg[piv] = t;
+    }
+    const double d = Sm[k * ng + k];
+    if (d == 0.0) { negdef = false; continue; }
+    for (int r = k + 1; r < ng; ++r) {
+      const double f = Sm[r * ng + k] / d;
+      for (int q = k; q < ng; ++q) Sm[r * ng + q] -= f * Sm[k * ng + q];
+      rg[r] -= f * rg[k];
+    }
+  }
+  for (int k = ng - 1; k >= 0; --k) {
+    double acc = rg[k];
+    for (int q = k + 1; q < ng; ++q) acc -= Sm[k * ng + q] * rg[q];
+    rg[k] = Sm[k * ng + k] != 0.0 ? acc / Sm[k * ng + k] : 0.0;
+  }
+  return negdef;
+}
+// r_x = grad f + J' mu column by column (entries of a column in COO order: the same sums as the host loop of round 3), the
+// general rows of J as dense vectors, the first right-hand side
+static __global__ void k_border_rx(int64_t B, int64_t Nz, int64_t Ns, int64_t nnzJ, const double* J, const double* g, const double* mu,
+                                   int64_t ldmu, const int* cptr, const int* ck, const int* crow, double* rx, double* rhsx, double* Grow,
+                                   BorderBar bar) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * Nz) return;
+  const int64_t b = idx / Nz, col = idx - b * Nz;
+  double acc = g[idx];
+  for (int e = cptr[col]; e < cptr[col + 1]; ++e) {
+    const double v = J[b * nnzJ + ck[e]];
+    const int row = crow[e];
+    acc += v * mu[b * ldmu + row];
+    if (row >= Ns) Grow[((int64_t)(row - Ns) * B + b) * Nz + col] += v;   // (this thread owns column col of instance b)
+  }
+  if (bar.z) {
+    // finite bounds: r_x with the bound multipliers, the right-hand side with the barrier gradient (this kernel runs once per point:
+    // a further delta_w attempt keeps both)
+    const wide::WideBar wb = wide::wide_bar(bar.z[idx], bar.lo[col], bar.hi[col], bar.zl[idx], bar.zu[idx], bar.mu[b]);
+    rx[idx] = acc + wb.zdiff;
+    rhsx[idx] = -(acc - wb.br);
+    return;
+  }
+  rx[idx] = acc;
+  rhsx[idx] = -acc;
+}
+// what the host loop needs of the point and the step, per instance: theta_1, theta_inf (rows n0 .. get their slack added), the
+// dual infeasibility over the free variables, sum |lam|, grad f' dz -- five numbers instead of five vectors over PCIe
+static __global__ __launch_bounds__(64) void k_border_stats(int64_t Nz, int64_t Nc, const double* c, const double* rx, const double* g,
+                                                            const double* dz, const double* lam, const int* fixed, const double* shift,
+                                                            int64_t n0, int64_t nsh, double* out, const double* sshift = nullptr,
+                                                            int64_t nss = 0) {
+  // sshift (optional, [B][nss]): the slacks of the stage rows, added to rows 0 .. nss - 1 (zero on equality rows)
+  const int64_t b = blockIdx.x;
+  const int l = threadIdx.x;
+  double th1 = 0.0, thinf = 0.0, dinf = 0.0, slam = 0.0, gd = 0.0;
+  for (int64_t k = l; k < Nc; k += 64) {
+    double cv = c[b * Nc + k] + ((shift && k >= n0) ? shift[b * nsh + (k - n0)] : 0.0);
+    if (sshift && k < nss) cv += sshift[b * nss + k];
+    const double v = fabs(cv);
+    th1 += v; thinf = fmax(thinf, v); slam += fabs(lam[b * Nc + k]);
+  }
+  for (int64_t k = l; k < Nz; k += 64) {
+    if (!fixed[k]) dinf = fmax(dinf, fabs(rx[b * Nz + k]));
+    gd += g[b * Nz + k] * dz[b * Nz + k];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    th1 += __shfl_down(th1, off, 64); slam += __shfl_down(slam, off, 64); gd += __shfl_down(gd, off, 64);
+    thinf = fmax(thinf, __shfl_down(thinf, off, 64)); dinf = fmax(dinf, __shfl_down(dinf, off, 64));
+  }
+  if (l == 0) { double* o = out + b * 5; o[0] = th1; o[1] = thinf; o[2] = dinf; o[3] = slam; o[4] = gd; }
+}
+// per-instance delta_w on the primal diagonal; a variable with lo == hi gets a huge entry instead (its step is ~1e-16 r); with
+// finite bounds (bar.z != NULL) the others get delta_w + z_L/(x-lo) + z_U/(hi-x)
+static __global__ void k_border_sig(int64_t B, int64_t Nz, const double* dw, const int* fixed, int pin_fixed, double* sig, BorderBar bar) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * Nz) return;
+  const int64_t b = idx / Nz, col = idx % Nz;
+  if (bar.z && !(pin_fixed && fixed[col])) {
+    sig[idx] = dw[b] + wide::wide_bar(bar.z[idx], bar.lo[col], bar.hi[col], bar.zl[idx], bar.zu[idx], bar.mu[b]).sig;
+    return;
+  }
+  sig[idx] = (pin_fixed && fixed[col]) ? 1e16 : dw[b];
+}
+// sl (sl.s != NULL: slack-eliminated inequality stage rows, see BorderSlack): such a row gets -(c + mu / nu) and s / nu in sigc
+// ([B][Nc], zero everywhere else), nu its entry of the multipliers
+static __global__ void k_border_rhsc(int64_t B, int64_t Nc, int64_t Ns, const double* c, double* rhsc, BorderSlack sl = BorderSlack(),
+                                     const double* mu = nullptr, int64_t ldmu = 0, double* sigc = nullptr) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * Nc) return;
+  if (sl.s) {
+    const int64_t b = idx / Nc, k = idx - b * Nc;
+    if (k < Ns && sl.mask[k]) {
+      const double nu = mu[b * ldmu + k];
+      rhsc[idx] = -(c[idx] + sl.mu[b] / nu);
+      sigc[idx] = sl.s[b * sl.Ns + k] / nu;
+      return;
+    }
+    sigc[idx] = 0.0;
+  }
+  rhsc[idx] = (idx % Nc) < Ns ? -c[idx] : 0.0;
+}
+// one wavefront per instance: S = -(G Y_x + dc I), r_g = -c_g - G v0_x (lane-strided partial sums, fixed tree), then lane 0: S
+// negative definite? and S drho = r_g (border_schur_solve)
+static __global__ __launch_bounds__(64) void k_border_solve(int64_t B, int64_t Nz, int64_t Nc, int64_t Ns, int ng, double delta_c,
+                                                            const double* Grow, const double* Yx, const double* v0x, const double* c,
+                                                            const double* gdiag, const double* gshift, double* rho, int* negdef_out) {
+  const int64_t b = blockIdx.x;
+  const int l = threadIdx.x;
+  __shared__ double Sm[BORDER_MAX_NG * BORDER_MAX_NG], rg[BORDER_MAX_NG], Lc[BORDER_MAX_NG * BORDER_MAX_NG];
+  auto gdot = [&](int row, const double* v) {
+    const double* gr = Grow + ((int64_t)row * B + b) * Nz;
+    double acc = 0.0;
+    for (int64_t k = l; k < Nz; k += 64) acc += gr[k] * v[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    return acc;   // lane 0
+  };
+  for (int a = 0; a < ng; ++a) {
+    for (int q = 0; q < ng; ++q) {
+      const double d = gdot(a, Yx + ((int64_t)q * B + b) * Nz);
+      // slack-eliminated inequality rows (general_solve_batch): s / nu on the diagonal, mu / nu in the right-hand side
+      if (l == 0) Sm[a * ng + q] = -d - (a == q ? delta_c + (gdiag ? gdiag[b * ng + a] : 0.0) : 0.0);
+    }
+    const double d = gdot(a, v0x + b * Nz);
+    if (l == 0) rg[a] = -c[b * Nc + Ns + a] - (gshift ? gshift[b * ng + a] : 0.0) - d;
+  }
+  if (l != 0) return;
+  const bool negdef = border_schur_solve(ng, Sm, rg, Lc);
+  for (int q = 0; q < ng; ++q) rho[b * ng + q] = rg[q];
+  negdef_out[b] = negdef ? 1 : 0;
+}
+// v = v0 - Y drho; the multipliers of the general rows are drho
+static __global__ void k_border_apply(int64_t B, int64_t Nz, int64_t Nc, int64_t Ns, int ng, const double* v0x, const double* v0c,
+                                      const double* Yx, const double* Yc, const double* rho, double* dx, int64_t lddx, double* dmu,
+                                      int64_t lddmu, double* hdx, double* hdm) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * (Nz + Nc)) return;
+  const int64_t b = idx / (Nz + Nc), k = idx - b * (Nz + Nc);
+  if (k < Nz) {
+    double v = v0x[b * Nz + k];
+    for (int q = 0; q < ng; ++q) v -= Yx[((int64_t)q * B + b) * Nz + k] * rho[b * ng + q];
+    dx[b * lddx + k] = v;
+    hdx[b * Nz + k] = v;
+  } else {
+    const int64_t r = k - Nz;
+    double v;
+    if (r < Ns) {
+      v = v0c[b * Nc + r];
+      for (int q = 0; q < ng; ++q) v -= Yc[((int64_t)q * B + b) * Nc + r] * rho[b * ng + q];
+    } else {
+      v = rho[b * ng + (r - Ns)];
+    }
+    dmu[b * lddmu + r] = v;
+    hdm[b * Nc + r] = v;
+  }
+}
+
 // ---- the bordered step of the solver on the tile path (dto_solver.cpp: bordered_step_tile): everything dto_kkt_border_factor /
 //      dto_kkt_border_solve are given, from the derivatives at the point.  One thread per (instance, column) -- a thread owns
 //      column `col` of instance b in r_x, rhs_x and all ng panel rows, so nothing is summed across threads:

@@ -2042,176 +2042,6 @@ struct QnHistory {
   }
 };
 
-// ---- device side of the bordered step (round 4; DTO_BORDER_HOST=1 selects the host algebra of round 3 instead).  Only the
-//      per-instance vectors the host-driven solve loop reads (grad f, c, r_x, the step) and B flags cross PCIe any more; the
-//      Jacobian, the n_g + 1 right-hand sides and solutions and the border algebra stay on the device.
-constexpr int BORDER_MAX_NG = 16;
-// r_x = grad f + J' mu column by column (entries of a column in COO order: the same sums as the host loop of round 3), the
-// general rows of J as dense vectors, the first right-hand side
-static __global__ void k_border_rx(int64_t B, int64_t Nz, int64_t Ns, int64_t nnzJ, const double* J, const double* g, const double* mu,
-                                   int64_t ldmu, const int* cptr, const int* ck, const int* crow, double* rx, double* rhsx, double* Grow,
-                                   BorderBar bar) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= B * Nz) return;
-  const int64_t b = idx / Nz, col = idx - b * Nz;
-  double acc = g[idx];
-  for (int e = cptr[col]; e < cptr[col + 1]; ++e) {
-    const double v = J[b * nnzJ + ck[e]];
-    const int row = crow[e];
-    acc += v * mu[b * ldmu + row];
-    if (row >= Ns) Grow[((int64_t)(row - Ns) * B + b) * Nz + col] += v;   // (this thread owns column col of instance b)
-  }
-  if (bar.z) {
-    // finite bounds: r_x with the bound multipliers, the right-hand side with the barrier gradient (this kernel runs once per point:
-    // a further delta_w attempt keeps both)
-    const wide::WideBar wb = wide::wide_bar(bar.z[idx], bar.lo[col], bar.hi[col], bar.zl[idx], bar.zu[idx], bar.mu[b]);
-    rx[idx] = acc + wb.zdiff;
-    rhsx[idx] = -(acc - wb.br);
-    return;
-  }
-  rx[idx] = acc;
-  rhsx[idx] = -acc;
-}
-// what the host loop needs of the point and the step, per instance: theta_1, theta_inf (rows n0 .. get their slack added), the
-// dual infeasibility over the free variables, sum |lam|, grad f' dz -- five numbers instead of five vectors over PCIe
-static __global__ __launch_bounds__(64) void k_border_stats(int64_t Nz, int64_t Nc, const double* c, const double* rx, const double* g,
-                                                            const double* dz, const double* lam, const int* fixed, const double* shift,
-                                                            int64_t n0, int64_t nsh, double* out, const double* sshift = nullptr,
-                                                            int64_t nss = 0) {
-  // sshift (optional, [B][nss]): the slacks of the stage rows, added to rows 0 .. nss - 1 (zero on equality rows)
-  const int64_t b = blockIdx.x;
-  const int l = threadIdx.x;
-  double th1 = 0.0, thinf = 0.0, dinf = 0.0, slam = 0.0, gd = 0.0;
-  for (int64_t k = l; k < Nc; k += 64) {
-    double cv = c[b * Nc + k] + ((shift && k >= n0) ? shift[b * nsh + (k - n0)] : 0.0);
-    if (sshift && k < nss) cv += sshift[b * nss + k];
-    const double v = fabs(cv);
-    th1 += v; thinf = fmax(thinf, v); slam += fabs(lam[b * Nc + k]);
-  }
-  for (int64_t k = l; k < Nz; k += 64) {
-    if (!fixed[k]) dinf = fmax(dinf, fabs(rx[b * Nz + k]));
-    gd += g[b * Nz + k] * dz[b * Nz + k];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    th1 += __shfl_down(th1, off, 64); slam += __shfl_down(slam, off, 64); gd += __shfl_down(gd, off, 64);
-    thinf = fmax(thinf, __shfl_down(thinf, off, 64)); dinf = fmax(dinf, __shfl_down(dinf, off, 64));
-  }
-  if (l == 0) { double* o = out + b * 5; o[0] = th1; o[1] = thinf; o[2] = dinf; o[3] = slam; o[4] = gd; }
-}
-// per-instance delta_w on the primal diagonal; a variable with lo == hi gets a huge entry instead (its step is ~1e-16 r); with
-// finite bounds (bar.z != NULL) the others get delta_w + z_L/(x-lo) + z_U/(hi-x)
-static __global__ void k_border_sig(int64_t B, int64_t Nz, const double* dw, const int* fixed, int pin_fixed, double* sig, BorderBar bar) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= B * Nz) return;
-  const int64_t b = idx / Nz, col = idx % Nz;
-  if (bar.z && !(pin_fixed && fixed[col])) {
-    sig[idx] = dw[b] + wide::wide_bar(bar.z[idx], bar.lo[col], bar.hi[col], bar.zl[idx], bar.zu[idx], bar.mu[b]).sig;
-    return;
-  }
-  sig[idx] = (pin_fixed && fixed[col]) ? 1e16 : dw[b];
-}
-// sl (sl.s != NULL: slack-eliminated inequality stage rows, see BorderSlack): such a row gets -(c + mu / nu) and s / nu in sigc
-// ([B][Nc], zero everywhere else), nu its entry of the multipliers
-static __global__ void k_border_rhsc(int64_t B, int64_t Nc, int64_t Ns, const double* c, double* rhsc, BorderSlack sl = BorderSlack(),
-                                     const double* mu = nullptr, int64_t ldmu = 0, double* sigc = nullptr) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= B * Nc) return;
-  if (sl.s) {
-    const int64_t b = idx / Nc, k = idx - b * Nc;
-    if (k < Ns && sl.mask[k]) {
-      const double nu = mu[b * ldmu + k];
-      rhsc[idx] = -(c[idx] + sl.mu[b] / nu);
-      sigc[idx] = sl.s[b * sl.Ns + k] / nu;
-      return;
-    }
-    sigc[idx] = 0.0;
-  }
-  rhsc[idx] = (idx % Nc) < Ns ? -c[idx] : 0.0;
-}
-// one wavefront per instance: S = -(G Y_x + dc I), r_g = -c_g - G v0_x (lane-strided partial sums, fixed tree), then lane 0: S
-// negative definite? (Cholesky of -S, symmetrised) and S drho = r_g by Gaussian elimination with partial pivoting
-static __global__ __launch_bounds__(64) void k_border_solve(int64_t B, int64_t Nz, int64_t Nc, int64_t Ns, int ng, double delta_c,
-                                                            const double* Grow, const double* Yx, const double* v0x, const double* c,
-                                                            const double* gdiag, const double* gshift, double* rho, int* negdef_out) {
-  const int64_t b = blockIdx.x;
-  const int l = threadIdx.x;
-  __shared__ double Sm[BORDER_MAX_NG * BORDER_MAX_NG], rg[BORDER_MAX_NG], Lc[BORDER_MAX_NG * BORDER_MAX_NG];
-  auto gdot = [&](int row, const double* v) {
-    const double* gr = Grow + ((int64_t)row * B + b) * Nz;
-    double acc = 0.0;
-    for (int64_t k = l; k < Nz; k += 64) acc += gr[k] * v[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    return acc;   // lane 0
-  };
-  for (int a = 0; a < ng; ++a) {
-    for (int q = 0; q < ng; ++q) {
-      const double d = gdot(a, Yx + ((int64_t)q * B + b) * Nz);
-      // slack-eliminated inequality rows (general_solve_batch): s / nu on the diagonal, mu / nu in the right-hand side
-      if (l == 0) Sm[a * ng + q] = -d - (a == q ? delta_c + (gdiag ? gdiag[b * ng + a] : 0.0) : 0.0);
-    }
-    const double d = gdot(a, v0x + b * Nz);
-    if (l == 0) rg[a] = -c[b * Nc + Ns + a] - (gshift ? gshift[b * ng + a] : 0.0) - d;
-  }
-  if (l != 0) return;
-  bool negdef = true;
-  for (int a = 0; a < ng && negdef; ++a)
-    for (int q = 0; q <= a; ++q) {
-      double acc = -0.5 * (Sm[a * ng + q] + Sm[q * ng + a]);
-      for (int k = 0; k < q; ++k) acc -= Lc[a * ng + k] * Lc[q * ng + k];
-      if (a == q) { if (!(acc > 0.0)) { negdef = false; break; } Lc[a * ng + a] = sqrt(acc); }
-      else Lc[a * ng + q] = acc / Lc[q * ng + q];
-    }
-  for (int k = 0; k < ng; ++k) {
-    int piv = k;
-    for (int r = k + 1; r < ng; ++r) if (fabs(Sm[r * ng + k]) > fabs(Sm[piv * ng + k])) piv = r;
-    if (piv != k) {
-      for (int q = 0; q < ng; ++q) { const double t = Sm[k * ng + q]; Sm[k * ng + q] = Sm[piv * ng + q]; Sm[piv * ng + q] = t; }
-      const double t = rg[k]; rg[k] = rg[piv]; rg[piv] = t;
-    }
-    const double d = Sm[k * ng + k];
-    if (d == 0.0) { negdef = false; continue; }
-    for (int r = k + 1; r < ng; ++r) {
-      const double f = Sm[r * ng + k] / d;
-      for (int q = k; q < ng; ++q) Sm[r * ng + q] -= f * Sm[k * ng + q];
-      rg[r] -= f * rg[k];
-    }
-  }
-  for (int k = ng - 1; k >= 0; --k) {
-    double acc = rg[k];
-    for (int q = k + 1; q < ng; ++q) acc -= Sm[k * ng + q] * rg[q];
-    rg[k] = Sm[k * ng + k] != 0.0 ? acc / Sm[k * ng + k] : 0.0;
-  }
-  for (int q = 0; q < ng; ++q) rho[b * ng + q] = rg[q];
-  negdef_out[b] = negdef ? 1 : 0;
-}
-// v = v0 - Y drho; the multipliers of the general rows are drho
-static __global__ void k_border_apply(int64_t B, int64_t Nz, int64_t Nc, int64_t Ns, int ng, const double* v0x, const double* v0c,
-                                      const double* Yx, const double* Yc, const double* rho, double* dx, int64_t lddx, double* dmu,
-                                      int64_t lddmu, double* hdx, double* hdm) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= B * (Nz + Nc)) return;
-  const int64_t b = idx / (Nz + Nc), k = idx - b * (Nz + Nc);
-  if (k < Nz) {
-    double v = v0x[b * Nz + k];
-    for (int q = 0; q < ng; ++q) v -= Yx[((int64_t)q * B + b) * Nz + k] * rho[b * ng + q];
-    dx[b * lddx + k] = v;
-    hdx[b * Nz + k] = v;
-  } else {
-    const int64_t r = k - Nz;
-    double v;
-    if (r < Ns) {
-      v = v0c[b * Nc + r];
-      for (int q = 0; q < ng; ++q) v -= Yc[((int64_t)q * B + b) * Nc + r] * rho[b * ng + q];
-    } else {
-      v = rho[b * ng + (r - Ns)];
-    }
-    dmu[b * lddmu + r] = v;
-    hdm[b * Nc + r] = v;
-  }
-}
-
 static int ensure_border_csc(Problem* p) {
   if (p->d_csc_ptr) return DTO_OK;
   const Layout& L = p->L;
@@ -2238,6 +2068,36 @@ static int ensure_border_csc(Problem* p) {
   return DTO_OK;
 }
 
+// ---- what the three bordered steps share ------------------------------------------------------------------------------------
+// carving the problem's one workspace (border_ws), in the order of each layout's map comment
+struct BorderCarve {
+  double* w;
+  double* take(size_t n) { double* q = w; w += n; return q; }
+};
+// J, c and grad f of the point into the workspace.  Not at a further delta_w attempt at the same point (reuse_point): everything
+// that depends on the point alone is still there
+static int border_eval_point(dto_problem* h, const dto_batch* b, double* dJ, int64_t nnzJ, double* dC, int64_t Nc, double* dG, int64_t Nz) {
+  int rc;
+  if ((rc = dto_eval_jac_g_batch(h, b, dJ, nnzJ))) return rc;
+  if ((rc = dto_eval_g_batch(h, b, dC, Nc))) return rc;
+  return dto_eval_grad_f_batch(h, b, dG, Nz);
+}
+// per-instance delta_w (dw: host [B]) through the sigma_x diagonal (k_border_sig; pin_fixed: a variable with lo == hi keeps its
+// value; bar: the barrier terms of finite bounds ride the same diagonal), and the system both linear solvers assemble from
+static int border_sigma_system(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c, bool pin_fixed,
+                               const BorderBar& bar, double* dDw, double* dSig, double* dSigC, dto_kkt_system& sys) {
+  const int64_t B = b->B, Nz = p->L.Nz;
+  hipStream_t st = (hipStream_t)b->stream;
+  HIP_TRY(hipMemcpyAsync(dDw, dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_border_sig, dim3((unsigned)(((size_t)B * Nz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw,
+                     (const int*)p->d_var_fixed, pin_fixed ? 1 : 0, dSig, bar);
+  sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = dSigC; sys.ldsc = dSigC ? p->L.Nc : 0;
+  sys.delta_w = 0.0; sys.delta_c = delta_c;
+  return DTO_OK;
+}
+
+// ---- the bordered step on the lane path, border algebra on the device (kernels: dto_border_kernels.hpp): one dto_kkt_solve for
+//      the step and one per general row, k_border_solve / k_border_apply for the Schur complement
 static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
                                 double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
                                 const double* gdiag, const double* gshift, const BorderBar* barp, const BorderSlack* slk) {
@@ -2255,19 +2115,17 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
   const size_t ws_need = (size_t)B * nnzJ + nBc + nBz * 6 + nBc * 4 + (size_t)ng * (2 * nBz + nBc) + (size_t)B * ng + 2 * (size_t)B + 8 +
                          (sl.s ? nBc : 0);
   HIP_TRY(p->border_ws.grow(ws_need));
-  double* w = p->border_ws;
-  auto take = [&](size_t n) { double* q = w; w += n; return q; };
-  double *dJ = take((size_t)B * nnzJ), *dC = take(nBc), *dG = take(nBz), *dSig = take(nBz), *dRxv = take(nBz), *dRhsx = take(nBz),
-         *dRhsc = take(nBc), *dZeroC = take(nBc), *dV0x = take(nBz), *dV0c = take(nBc), *dGrow = take((size_t)ng * nBz),
-         *dYx = take((size_t)ng * nBz), *dYc = take((size_t)ng * nBc), *dHdx = take(nBz), *dHdm = take(nBc), *dRho = take((size_t)B * ng);
-  int* dFlag = reinterpret_cast<int*>(take((size_t)B / 2 + 4));
-  double* dDw = take((size_t)B);
-  double* dSigC = sl.s ? take(nBc) : nullptr;
+  BorderCarve ws{p->border_ws};
+  double *dJ = ws.take((size_t)B * nnzJ), *dC = ws.take(nBc), *dG = ws.take(nBz), *dSig = ws.take(nBz), *dRxv = ws.take(nBz),
+         *dRhsx = ws.take(nBz), *dRhsc = ws.take(nBc), *dZeroC = ws.take(nBc), *dV0x = ws.take(nBz), *dV0c = ws.take(nBc),
+         *dGrow = ws.take((size_t)ng * nBz), *dYx = ws.take((size_t)ng * nBz), *dYc = ws.take((size_t)ng * nBc), *dHdx = ws.take(nBz),
+         *dHdm = ws.take(nBc), *dRho = ws.take((size_t)B * ng);
+  int* dFlag = reinterpret_cast<int*>(ws.take((size_t)B / 2 + 4));
+  double* dDw = ws.take((size_t)B);
+  double* dSigC = sl.s ? ws.take(nBc) : nullptr;
 #define DRC(expr) do { rc = (expr); if (rc) return rc; } while (0)
-  if (!(stats && stats->reuse_point)) {   // (a further delta_w attempt at the same point keeps all of this in the workspace)
-    DRC(dto_eval_jac_g_batch(h, b, dJ, nnzJ));
-    DRC(dto_eval_g_batch(h, b, dC, Nc));
-    DRC(dto_eval_grad_f_batch(h, b, dG, Nz));
+  if (!(stats && stats->reuse_point)) {
+    DRC(border_eval_point(h, b, dJ, nnzJ, dC, Nc, dG, Nz));
     HIP_TRY(hipMemsetAsync(dGrow, 0, (size_t)ng * nBz * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(dZeroC, 0, nBc * sizeof(double), st));
     hipLaunchKernelGGL(k_border_rx, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, Ns, nnzJ, (const double*)dJ, (const double*)dG,
@@ -2275,13 +2133,8 @@ static int bordered_step_device(Problem* p, const dto_batch* b, const double* mu
     hipLaunchKernelGGL(k_border_rhsc, dim3((unsigned)((nBc + 255) / 256)), dim3(256), 0, st, B, Nc, Ns, (const double*)dC, dRhsc, sl, mu, ldmu,
                        dSigC);
   }
-  // per-instance delta_w through the sigma_x diagonal (pin_fixed: a variable with lo == hi keeps its value)
-  HIP_TRY(hipMemcpyAsync(dDw, dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_border_sig, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw, (const int*)p->d_var_fixed,
-                     pin_fixed ? 1 : 0, dSig, bar);
   dto_kkt_system sys;
-  sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = dSigC; sys.ldsc = dSigC ? Nc : 0;
-  sys.delta_w = 0.0; sys.delta_c = delta_c;
+  DRC(border_sigma_system(p, b, mu, ldmu, dw, delta_c, pin_fixed, bar, dDw, dSig, dSigC, sys));
   DRC(dto_kkt_assemble(h, b, &sys));
   std::vector<int32_t> iok((size_t)B, 1);
   DRC(dto_kkt_factor(h, iok.data(), nullptr, (void*)st));
@@ -2372,15 +2225,13 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
   // workspace: J | c | grad | sigma | r_x | rhs_x | rhs_c | panel [B * ng][Nz] | C [B][ng * ng] | rhs_b [B][ng] | delta_w [B]
   const size_t nBz = (size_t)B * Nz, nBc = (size_t)B * Nc, nBg = (size_t)B * ng;
   HIP_TRY(p->border_ws.grow((size_t)B * nnzJ + 2 * nBc + 5 * nBz + nBg * Nz + nBg * ng + nBg + (size_t)B));
-  double* w = p->border_ws;
-  auto take = [&](size_t n) { double* q = w; w += n; return q; };
-  double *dJ = take((size_t)B * nnzJ), *dC = take(nBc), *dG = take(nBz), *dSig = take(nBz), *dRxv = take(nBz), *dRhsx = take(nBz),
-         *dRhsc = take(nBc), *dPanel = take(nBg * Nz), *dCb = take(nBg * ng), *dRhsb = take(nBg), *dDw = take((size_t)B);
+  BorderCarve ws{p->border_ws};
+  double *dJ = ws.take((size_t)B * nnzJ), *dC = ws.take(nBc), *dG = ws.take(nBz), *dSig = ws.take(nBz), *dRxv = ws.take(nBz),
+         *dRhsx = ws.take(nBz), *dRhsc = ws.take(nBc), *dPanel = ws.take(nBg * Nz), *dCb = ws.take(nBg * ng), *dRhsb = ws.take(nBg),
+         *dDw = ws.take((size_t)B);
 #define DRC(expr) do { rc = (expr); if (rc) return rc; } while (0)
-  if (!(stats && stats->reuse_point)) {   // (a further delta_w attempt at the same point keeps J, c, grad f and r_x)
-    DRC(dto_eval_jac_g_batch(h, b, dJ, nnzJ));
-    DRC(dto_eval_g_batch(h, b, dC, Nc));
-    DRC(dto_eval_grad_f_batch(h, b, dG, Nz));
+  if (!(stats && stats->reuse_point)) {
+    DRC(border_eval_point(h, b, dJ, nnzJ, dC, Nc, dG, Nz));
     if (qn) DRC(qn_update(p, *qn, B, dJ, dG, mu, ldmu, st));   // the pair of the step that led here joins the history
   }
   // (the right-hand sides, the panel and C are written again at every attempt: one launch, and nothing to clear first)
@@ -2398,12 +2249,8 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
     dws.resize((size_t)B);
     for (int64_t i = 0; i < B; ++i) dws[(size_t)i] = dw[i] + qn->sigma[(size_t)i];
   }
-  HIP_TRY(hipMemcpyAsync(dDw, qn ? dws.data() : dw, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_border_sig, dim3((unsigned)((nBz + 255) / 256)), dim3(256), 0, st, B, Nz, (const double*)dDw, (const int*)p->d_var_fixed,
-                     pin_fixed ? 1 : 0, dSig, bar);
   dto_kkt_system sys;
-  sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
-  sys.delta_w = 0.0; sys.delta_c = delta_c;
+  DRC(border_sigma_system(p, b, mu, ldmu, qn ? dws.data() : dw, delta_c, pin_fixed, bar, dDw, dSig, nullptr, sys));
   DRC(wide_kkt_assemble(p, b, &sys, qn != nullptr));
   std::vector<int32_t> iok((size_t)B, 1), negdef((size_t)B, 1), sing((size_t)B, 0);
   DRC(wide_kkt_factor(p, iok.data(), nullptr, st));
@@ -2438,46 +2285,34 @@ static int bordered_step_tile(Problem* p, const dto_batch* b, const double* mu, 
   return DTO_OK;
 }
 
-static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
-                         double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
-                         const double* gdiag, const double* gshift, const BorderBar* barp, const BorderSlack* slk) {
-  if (p->vt->launch_wide)   // (no stage rows on the tile path: slk is NULL)
-    return bordered_step_tile(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp);
+// ---- the bordered step on the lane path, border algebra on the host (round 3; DTO_BORDER_HOST=1, or more than BORDER_MAX_NG
+//      general rows): every right-hand side and solution of the n_g + 1 solves crosses PCIe, the Schur complement is formed and
+//      solved here (border_schur_solve, the function lane 0 of k_border_solve calls).  Equality rows and free or fixed variables
+//      only; stats gets whole vectors, which border_loop_host_stats reduces to the numbers the device border delivers
+static int bordered_step_host(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
+                              double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed) {
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc, ng = L.Ngen, Ns = Nc - ng, nnzJ = L.nnzJ;
-  {
-    const char* e = getenv("DTO_BORDER_HOST");
-    if (!(e && atoi(e) != 0) && ng <= BORDER_MAX_NG)
-      return bordered_step_device(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp, slk);
-    if (slk) return set_error(DTO_ERR_UNSUPPORTED, "inequality stage rows beside GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
-    if (barp) return set_error(DTO_ERR_UNSUPPORTED, "variable bounds beside GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
-    if (gdiag) return set_error(DTO_ERR_UNSUPPORTED, "inequality GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
-  }
   hipStream_t st = (hipStream_t)b->stream;
   dto_problem* h = reinterpret_cast<dto_problem*>(p);
   int rc;
-  // one workspace kept in the problem (grown when a larger batch comes): J | c | grad | sigma | rhs_x | rhs_c | sol_x | sol_c
-  HIP_TRY(p->border_ws.grow((size_t)B * ((size_t)nnzJ + 4 * (size_t)Nz + 3 * (size_t)Nc)));
-  double* dJ = p->border_ws;
-  double* dC = dJ + (size_t)B * nnzJ;
-  double* dG = dC + (size_t)B * Nc;
-  double* dSig = dG + (size_t)B * Nz;
-  double* dRx = dSig + (size_t)B * Nz;
-  double* dRc = dRx + (size_t)B * Nz;
-  double* dSx = dRc + (size_t)B * Nc;
-  double* dSc = dSx + (size_t)B * Nz;
+  // workspace: J | c | grad | sigma | rhs_x | rhs_c | sol_x | sol_c
+  const size_t nBz = (size_t)B * Nz, nBc = (size_t)B * Nc;
+  HIP_TRY(p->border_ws.grow((size_t)B * nnzJ + 4 * nBz + 3 * nBc));
+  BorderCarve ws{p->border_ws};
+  double *dJ = ws.take((size_t)B * nnzJ), *dC = ws.take(nBc), *dG = ws.take(nBz), *dSig = ws.take(nBz), *dRx = ws.take(nBz),
+         *dRc = ws.take(nBc), *dSx = ws.take(nBz), *dSc = ws.take(nBc);
   // ---- derivatives at (x, mu): callbacks on the device, the small vectors come to the host
-  if ((rc = dto_eval_jac_g_batch(h, b, dJ, nnzJ))) return rc;
-  if ((rc = dto_eval_g_batch(h, b, dC, Nc))) return rc;
-  if ((rc = dto_eval_grad_f_batch(h, b, dG, Nz))) return rc;
-  std::vector<double> J((size_t)B * nnzJ), c((size_t)B * Nc), g((size_t)B * Nz), m((size_t)B * Nc);
+#define DRC(expr) do { rc = (expr); if (rc) return rc; } while (0)
+  DRC(border_eval_point(h, b, dJ, nnzJ, dC, Nc, dG, Nz));
+  std::vector<double> J((size_t)B * nnzJ), c(nBc), g(nBz), m(nBc);
   HIP_TRY(hipMemcpyAsync(J.data(), dJ, J.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(c.data(), dC, c.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(g.data(), dG, g.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpy2DAsync(m.data(), Nc * sizeof(double), mu, ldmu * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   // r_x = grad f + J' mu (all rows, general ones included); the general rows of J as dense vectors
-  std::vector<double> rx((size_t)B * Nz), Grow((size_t)ng * B * Nz, 0.0);
+  std::vector<double> rx(nBz), Grow((size_t)ng * nBz, 0.0);
   for (int64_t i = 0; i < B; ++i) {
     double* r = &rx[(size_t)i * Nz];
     for (int64_t k = 0; k < Nz; ++k) r[k] = g[(size_t)i * Nz + k];
@@ -2489,7 +2324,7 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
     }
   }
   // ---- stage part: assemble, factor (per-instance delta_w through the sigma_x diagonal), solve for the 1 + n_g right-hand sides
-  std::vector<double> sig((size_t)B * Nz);
+  std::vector<double> sig(nBz);
   for (int64_t i = 0; i < B; ++i)
     for (int64_t k = 0; k < Nz; ++k)   // pin_fixed: a variable with lo == hi keeps its value (a huge diagonal entry: its step is ~1e-16 r)
       sig[(size_t)i * Nz + k] = (pin_fixed && L.var_lo[(size_t)k] == L.var_hi[(size_t)k]) ? 1e16 : dw[i];
@@ -2497,32 +2332,27 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
   dto_kkt_system sys;
   sys.mu = mu; sys.ldmu = ldmu; sys.sigma_x = dSig; sys.ldsx = Nz; sys.sigma_c = nullptr; sys.ldsc = 0;
   sys.delta_w = 0.0; sys.delta_c = delta_c;
-  if ((rc = dto_kkt_assemble(h, b, &sys))) return rc;
+  DRC(dto_kkt_assemble(h, b, &sys));
   std::vector<int32_t> iok((size_t)B, 1);
-  if ((rc = dto_kkt_factor(h, iok.data(), nullptr, (void*)st))) return rc;
-  std::vector<double> rhsx((size_t)B * Nz), rhsc((size_t)B * Nc, 0.0), solx((size_t)B * Nz), solc((size_t)B * Nc);
-  std::vector<double> Yx((size_t)ng * B * Nz), Yc((size_t)ng * B * Nc);
+  DRC(dto_kkt_factor(h, iok.data(), nullptr, (void*)st));
+  std::vector<double> rhsx(nBz), rhsc(nBc, 0.0), solx(nBz), solc(nBc), Yx((size_t)ng * nBz), Yc((size_t)ng * nBc);
   auto solve = [&](const double* hx, const double* hc, double* ox, double* oc) -> int {
-    HIP_TRY(hipMemcpyAsync(dRx, hx, (size_t)B * Nz * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dRc, hc, (size_t)B * Nc * sizeof(double), hipMemcpyHostToDevice, st));
-    int r = dto_kkt_solve(h, dRx, Nz, dRc, Nc, dSx, Nz, dSc, Nc, (void*)st);
-    if (r) return r;
-    HIP_TRY(hipMemcpyAsync(ox, dSx, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(oc, dSc, (size_t)B * Nc * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(dRx, hx, nBz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dRc, hc, nBc * sizeof(double), hipMemcpyHostToDevice, st));
+    DRC(dto_kkt_solve(h, dRx, Nz, dRc, Nc, dSx, Nz, dSc, Nc, (void*)st));
+    HIP_TRY(hipMemcpyAsync(ox, dSx, nBz * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(oc, dSc, nBc * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return DTO_OK;
   };
   for (size_t k = 0; k < rhsx.size(); ++k) rhsx[k] = -rx[k];
   for (int64_t i = 0; i < B; ++i)
     for (int64_t k = 0; k < Ns; ++k) rhsc[(size_t)i * Nc + k] = -c[(size_t)i * Nc + k];
-  if ((rc = solve(rhsx.data(), rhsc.data(), solx.data(), solc.data()))) return rc;
-  std::vector<double> zero_c((size_t)B * Nc, 0.0);
-  for (int64_t j = 0; j < ng; ++j)
-    if ((rc = solve(&Grow[(size_t)j * B * Nz], zero_c.data(), &Yx[(size_t)j * B * Nz], &Yc[(size_t)j * B * Nc]))) return rc;
-  // ---- border: S drho = r_g - G v0_x per instance (dense n_g x n_g, Gaussian elimination with partial pivoting); S must be
-  //      negative definite for the inertia of the bordered matrix to be (Nz, Nc)
-  std::vector<double> hdx((size_t)B * Nz), hdm((size_t)B * Nc);
-  std::vector<double> Sm((size_t)ng * ng), rg((size_t)ng), Lc((size_t)ng * ng);
+  DRC(solve(rhsx.data(), rhsc.data(), solx.data(), solc.data()));
+  std::vector<double> zero_c(nBc, 0.0);
+  for (int64_t j = 0; j < ng; ++j) DRC(solve(&Grow[(size_t)j * nBz], zero_c.data(), &Yx[(size_t)j * nBz], &Yc[(size_t)j * nBc]));
+  // ---- border: S = -(G Y_x + dc I), S drho = r_g - G v0_x per instance; v = v0 - Y drho, the general rows' multipliers are drho
+  std::vector<double> hdx(nBz), hdm(nBc), Sm((size_t)ng * ng), rg((size_t)ng), Lc((size_t)ng * ng);
   for (int64_t i = 0; i < B; ++i) {
     auto gdot = [&](int64_t row, const double* v) {
       const double* gr = &Grow[((size_t)row * B + i) * Nz];
@@ -2534,46 +2364,19 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
       for (int64_t q = 0; q < ng; ++q) Sm[(size_t)a * ng + q] = -gdot(a, &Yx[((size_t)q * B + i) * Nz]) - (a == q ? delta_c : 0.0);
       rg[(size_t)a] = -c[(size_t)i * Nc + Ns + a] - gdot(a, &solx[(size_t)i * Nz]);
     }
-    // negative definiteness: Cholesky of -S (symmetrised)
-    bool negdef = true;
-    for (int64_t a = 0; a < ng && negdef; ++a)
-      for (int64_t q = 0; q <= a; ++q) {
-        double acc = -0.5 * (Sm[(size_t)a * ng + q] + Sm[(size_t)q * ng + a]);
-        for (int64_t k = 0; k < q; ++k) acc -= Lc[(size_t)a * ng + k] * Lc[(size_t)q * ng + k];
-        if (a == q) { if (!(acc > 0.0)) { negdef = false; break; } Lc[(size_t)a * ng + a] = std::sqrt(acc); }
-        else Lc[(size_t)a * ng + q] = acc / Lc[(size_t)q * ng + q];
-      }
-    // solve S drho = rg
-    std::vector<double> A(Sm), x(rg);
-    for (int64_t k = 0; k < ng; ++k) {
-      int64_t piv = k;
-      for (int64_t r = k + 1; r < ng; ++r) if (std::fabs(A[(size_t)r * ng + k]) > std::fabs(A[(size_t)piv * ng + k])) piv = r;
-      if (piv != k) { for (int64_t q = 0; q < ng; ++q) std::swap(A[(size_t)k * ng + q], A[(size_t)piv * ng + q]); std::swap(x[(size_t)k], x[(size_t)piv]); }
-      const double d = A[(size_t)k * ng + k];
-      if (d == 0.0) { negdef = false; continue; }
-      for (int64_t r = k + 1; r < ng; ++r) {
-        const double f = A[(size_t)r * ng + k] / d;
-        for (int64_t q = k; q < ng; ++q) A[(size_t)r * ng + q] -= f * A[(size_t)k * ng + q];
-        x[(size_t)r] -= f * x[(size_t)k];
-      }
-    }
-    for (int64_t k = ng - 1; k >= 0; --k) {
-      double acc = x[(size_t)k];
-      for (int64_t q = k + 1; q < ng; ++q) acc -= A[(size_t)k * ng + q] * x[(size_t)q];
-      x[(size_t)k] = A[(size_t)k * ng + k] != 0.0 ? acc / A[(size_t)k * ng + k] : 0.0;
-    }
+    const bool negdef = border_schur_solve((int)ng, Sm.data(), rg.data(), Lc.data());
     if (ok_out) ok_out[i] = (iok[(size_t)i] != 0 && negdef) ? 1 : 0;
     for (int64_t k = 0; k < Nz; ++k) {
       double v = solx[(size_t)i * Nz + k];
-      for (int64_t q = 0; q < ng; ++q) v -= Yx[((size_t)q * B + i) * Nz + k] * x[(size_t)q];
+      for (int64_t q = 0; q < ng; ++q) v -= Yx[((size_t)q * B + i) * Nz + k] * rg[(size_t)q];
       hdx[(size_t)i * Nz + k] = v;
     }
     for (int64_t k = 0; k < Ns; ++k) {
       double v = solc[(size_t)i * Nc + k];
-      for (int64_t q = 0; q < ng; ++q) v -= Yc[((size_t)q * B + i) * Nc + k] * x[(size_t)q];
+      for (int64_t q = 0; q < ng; ++q) v -= Yc[((size_t)q * B + i) * Nc + k] * rg[(size_t)q];
       hdm[(size_t)i * Nc + k] = v;
     }
-    for (int64_t q = 0; q < ng; ++q) hdm[(size_t)i * Nc + Ns + q] = x[(size_t)q];
+    for (int64_t q = 0; q < ng; ++q) hdm[(size_t)i * Nc + Ns + q] = rg[(size_t)q];
   }
   HIP_TRY(hipMemcpy2DAsync(dx, lddx * sizeof(double), hdx.data(), Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpy2DAsync(dmu, lddmu * sizeof(double), hdm.data(), Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
@@ -2581,8 +2384,26 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
   if (stats) {
     stats->grad.swap(g); stats->c.swap(c); stats->rx.swap(rx); stats->dz.swap(hdx); stats->dmu.swap(hdm);
   }
+#undef DRC
   return DTO_OK;
 }
+
+// ---- the linear solver of general_solve_batch and of dto_kkt_step_batch with general rows: tile path, lane path with the border
+//      algebra on the device, or on the host
+static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64_t ldmu, const double* dw, double delta_c,
+                         double* dx, int64_t lddx, double* dmu, int64_t lddmu, int* ok_out, BorderStats* stats, bool pin_fixed,
+                         const double* gdiag, const double* gshift, const BorderBar* barp, const BorderSlack* slk) {
+  if (p->vt->launch_wide)   // (no stage rows on the tile path: slk is NULL)
+    return bordered_step_tile(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp);
+  const char* e = getenv("DTO_BORDER_HOST");
+  if (!(e && atoi(e) != 0) && p->L.Ngen <= BORDER_MAX_NG)
+    return bordered_step_device(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed, gdiag, gshift, barp, slk);
+  if (slk) return set_error(DTO_ERR_UNSUPPORTED, "inequality stage rows beside GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
+  if (barp) return set_error(DTO_ERR_UNSUPPORTED, "variable bounds beside GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
+  if (gdiag) return set_error(DTO_ERR_UNSUPPORTED, "inequality GeneralConstraint rows need the device border (DTO_BORDER_HOST unset, at most 16 general rows)");
+  return bordered_step_host(p, b, mu, ldmu, dw, delta_c, dx, lddx, dmu, lddmu, ok_out, stats, pin_fixed);
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Solve for models with multi-knot GeneralConstraint rows: the filter line-search SQP iteration of the other paths, driven
@@ -2610,450 +2431,583 @@ static __global__ __launch_bounds__(64) void k_rows_abs_sum(const double* rows, 
   if (threadIdx.x == 0) out[b] = acc;
 }
 
-static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
-                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs) {
+// The state of one general_solve_batch call: device buffers (DevBufs: released on every return), their host mirrors, the
+// per-instance globalisation records, the row classification with the flags that follow from it, and the optional parts (barrier
+// terms of bounds, slacks of stage rows, secant pairs).  The phases below are the loop in order, as A - E are wide_outer's; the
+// differences from that loop that are kept on purpose ("Host-driven loops") are marked (difference n) where they live.
+struct BorderLoop {
+  Problem* p = nullptr;
+  dto_problem* h = nullptr;
+  hipStream_t st = nullptr;
+  dto_options user{};
+  dto_solver_opts o{};
+  dto_batch bz{};                      // the caller's batch with x = z (params / ldp stay the caller's: the point, the trials, the slack
+                                       // initialisation and bordered_step)
+  int64_t B = 0, Nz = 0, Nc = 0, ng = 0, Ns = 0;
+  // rows and bounds: ineq [ng] marks the inequality general rows (ni of them), smask [Ns] the inequality stage rows (nsi; empty
+  // without one), n_bound counts the finite bound sides of the variables that are not fixed
+  std::vector<char> ineq;
+  std::vector<int> smask;
+  int64_t ni = 0, nsi = 0, n_bound = 0;
+  bool bounds = false, bounds_or_slk = false, barrier = false;   // n_bound > 0; that or nsi > 0; that or ni > 0: one mu per instance
+  bool lbfgs = false, timed_out = false;
+  int nth = 1;                         // numbers per instance of a trial point (k_rows_abs_sum / k_border_trial)
+  std::chrono::steady_clock::time_point t_start;
+  DevBuf<double> z, lam, dz, dlam, zt, df, dc, dal, dth;
+  DevBuf<double> dgd, dgs, dst;        // [B][ng]: s / nu, mu / nu, trial slacks of the general rows
+  DevBuf<double> d5;                   // [B][5] statistics of the point and the step; with bounds [B][BORDER_BAR_NSTAT] behind them,
+                                       // with inequality stage rows [B][BORDER_SLK_NSTAT] behind those
+  DevBuf<double> zl, zu, dlo, dhi, dmub, dad;   // finite bounds only: multipliers [B][Nz], shared bounds [Nz]; mu and alpha_d [B]: those
+                                                // and inequality stage rows
+  DevBuf<double> ss, sds;                       // inequality stage rows only: slacks and their step [B][Ns]
+  DevBuf<int> dsmask;                           //   and the 0/1 mask of those rows [Ns]
+  BorderBar bar;
+  BorderSlack slk;
+  QnHistory qn;                        // (allocated in the limited-memory mode only)
+  BorderStats bs;                      // what the step of this iteration left
+  std::vector<GlobInst> I;             // (mu: finite bounds, inequality general rows and inequality stage rows share one per instance)
+  std::vector<double> hz, hmu, had;    // (hz: the start point without bounds, staged here so that its upload needs no wait)
+  // slacks and multipliers of the general rows on the host (the multipliers are mirrored into lam after every update), the slack
+  // steps, s / nu, mu / nu and the trial slacks
+  std::vector<double> hs, hnu, hds, hgd, hgs, hst;
+  std::vector<double> dwv, hf, hth, hal, hphi0, hst5, hdnu, th0, gphid, chosen_a, apmax, admax;
+  std::vector<int> okv;
+  std::vector<char> mu_moved, ftype_a;
+  std::vector<MostFeasible> best_a;
+  // hst5, the host copy of d5: the block of instance i behind the [B][5]
+  const double* bound_stats(int64_t i) const { return bounds ? &hst5[(size_t)B * 5 + (size_t)i * BORDER_BAR_NSTAT] : nullptr; }
+  const double* slack_stats(int64_t i) const {
+    return nsi > 0 ? &hst5[(size_t)B * 5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0) + (size_t)i * BORDER_SLK_NSTAT] : nullptr;
+  }
+  bool running(int64_t i) const { return I[(size_t)i].status == 0; }
+  int put_nu() {   // host multipliers of the general rows -> their columns of lam
+    HIP_TRY(hipMemcpy2DAsync(lam + Ns, Nc * sizeof(double), hnu.data(), ng * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
+    return DTO_OK;
+  }
+};
+
+// ---- begin: argument checks, row classification, allocation, the start point (pushed inside finite bounds, fixed variables on
+//      their values), slacks and multipliers of the inequality rows (s = max(-c, 1e-2), nu = 1, mu_init)
+static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, const dto_batch* b, int64_t ldxo, bool want_mu, int64_t ldmuo,
+                             bool lbfgs) {
   int rc = p->ensure_device();
   if (rc) return rc;
   const Layout& L = p->L;
   const int64_t B = b->B, Nz = L.Nz, Nc = L.Nc;
   // lbfgs: the limited-memory mode of the tile path (12 border rows are the compact matrix, up to four general rows share its panel).
-  // Everything below is the loop as it stands; the step (bordered_step_tile) and the secant pairs after it are what differ
+  // The loop is the same; the step (bordered_step_tile) and the secant pairs after it (border_loop_save_pair) are what differ
   if (lbfgs && (!p->vt->launch_wide || 2 * QnHistory::M + L.Ngen > KB_MAX))
     return set_error(DTO_ERR_UNSUPPORTED, "limited-memory bordered loop: tile path with at most four GeneralConstraint rows");
   if (lbfgs && b->B < 1) return set_error(DTO_ERR_INVALID, "empty batch");
-  if (lbfgs && (b->ldx < Nz || ldxo < Nz || (mu_out && ldmuo < Nc))) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (lbfgs && (b->ldx < Nz || ldxo < Nz || (want_mu && ldmuo < Nc))) return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if (lbfgs && L.Nstage != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows, GeneralConstraint rows and bounds only");
   // per-instance parameters (dto_batch.params, [B][ldp]): every callback of this loop and both linear solvers read the instance's own
   // (dto_kkt_assemble / wide_kkt_assemble take them from the batch at every call, a further delta_w attempt at the same point included)
   if (b->params && L.Nw > 0 && b->ldp < L.Nw) return set_error(DTO_ERR_INVALID, "ldp < num_parameters");
   // finite bound sides of the variables that are not fixed (the tests of k_wide_init_bounds: a side is finite inside +-1e300)
-  int64_t n_bound = 0;
   for (int64_t i = 0; i < Nz; ++i)
-    if (L.var_lo[i] != L.var_hi[i]) n_bound += (L.var_lo[i] > -1e300 ? 1 : 0) + (L.var_hi[i] < 1e300 ? 1 : 0);
-  const bool bounds = n_bound > 0;
+    if (L.var_lo[i] != L.var_hi[i]) G.n_bound += (L.var_lo[i] > -1e300 ? 1 : 0) + (L.var_hi[i] < 1e300 ? 1 : 0);
   // inequality rows (c <= 0: src/general_constraint.jl:15-19 `indices_inequality`) among the GENERAL rows are carried with slacks
   // g_i + s_i = 0, s_i >= 0 (round 4): the border's diagonal gets s_i / nu_i, its right-hand side mu / nu_i.  Inequality rows of
   // stage Constraints get the same elimination with their slacks on the device (BorderSlack: about T of them per instance), s / nu
   // through dto_kkt_system.sigma_c; dynamics rows are equalities
   const int64_t ng = L.Ngen, Ns = Nc - ng;
-  std::vector<char> ineq((size_t)std::max<int64_t>(1, ng), 0);
-  std::vector<int> smask;
-  int64_t ni = 0, nsi = 0;
+  G.ineq.assign((size_t)std::max<int64_t>(1, ng), 0);
   for (int64_t i = 0; i < Nc; ++i) {
     if (L.con_lo[i] == L.con_hi[i]) continue;
     if (i < L.Ndyn || !(L.con_hi[i] == 0.0) || std::isfinite(L.con_lo[i]))
       return set_error(DTO_ERR_UNSUPPORTED, "GeneralConstraint solve path: equality rows and inequality rows c <= 0");
     if (i < Ns) {
-      if (smask.empty()) smask.assign((size_t)Ns, 0);
-      smask[(size_t)i] = 1; ++nsi;
+      if (G.smask.empty()) G.smask.assign((size_t)Ns, 0);
+      G.smask[(size_t)i] = 1; ++G.nsi;
     } else {
-      ineq[(size_t)(i - Ns)] = 1; ++ni;
+      G.ineq[(size_t)(i - Ns)] = 1; ++G.ni;
     }
   }
-  dto_options u;
-  if (opt) u = *opt; else dto_options_default(&u);
-  dto_solver_opts o;
-  default_opts(o, u);
-  hipStream_t st = (hipStream_t)b->stream;
-  dto_problem* h = reinterpret_cast<dto_problem*>(p);
-  // the temporaries of this call: released on every return
-  DevBuf<double> z, lam, dz, dlam, zt, df, dc, dal, dth;
-  DevBuf<double> dgd, dgs, dst, dnu;   // [B][ng]: s / nu, mu / nu, trial slacks, multipliers of the general rows
-  DevBuf<double> d5;                   // [B][5] statistics of the point and the step; with bounds [B][BORDER_BAR_NSTAT] behind them
-  DevBuf<double> zl, zu, dlo, dhi, dmub, dad;   // finite bounds only: multipliers [B][Nz], shared bounds [Nz]; mu and alpha_d [B]: those
-                                                // and inequality stage rows
-  DevBuf<double> ss, sds;                       // inequality stage rows only: slacks and their step [B][Ns]
-  DevBuf<int> dsmask;                           //   and the 0/1 mask of those rows [Ns]
-  const bool bounds_or_slk = bounds || nsi > 0;
-  const int nth = nsi > 0 ? 3 : (bounds ? 2 : 1);   // numbers per instance of a trial point (k_rows_abs_sum / k_border_trial)
-  HIP_TRY(z.alloc((size_t)B * Nz));
-  HIP_TRY(lam.alloc((size_t)B * Nc));
-  HIP_TRY(dz.alloc((size_t)B * Nz));
-  HIP_TRY(dlam.alloc((size_t)B * Nc));
-  HIP_TRY(zt.alloc((size_t)B * Nz));
-  HIP_TRY(df.alloc((size_t)B));
-  HIP_TRY(dc.alloc((size_t)B * Nc));
-  HIP_TRY(dal.alloc((size_t)B));
-  HIP_TRY(dth.alloc((size_t)B * nth));   // (with bounds: theta and sum log(gap) of a trial point; with stage slacks sum log(s) behind)
+  const int64_t ni = G.ni, nsi = G.nsi;
+  const bool bounds = G.bounds = G.n_bound > 0;
+  G.bounds_or_slk = bounds || nsi > 0;
+  G.barrier = bounds || ni > 0 || nsi > 0;
+  G.nth = nsi > 0 ? 3 : (bounds ? 2 : 1);
+  G.lbfgs = lbfgs;
+  G.p = p; G.h = reinterpret_cast<dto_problem*>(p); G.st = (hipStream_t)b->stream;
+  G.B = B; G.Nz = Nz; G.Nc = Nc; G.ng = ng; G.Ns = Ns;
+  if (opt) G.user = *opt; else dto_options_default(&G.user);
+  default_opts(G.o, G.user);
+  const dto_solver_opts& o = G.o;
+  hipStream_t st = G.st;
+  HIP_TRY(G.z.alloc((size_t)B * Nz));
+  HIP_TRY(G.lam.alloc((size_t)B * Nc));
+  HIP_TRY(G.dz.alloc((size_t)B * Nz));
+  HIP_TRY(G.dlam.alloc((size_t)B * Nc));
+  HIP_TRY(G.zt.alloc((size_t)B * Nz));
+  HIP_TRY(G.df.alloc((size_t)B));
+  HIP_TRY(G.dc.alloc((size_t)B * Nc));
+  HIP_TRY(G.dal.alloc((size_t)B));
+  HIP_TRY(G.dth.alloc((size_t)B * G.nth));   // (with bounds: theta and sum log(gap) of a trial point; with stage slacks sum log(s) behind)
   if (ni > 0) {
-    for (DevBuf<double>* q : {&dgd, &dgs, &dst, &dnu}) HIP_TRY(q->alloc((size_t)B * ng));
+    for (DevBuf<double>* q : {&G.dgd, &G.dgs, &G.dst}) HIP_TRY(q->alloc((size_t)B * ng));
   }
-  if (bounds_or_slk) {
-    HIP_TRY(dmub.alloc((size_t)B));
-    HIP_TRY(dad.alloc((size_t)B));
+  if (G.bounds_or_slk) {
+    HIP_TRY(G.dmub.alloc((size_t)B));
+    HIP_TRY(G.dad.alloc((size_t)B));
   }
-  BorderBar bar;
-  BorderSlack slk;
-  std::vector<double> hz;
   if (bounds) {
     // the guess pushed inside the bounds, fixed variables on their values, z_L / z_U on the central path of mu_init: the cold
     // start of the tile solver, instance-major over [B][Nz] with the problem's shared bounds (ldb = 0)
-    HIP_TRY(zl.alloc((size_t)B * Nz));
-    HIP_TRY(zu.alloc((size_t)B * Nz));
-    HIP_TRY(dlo.alloc((size_t)Nz));
-    HIP_TRY(dhi.alloc((size_t)Nz));
-    HIP_TRY(hipMemcpyAsync(dlo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dhi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpy2DAsync(z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (double*)z, (double*)zl, (double*)zu,
-                       (const double*)dlo, (const double*)dhi, (int64_t)0, o.mu_init, o.bound_push, o.bound_frac, Nz);
+    HIP_TRY(G.zl.alloc((size_t)B * Nz));
+    HIP_TRY(G.zu.alloc((size_t)B * Nz));
+    HIP_TRY(G.dlo.alloc((size_t)Nz));
+    HIP_TRY(G.dhi.alloc((size_t)Nz));
+    HIP_TRY(hipMemcpyAsync(G.dlo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(G.dhi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(G.z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (double*)G.z, (double*)G.zl, (double*)G.zu,
+                       (const double*)G.dlo, (const double*)G.dhi, (int64_t)0, o.mu_init, o.bound_push, o.bound_frac, Nz);
     HIP_TRY(hipGetLastError());
-    bar.z = z; bar.zl = zl; bar.zu = zu; bar.lo = dlo; bar.hi = dhi; bar.mu = dmub;
+    G.bar.z = G.z; G.bar.zl = G.zl; G.bar.zu = G.zu; G.bar.lo = G.dlo; G.bar.hi = G.dhi; G.bar.mu = G.dmub;
   } else {
     // the guess, with the fixed variables put on their values
+    std::vector<double>& hz = G.hz;
     hz.resize((size_t)B * Nz);
     HIP_TRY(hipMemcpy2DAsync(hz.data(), Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < B; ++i)
       for (int64_t k = 0; k < Nz; ++k)
         if (L.var_lo[k] == L.var_hi[k]) hz[(size_t)i * Nz + k] = L.var_lo[k];
-    HIP_TRY(hipMemcpyAsync(z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(G.z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  HIP_TRY(hipMemsetAsync(lam, 0, (size_t)B * Nc * sizeof(double), st));
-  QnHistory qn;   // (allocated in the limited-memory mode only; released on every return)
+  HIP_TRY(hipMemsetAsync(G.lam, 0, (size_t)B * Nc * sizeof(double), st));
   if (lbfgs) {
     if ((rc = ensure_border_csc(p))) return rc;
-    if ((rc = qn.init(B, Nz, st))) return rc;
+    if ((rc = G.qn.init(B, Nz, st))) return rc;
   }
-  using Inst = GlobInst;   // (mu: finite bounds, inequality general rows and inequality stage rows share one per instance)
-  std::vector<Inst> I((size_t)B);
-  const bool barrier = bounds || ni > 0 || nsi > 0;
-  if (barrier)
-    for (int64_t i = 0; i < B; ++i) I[(size_t)i].mu = o.mu_init;
-  std::vector<double> hmu((size_t)(bounds_or_slk ? B : 0)), had((size_t)(bounds_or_slk ? B : 0));
-  // slacks and multipliers of the general rows on the host (the multipliers are mirrored into lam after every update)
-  std::vector<double> hs((size_t)B * std::max<int64_t>(1, ng), 0.0), hnu((size_t)B * std::max<int64_t>(1, ng), 0.0), hds((size_t)B * std::max<int64_t>(1, ng), 0.0);
-  std::vector<double> hgd((size_t)B * std::max<int64_t>(1, ng), 0.0), hgs((size_t)B * std::max<int64_t>(1, ng), 0.0), hst((size_t)B * std::max<int64_t>(1, ng), 0.0);
-  std::vector<double> dwv((size_t)B), hf((size_t)B), hth((size_t)B * nth), hal((size_t)B), hphi0((size_t)B);
-  std::vector<int> okv((size_t)B);
-  constexpr int TRIALS = DTO_LS_TRIALS;
-  dto_batch bz = *b;
-  bz.x = z; bz.ldx = Nz;   // (params / ldp stay the caller's: the point, the trials, the slack initialisation and bordered_step)
-  auto put_nu = [&]() -> int {   // host multipliers of the general rows -> their columns of lam
-    HIP_TRY(hipMemcpy2DAsync(lam + Ns, Nc * sizeof(double), hnu.data(), ng * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyHostToDevice, st));
-    return DTO_OK;
-  };
+  G.I.assign((size_t)B, GlobInst());
+  if (G.barrier)
+    for (int64_t i = 0; i < B; ++i) G.I[(size_t)i].mu = o.mu_init;
+  const size_t nBg = (size_t)B * std::max<int64_t>(1, ng);
+  G.hmu.assign((size_t)(G.bounds_or_slk ? B : 0), 0.0); G.had = G.hmu;
+  for (std::vector<double>* v : {&G.hs, &G.hnu, &G.hds, &G.hgd, &G.hgs, &G.hst}) v->assign(nBg, 0.0);
+  for (std::vector<double>* v : {&G.dwv, &G.hf, &G.hal, &G.hphi0}) v->assign((size_t)B, 0.0);
+  G.hth.assign((size_t)B * G.nth, 0.0);
+  G.okv.assign((size_t)B, 0);
+  G.mu_moved.assign((size_t)B, 0);
+  G.bz = *b;
+  G.bz.x = G.z; G.bz.ldx = Nz;
   if (nsi > 0) {
     // the same start for the slacks of the inequality stage rows, on the device: s = max(-c, 1e-2), nu = 1 in their entries of lam
-    HIP_TRY(ss.alloc((size_t)B * Ns));
-    HIP_TRY(sds.alloc((size_t)B * Ns));
-    HIP_TRY(dsmask.alloc((size_t)Ns));
-    HIP_TRY(hipMemcpyAsync(dsmask, smask.data(), (size_t)Ns * sizeof(int), hipMemcpyHostToDevice, st));
-    slk.s = ss; slk.ds = sds; slk.mask = dsmask; slk.mu = dmub; slk.Ns = Ns;
-    if ((rc = dto_eval_g_batch(h, &bz, dc, Nc))) return rc;
-    hipLaunchKernelGGL(k_border_slack_init, dim3((unsigned)(((size_t)B * Ns + 255) / 256)), dim3(256), 0, st, B, Nc, slk, (const double*)dc,
-                       (double*)lam);
+    HIP_TRY(G.ss.alloc((size_t)B * Ns));
+    HIP_TRY(G.sds.alloc((size_t)B * Ns));
+    HIP_TRY(G.dsmask.alloc((size_t)Ns));
+    HIP_TRY(hipMemcpyAsync(G.dsmask, G.smask.data(), (size_t)Ns * sizeof(int), hipMemcpyHostToDevice, st));
+    G.slk.s = G.ss; G.slk.ds = G.sds; G.slk.mask = G.dsmask; G.slk.mu = G.dmub; G.slk.Ns = Ns;
+    if ((rc = dto_eval_g_batch(G.h, &G.bz, G.dc, Nc))) return rc;
+    hipLaunchKernelGGL(k_border_slack_init, dim3((unsigned)(((size_t)B * Ns + 255) / 256)), dim3(256), 0, st, B, Nc, G.slk, (const double*)G.dc,
+                       (double*)G.lam);
     HIP_TRY(hipGetLastError());
   }
   if (ni > 0) {
     // slacks from the constraint values at the guess, pushed inside (s >= 1e-2), multipliers 1 (Ipopt's bound_mult_init_val), mu_init
-    if ((rc = dto_eval_g_batch(h, &bz, dc, Nc))) return rc;
+    if ((rc = dto_eval_g_batch(G.h, &G.bz, G.dc, Nc))) return rc;
     std::vector<double> hg((size_t)B * ng);
-    HIP_TRY(hipMemcpy2DAsync(hg.data(), ng * sizeof(double), dc + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpy2DAsync(hg.data(), ng * sizeof(double), G.dc + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    for (int64_t i = 0; i < B; ++i) {
-      I[(size_t)i].mu = o.mu_init;
+    for (int64_t i = 0; i < B; ++i)
       for (int64_t q = 0; q < ng; ++q)
-        if (ineq[(size_t)q]) { hs[(size_t)(i * ng + q)] = std::max(-hg[(size_t)(i * ng + q)], 1e-2); hnu[(size_t)(i * ng + q)] = 1.0; }
-    }
-    if ((rc = put_nu())) return rc;
+        if (G.ineq[(size_t)q]) { G.hs[(size_t)(i * ng + q)] = std::max(-hg[(size_t)(i * ng + q)], 1e-2); G.hnu[(size_t)(i * ng + q)] = 1.0; }
+    if ((rc = G.put_nu())) return rc;
   }
-  const double kappa_sigma = 1e10;
-  std::vector<char> mu_moved((size_t)B, 0);
-  const auto t_start = std::chrono::steady_clock::now();
-  bool timed_out = false;
-  for (;;) {
-    if (ni > 0) {
+  G.t_start = std::chrono::steady_clock::now();
+  return DTO_OK;
+}
+
+// ---- the step at the current point: what it needs of the host state (s / nu and mu / nu of the inequality general rows, the
+//      barrier parameter), then the delta_w ladder per instance (Algorithm IC) around bordered_step -- all instances share the
+//      sweeps, a further attempt keeps the point's derivatives.  (difference 3) the first delta_w is 0 unless the last line search
+//      failed: no decay of the last value, no Gauss-Newton fallback
+static int border_loop_step(BorderLoop& G) {
+  const int64_t B = G.B, ng = G.ng;
+  const dto_solver_opts& o = G.o;
+  hipStream_t st = G.st;
+  if (G.ni > 0) {
+    for (int64_t i = 0; i < B; ++i)
+      for (int64_t q = 0; q < ng; ++q) {
+        const size_t e = (size_t)(i * ng + q);
+        G.hgd[e] = G.ineq[(size_t)q] ? G.hs[e] / G.hnu[e] : 0.0;
+        G.hgs[e] = G.ineq[(size_t)q] ? G.I[(size_t)i].mu / G.hnu[e] : 0.0;
+      }
+    HIP_TRY(hipMemcpyAsync(G.dgd, G.hgd.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(G.dgs, G.hgs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  if (G.bounds_or_slk) {   // the barrier parameter the step is computed with
+    for (int64_t i = 0; i < B; ++i) G.hmu[(size_t)i] = G.I[(size_t)i].mu;
+    HIP_TRY(hipMemcpyAsync(G.dmub, G.hmu.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  for (int64_t i = 0; i < B; ++i) G.dwv[(size_t)i] = G.I[(size_t)i].ls_fail ? ladder_after_ls_fail(o, G.I[(size_t)i].dlast) : 0.0;
+  G.bs = BorderStats();
+  G.bs.qn = G.lbfgs ? &G.qn : nullptr;
+  for (int attempt = 0;; ++attempt) {
+    G.bs.reuse_point = attempt > 0;
+    const int rc = bordered_step(G.p, &G.bz, G.lam, G.Nc, G.dwv.data(), o.delta_c, G.dz, G.Nz, G.dlam, G.Nc, G.okv.data(), &G.bs, true,
+                                 G.ni > 0 ? G.dgd : nullptr, G.ni > 0 ? G.dgs : nullptr, G.bounds ? &G.bar : nullptr, G.nsi > 0 ? &G.slk : nullptr);
+    if (rc) return rc;
+    bool again = false;
+    for (int64_t i = 0; i < B; ++i) {
+      if (!G.running(i) || G.okv[(size_t)i] || attempt >= o.max_refactor) continue;
+      G.dwv[(size_t)i] = ladder_next(o, G.dwv[(size_t)i], G.I[(size_t)i].dlast);
+      again = true;
+    }
+    if (!again) return DTO_OK;
+  }
+}
+
+// the host border's whole vectors (BorderStats grad, c, rx, dz, dmu; hm: the multipliers) reduced to what the device border delivers:
+// theta_1, theta_inf, dual infeasibility over the free variables, sum |lam|, grad f' dz per instance in hst5, the steps of the
+// general rows' multipliers in hdnu.  Sums run over k ascending, the slack of an inequality general row is added before the
+// absolute value
+static void border_loop_host_stats(BorderLoop& G, const std::vector<double>& hm) {
+  const Layout& L = G.p->L;
+  const int64_t Nz = G.Nz, Nc = G.Nc, ng = G.ng, Ns = G.Ns;
+  const BorderStats& bs = G.bs;
+  G.hst5.assign((size_t)G.B * 5, 0.0);
+  G.hdnu.resize((size_t)G.B * ng);
+  for (int64_t i = 0; i < G.B; ++i) {
+    for (int64_t q = 0; q < ng; ++q) G.hdnu[(size_t)(i * ng + q)] = bs.dmu[(size_t)i * Nc + Ns + q];
+    if (!G.running(i)) continue;
+    double th1 = 0, thinf = 0, dinf = 0, slam = 0, gd = 0;
+    for (int64_t k = 0; k < Nc; ++k) {
+      const double sk = (k >= Ns && G.ineq[(size_t)(k - Ns)]) ? G.hs[(size_t)(i * ng + (k - Ns))] : 0.0;   // inequality rows: g + s
+      const double v = std::fabs(bs.c[(size_t)i * Nc + k] + sk); th1 += v; thinf = std::max(thinf, v); slam += std::fabs(hm[(size_t)i * Nc + k]);
+    }
+    for (int64_t k = 0; k < Nz; ++k) {
+      if (L.var_lo[k] != L.var_hi[k]) dinf = std::max(dinf, std::fabs(bs.rx[(size_t)i * Nz + k]));
+      gd += bs.grad[(size_t)i * Nz + k] * bs.dz[(size_t)i * Nz + k];
+    }
+    double* q5 = &G.hst5[(size_t)i * 5];
+    q5[0] = th1; q5[1] = thinf; q5[2] = dinf; q5[3] = slam; q5[4] = gd;
+  }
+}
+
+// ---- what the host rules need of the point and the step, per instance: the objective (hf, and phi_0 of the line search), five
+//      numbers in hst5 -- behind them BORDER_BAR_NSTAT with bounds and BORDER_SLK_NSTAT with inequality stage rows, in the same
+//      buffer and the same copy (difference 6: the tile path has all of this from k_wide_step) -- and the steps of the general
+//      rows' multipliers (hdnu).  The device borders left grad f, c and r_x in the workspace (bs.d_*): three reductions, one copy;
+//      the host border left vectors: border_loop_host_stats
+static int border_loop_point_stats(BorderLoop& G) {
+  const int64_t B = G.B, Nz = G.Nz, Nc = G.Nc, ng = G.ng, Ns = G.Ns;
+  hipStream_t st = G.st;
+  const BorderStats& bs = G.bs;
+  const bool dev_stats = bs.d_grad != nullptr;
+  std::vector<double> hm;
+  if (dev_stats) {
+    const size_t n5 = (size_t)B * 5, nbar = n5 + (G.bounds ? (size_t)B * BORDER_BAR_NSTAT : 0),
+                 nstat = nbar + (G.nsi > 0 ? (size_t)B * BORDER_SLK_NSTAT : 0);
+    if (!G.d5) HIP_TRY(G.d5.alloc(nstat));
+    if (G.ni > 0) HIP_TRY(hipMemcpyAsync(G.dst, G.hs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));   // slack shift of theta
+    hipLaunchKernelGGL(k_border_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, Nc, bs.d_c, bs.d_rx, bs.d_grad, (const double*)G.dz, (const double*)G.lam,
+                       (const int*)G.p->d_var_fixed, (const double*)(G.ni > 0 ? G.dst : nullptr), Ns, ng, G.d5, (const double*)G.slk.s, G.slk.Ns);
+    if (G.bounds)
+      hipLaunchKernelGGL(k_border_bar_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, G.bar, (const double*)G.dz, bs.d_rx, (const int*)G.p->d_var_fixed,
+                         G.o.tau_min, G.d5 + n5);
+    if (G.nsi > 0)
+      hipLaunchKernelGGL(k_border_slack_stats, dim3((unsigned)B), dim3(64), 0, st, Nc, G.slk, (const double*)G.lam, (const double*)G.dlam, G.o.tau_min,
+                         G.d5 + nbar);
+    G.hst5.resize(nstat);
+    HIP_TRY(hipMemcpyAsync(G.hst5.data(), G.d5, G.hst5.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    G.hdnu.resize((size_t)B * ng);
+    if (ng > 0)
+      HIP_TRY(hipMemcpy2DAsync(G.hdnu.data(), ng * sizeof(double), G.dlam + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+  }
+  const int rc = dto_eval_f_batch(G.h, &G.bz, G.df);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(G.hf.data(), G.df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (!dev_stats) {
+    hm.resize((size_t)B * Nc);
+    HIP_TRY(hipMemcpyAsync(hm.data(), G.lam, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  if (!dev_stats) border_loop_host_stats(G, hm);
+  G.hphi0 = G.hf;   // objective at the current point: the line search's phi_0
+  return DTO_OK;
+}
+
+// ---- convergence test at the point the step was computed at (Ipopt's scaled error, reference Options) and monotone barrier
+//      update; host arithmetic only.  Fills th0 and gphid (theta_1 and the merit's directional derivative) for the line search and
+//      the slack steps hds of the inequality general rows; false when no instance is left running.
+//      (difference 1) no acceptable-level termination: terminal_status with acc_count = 0 never returns 4.
+//      (difference 4) dlast is recorded here, after the test, not when the factorisation is accepted; a step from a matrix whose
+//      inertia was never corrected sets ls_fail.
+//      (difference 5) an instance whose barrier parameter moved keeps the step of the old one unused: mu_moved gives it alpha = 0
+//      for this round (border_loop_step_limits) and the iteration is not counted (border_loop_trials)
+static bool border_loop_convergence(BorderLoop& G) {
+  const dto_solver_opts& o = G.o;
+  const int64_t B = G.B, ng = G.ng;
+  bool any = false;
+  G.th0.assign((size_t)B, 0.0); G.gphid.assign((size_t)B, 0.0);
+  for (int64_t i = 0; i < B; ++i) {
+    GlobInst& s = G.I[(size_t)i];
+    if (s.status != 0) continue;
+    const double* q5 = &G.hst5[(size_t)i * 5];
+    const double th1 = q5[0], thinf = q5[1], slam = q5[3], gd = q5[4];
+    double dinf = q5[2];
+    // complementarity of the slack / multiplier pairs against mu_target (termination; against mu: the barrier update below); the
+    // step of the inequality rows: ds = (mu - s nu) / nu - (s / nu) dnu, barrier term of the merit's directional derivative
+    double c0 = 0.0, snu = 0.0, bar_d = 0.0;
+    for (int64_t q = 0; q < ng; ++q) {
+      if (!G.ineq[(size_t)q]) continue;
+      const size_t e = (size_t)(i * ng + q);
+      const double sv = G.hs[e], nv = G.hnu[e], dnu = G.hdnu[e];
+      c0 = std::max(c0, std::fabs(sv * nv - o.mu_target)); snu += std::fabs(nv);
+      G.hds[e] = (s.mu - sv * nv) / nv - (sv / nv) * dnu;
+      bar_d += G.hds[e] / sv;
+    }
+    // finite variable bounds: the bound multipliers join the scaling, the largest and the smallest gap z give the complementarity
+    // error against any mu (as wide_convergence forms it), r_x already holds - z_L + z_U
+    const double* qb = G.bound_stats(i);
+    auto compl_bounds = [&](double mu_at) {
+      if (!qb) return 0.0;
+      const double szmin = qb[BORDER_BAR_ISZMAX] > 0.0 ? 1.0 / qb[BORDER_BAR_ISZMAX] : 1e300;
+      return std::max(qb[BORDER_BAR_SZMAX] - mu_at, mu_at - szmin);
+    };
+    if (qb) { dinf = qb[BORDER_BAR_DINF]; c0 = std::max(c0, compl_bounds(o.mu_target)); }
+    // inequality stage rows: the same two extremes of s nu from the device (nsi > 0 implies the device border), their ds / s in
+    // the merit's directional derivative exactly as the general rows' slacks
+    const double* qs = G.slack_stats(i);
+    auto compl_slack = [&](double mu_at) {
+      if (!qs) return 0.0;
+      const double snumin = qs[BORDER_SLK_ISNUMAX] > 0.0 ? 1.0 / qs[BORDER_SLK_ISNUMAX] : 1e300;
+      return std::max(qs[BORDER_SLK_SNUMAX] - mu_at, mu_at - snumin);
+    };
+    if (qs) { c0 = std::max(c0, compl_slack(o.mu_target)); snu += qs[BORDER_SLK_SUMNU]; bar_d += qs[BORDER_SLK_DSS]; }
+    // (the slack's bound multiplier of a slack-eliminated row IS its nu: it counts among the bound multipliers, as the slack
+    //  multipliers do in conv_body)
+    const ErrScale es = ipopt_scaling(o, slam, G.Nc, snu + (qb ? qb[BORDER_BAR_SUMZ] : 0.0), G.ni + G.n_bound + G.nsi);
+    const IterMeasures m{G.hf[(size_t)i], th1, thinf, dinf, std::max(std::max(dinf / es.sd, thinf), c0 / es.sc), c0};
+    G.mu_moved[(size_t)i] = 0;
+    s.status = terminal_status(o, s.iter, m, 0);
+    if (s.status == 0 && G.barrier) {
+      // Ipopt's monotone rule: once the barrier problem is solved to kappa_eps mu the parameter drops (and the filter is reset);
+      // the step computed above belongs to the old mu: this instance waits one round (alpha = 0) for the step of the new one
+      const double mu = monotone_mu(o, s.mu, std::max(dinf / es.sd, thinf), es.sc, [&](double mu_at) {
+        double c = std::max(compl_bounds(mu_at), compl_slack(mu_at));
+        for (int64_t q = 0; q < ng; ++q)
+          if (G.ineq[(size_t)q]) c = std::max(c, std::fabs(G.hs[(size_t)(i * ng + q)] * G.hnu[(size_t)(i * ng + q)] - mu_at));
+        return c;
+      });
+      if (mu != s.mu) { s.mu = mu; s.filter_n = 0; G.mu_moved[(size_t)i] = 1; }
+    }
+    init_theta_limits(s, th1);
+    G.th0[(size_t)i] = th1; G.gphid[(size_t)i] = gd - s.mu * bar_d;
+    if (qb) G.gphid[(size_t)i] += qb[BORDER_BAR_DPHI];
+    if (s.status == 0) {
+      any = true;
+      if (G.dwv[(size_t)i] > 0.0) s.dlast = G.dwv[(size_t)i]; else s.dlast = 0.0;
+      if (!G.okv[(size_t)i]) s.ls_fail = 1;
+    }
+  }
+  return any;
+}
+
+// ---- where the trials start: alpha_p^max and alpha_d^max, the fraction-to-the-boundary steps combined by min over the bounds and
+//      the slacks of inequality stage rows (from the device's statistics) and of inequality general rows (here), and phi_0, the
+//      barrier function f - mu (sum log(gap) + sum log s) at the point.  Without a barrier alpha^max = 1 and phi_0 = f
+static void border_loop_step_limits(BorderLoop& G) {
+  const int64_t B = G.B, ng = G.ng;
+  G.chosen_a.assign((size_t)B, -1.0);
+  G.ftype_a.assign((size_t)B, 0);
+  G.best_a.assign((size_t)B, MostFeasible());
+  G.apmax.assign((size_t)B, 1.0); G.admax.assign((size_t)B, 1.0);
+  for (int64_t i = 0; i < B && G.barrier; ++i) {
+    const GlobInst& s = G.I[(size_t)i];
+    if (s.status != 0) continue;
+    if (G.mu_moved[(size_t)i]) { G.chosen_a[(size_t)i] = 0.0; continue; }   // waits for the step of its new barrier parameter
+    double &ap = G.apmax[(size_t)i], &ad = G.admax[(size_t)i], &phi0 = G.hphi0[(size_t)i];
+    if (const double* qb = G.bound_stats(i)) {
+      ap = qb[BORDER_BAR_APMAX]; ad = qb[BORDER_BAR_ADMAX];
+      phi0 -= s.mu * qb[BORDER_BAR_LOGBAR];
+    }
+    if (const double* qs = G.slack_stats(i)) {   // the slacks of the inequality stage rows: the same three numbers
+      ap = std::min(ap, qs[BORDER_SLK_APMAX]); ad = std::min(ad, qs[BORDER_SLK_ADMAX]);
+      phi0 -= s.mu * qs[BORDER_SLK_LOGS];
+    }
+    if (G.ni == 0) continue;
+    const double tau = std::max(G.o.tau_min, 1.0 - s.mu);
+    double lb = 0.0;
+    for (int64_t q = 0; q < ng; ++q) {
+      if (!G.ineq[(size_t)q]) continue;
+      const size_t e = (size_t)(i * ng + q);
+      const double dnu = G.hdnu[e];
+      if (G.hds[e] < 0.0) ap = std::min(ap, -tau * G.hs[e] / G.hds[e]);
+      if (dnu < 0.0) ad = std::min(ad, -tau * G.hnu[e] / dnu);
+      lb += std::log(G.hs[e]);
+    }
+    phi0 -= s.mu * lb;
+  }
+}
+
+// ---- filter line search over alpha = alpha_p^max 2^-k: objective and l1 violation of a trial point from the callbacks (the
+//      violation summed on the device, with bounds or stage slacks the sums of logarithms in the same launch: difference 6, the
+//      tile path reads a merit table of all trials).  Trial k is evaluated only while some running instance has not accepted a
+//      shorter-numbered one (round 4: all eight trials of every iteration, each with its constraint vector over PCIe, were most of
+//      the 8.7 ms an iteration of a 512-instance batch took; a Newton step near the solution is accepted at alpha = 1).  Then the
+//      decision per instance: hal, the alpha it moves with.  (difference 2) ls_fail after an accepted trial is okv ? 0 : 1
+static int border_loop_trials(BorderLoop& G) {
+  constexpr int TRIALS = DTO_LS_TRIALS;
+  const int64_t B = G.B, Nz = G.Nz, Nc = G.Nc, ng = G.ng, Ns = G.Ns;
+  const int nth = G.nth;
+  hipStream_t st = G.st;
+  auto undecided = [&](int64_t i) { return G.running(i) && G.chosen_a[(size_t)i] < 0.0; };
+  for (int k = 0; k < TRIALS; ++k) {
+    bool some = false;
+    for (int64_t i = 0; i < B; ++i) some = some || undecided(i);
+    if (!some) break;
+    const double alpha2 = std::ldexp(1.0, -k);
+    for (int64_t i = 0; i < B; ++i) G.hal[(size_t)i] = undecided(i) ? G.apmax[(size_t)i] * alpha2 : 0.0;
+    if (G.ni > 0) {
       for (int64_t i = 0; i < B; ++i)
         for (int64_t q = 0; q < ng; ++q) {
           const size_t e = (size_t)(i * ng + q);
-          hgd[e] = ineq[(size_t)q] ? hs[e] / hnu[e] : 0.0;
-          hgs[e] = ineq[(size_t)q] ? I[(size_t)i].mu / hnu[e] : 0.0;
+          G.hst[e] = G.ineq[(size_t)q] ? G.hs[e] + G.hal[(size_t)i] * G.hds[e] : 0.0;
         }
-      HIP_TRY(hipMemcpyAsync(dgd, hgd.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(dgs, hgs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(G.dst, G.hst.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
     }
-    if (bounds_or_slk) {   // the barrier parameter the step is computed with
-      for (int64_t i = 0; i < B; ++i) hmu[(size_t)i] = I[(size_t)i].mu;
-      HIP_TRY(hipMemcpyAsync(dmub, hmu.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    // ---- step at the current point: delta_w ladder per instance (Algorithm IC), all instances share the sweeps
-    for (int64_t i = 0; i < B; ++i) dwv[(size_t)i] = I[(size_t)i].ls_fail ? ladder_after_ls_fail(o, I[(size_t)i].dlast) : 0.0;
-    BorderStats bs;
-    bs.qn = lbfgs ? &qn : nullptr;
-    for (int attempt = 0;; ++attempt) {
-      bs.reuse_point = attempt > 0;
-      if ((rc = bordered_step(p, &bz, lam, Nc, dwv.data(), o.delta_c, dz, Nz, dlam, Nc, okv.data(), &bs, true, ni > 0 ? dgd : nullptr, ni > 0 ? dgs : nullptr,
-                              bounds ? &bar : nullptr, nsi > 0 ? &slk : nullptr))) return rc;
-      bool again = false;
-      for (int64_t i = 0; i < B; ++i) {
-        Inst& s = I[(size_t)i];
-        if (s.status != 0 || okv[(size_t)i] || attempt >= o.max_refactor) continue;
-        dwv[(size_t)i] = ladder_next(o, dwv[(size_t)i], s.dlast);
-        again = true;
-      }
-      if (!again) break;
-    }
-    const bool dev_stats = bs.d_grad != nullptr;
-    std::vector<double> hst5, hdnu;
-    if (dev_stats) {
-      // device border: five numbers per instance (and the steps of the general rows' multipliers) instead of five vectors
-      // (with bounds BORDER_BAR_NSTAT more behind them, in the same buffer and the same copy)
-      // (with inequality stage rows BORDER_SLK_NSTAT more behind those)
-      const size_t n5 = (size_t)B * 5, nbar = n5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0),
-                   nstat = nbar + (nsi > 0 ? (size_t)B * BORDER_SLK_NSTAT : 0);
-      if (!d5) HIP_TRY(d5.alloc(nstat));
-      if (ni > 0) HIP_TRY(hipMemcpyAsync(dst, hs.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));   // slack shift of theta
-      hipLaunchKernelGGL(k_border_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, Nc, bs.d_c, bs.d_rx, bs.d_grad, (const double*)dz, (const double*)lam,
-                         (const int*)p->d_var_fixed, (const double*)(ni > 0 ? dst : nullptr), Ns, ng, d5, (const double*)slk.s, slk.Ns);
-      if (bounds)
-        hipLaunchKernelGGL(k_border_bar_stats, dim3((unsigned)B), dim3(64), 0, st, Nz, bar, (const double*)dz, bs.d_rx, (const int*)p->d_var_fixed,
-                           o.tau_min, d5 + n5);
-      if (nsi > 0)
-        hipLaunchKernelGGL(k_border_slack_stats, dim3((unsigned)B), dim3(64), 0, st, Nc, slk, (const double*)lam, (const double*)dlam, o.tau_min,
-                           d5 + nbar);
-      hst5.resize(nstat);
-      HIP_TRY(hipMemcpyAsync(hst5.data(), d5, hst5.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      if (ng > 0) {
-        hdnu.resize((size_t)B * ng);
-        HIP_TRY(hipMemcpy2DAsync(hdnu.data(), ng * sizeof(double), dlam + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
-      }
-    }
-    auto dnu_of = [&](int64_t i, int64_t q) { return dev_stats ? hdnu[(size_t)(i * ng + q)] : bs.dmu[(size_t)i * Nc + Ns + q]; };
-    // ---- convergence test (Ipopt's scaled error, reference Options), at the point the step was computed at
-    if ((rc = dto_eval_f_batch(h, &bz, df))) return rc;
-    HIP_TRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-    std::vector<double> hm;
-    if (!dev_stats) {
-      hm.resize((size_t)B * Nc);
-      HIP_TRY(hipMemcpyAsync(hm.data(), lam, hm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    hphi0 = hf;   // objective at the current point: the line search's phi_0
-    bool any = false;
-    std::vector<double> th0((size_t)B), gphid((size_t)B);
-    for (int64_t i = 0; i < B; ++i) {
-      Inst& s = I[(size_t)i];
-      if (s.status != 0) continue;
-      double th1 = 0, thinf = 0, dinf = 0, slam = 0, gd = 0;
-      if (dev_stats) {
-        const double* q5 = &hst5[(size_t)i * 5];
-        th1 = q5[0]; thinf = q5[1]; dinf = q5[2]; slam = q5[3]; gd = q5[4];
-      } else {
-        for (int64_t k = 0; k < Nc; ++k) {
-          const double sk = (k >= Ns && ineq[(size_t)(k - Ns)]) ? hs[(size_t)(i * ng + (k - Ns))] : 0.0;   // inequality rows: g + s
-          const double v = std::fabs(bs.c[(size_t)i * Nc + k] + sk); th1 += v; thinf = std::max(thinf, v); slam += std::fabs(hm[(size_t)i * Nc + k]);
-        }
-        for (int64_t k = 0; k < Nz; ++k) {
-          if (L.var_lo[k] != L.var_hi[k]) dinf = std::max(dinf, std::fabs(bs.rx[(size_t)i * Nz + k]));
-          gd += bs.grad[(size_t)i * Nz + k] * bs.dz[(size_t)i * Nz + k];
-        }
-      }
-      // complementarity of the slack / multiplier pairs against mu_target (termination; against mu: the barrier update below); the
-      // step of the inequality rows: ds = (mu - s nu) / nu - (s / nu) dnu, barrier term of the merit's directional derivative
-      double c0 = 0.0, snu = 0.0, bar_d = 0.0;
-      for (int64_t q = 0; q < ng; ++q) {
-        if (!ineq[(size_t)q]) continue;
-        const size_t e = (size_t)(i * ng + q);
-        const double sv = hs[e], nv = hnu[e], dnu = dnu_of(i, q);
-        c0 = std::max(c0, std::fabs(sv * nv - o.mu_target)); snu += std::fabs(nv);
-        hds[e] = (s.mu - sv * nv) / nv - (sv / nv) * dnu;
-        bar_d += hds[e] / sv;
-      }
-      // finite variable bounds: the bound multipliers join the scaling, the largest and the smallest gap z give the complementarity
-      // error against any mu (as wide_convergence forms it), r_x already holds - z_L + z_U
-      const double* qb = bounds ? &hst5[(size_t)B * 5 + (size_t)i * BORDER_BAR_NSTAT] : nullptr;
-      auto compl_bounds = [&](double mu_at) {
-        if (!bounds) return 0.0;
-        const double szmin = qb[BORDER_BAR_ISZMAX] > 0.0 ? 1.0 / qb[BORDER_BAR_ISZMAX] : 1e300;
-        return std::max(qb[BORDER_BAR_SZMAX] - mu_at, mu_at - szmin);
-      };
-      if (bounds) { dinf = qb[BORDER_BAR_DINF]; c0 = std::max(c0, compl_bounds(o.mu_target)); }
-      // inequality stage rows: the same two extremes of s nu from the device (nsi > 0 implies the device border), their ds / s in
-      // the merit's directional derivative exactly as the general rows' slacks
-      const double* qs = nsi > 0 ? &hst5[(size_t)B * 5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0) + (size_t)i * BORDER_SLK_NSTAT] : nullptr;
-      auto compl_slack = [&](double mu_at) {
-        if (!qs) return 0.0;
-        const double snumin = qs[BORDER_SLK_ISNUMAX] > 0.0 ? 1.0 / qs[BORDER_SLK_ISNUMAX] : 1e300;
-        return std::max(qs[BORDER_SLK_SNUMAX] - mu_at, mu_at - snumin);
-      };
-      if (qs) { c0 = std::max(c0, compl_slack(o.mu_target)); snu += qs[BORDER_SLK_SUMNU]; bar_d += qs[BORDER_SLK_DSS]; }
-      // (the slack's bound multiplier of a slack-eliminated row IS its nu: it counts among the bound multipliers, as the slack
-      //  multipliers do in conv_body)
-      const ErrScale es = ipopt_scaling(o, slam, Nc, snu + (bounds ? qb[BORDER_BAR_SUMZ] : 0.0), ni + n_bound + nsi);
-      const IterMeasures m{hf[(size_t)i], th1, thinf, dinf, std::max(std::max(dinf / es.sd, thinf), c0 / es.sc), c0};
-      mu_moved[(size_t)i] = 0;
-      s.status = terminal_status(o, s.iter, m, 0);   // acc_count = 0: no acceptable-level termination on this path
-      if (s.status == 0 && barrier) {
-        // Ipopt's monotone rule: once the barrier problem is solved to kappa_eps mu the parameter drops (and the filter is reset);
-        // the step computed above belongs to the old mu: this instance waits one round (alpha = 0) for the step of the new one
-        const double mu = monotone_mu(o, s.mu, std::max(dinf / es.sd, thinf), es.sc, [&](double mu_at) {
-          double c = std::max(compl_bounds(mu_at), compl_slack(mu_at));
-          for (int64_t q = 0; q < ng; ++q)
-            if (ineq[(size_t)q]) c = std::max(c, std::fabs(hs[(size_t)(i * ng + q)] * hnu[(size_t)(i * ng + q)] - mu_at));
-          return c;
-        });
-        if (mu != s.mu) { s.mu = mu; s.filter_n = 0; mu_moved[(size_t)i] = 1; }
-      }
-      init_theta_limits(s, th1);
-      th0[(size_t)i] = th1; gphid[(size_t)i] = gd - s.mu * bar_d;
-      if (bounds) gphid[(size_t)i] += qb[BORDER_BAR_DPHI];
-      if (s.status == 0) {
-        any = true;
-        if (dwv[(size_t)i] > 0.0) s.dlast = dwv[(size_t)i]; else s.dlast = 0.0;
-        if (!okv[(size_t)i]) s.ls_fail = 1;
-      }
-    }
-    if (!any) break;
-    // ---- filter line search over alpha = 2^-k: objective and l1 violation of a trial point from the callbacks (the violation
-    //      summed on the device).  Trial k is evaluated only while some running instance has not accepted a shorter-numbered
-    //      one (round 4: all eight trials of every iteration, each with its constraint vector over PCIe, were most of the
-    //      8.7 ms an iteration of a 512-instance batch took; a Newton step near the solution is accepted at alpha = 1)
-    std::vector<double> chosen_a((size_t)B, -1.0);
-    std::vector<char> ftype_a((size_t)B, 0);
-    std::vector<MostFeasible> best_a((size_t)B);
-    // inequality rows: the trials start from the fraction-to-the-boundary step of the slacks, the merit is the barrier function
-    std::vector<double> apmax((size_t)B, 1.0), admax((size_t)B, 1.0);
-    // finite bounds: the same from the device's statistics -- alpha_p^max and alpha_d^max combined by min, sum log(gap) in the merit
-    for (int64_t i = 0; i < B && barrier; ++i) {
-      Inst& s = I[(size_t)i];
-      if (s.status != 0) continue;
-      if (mu_moved[(size_t)i]) { chosen_a[(size_t)i] = 0.0; continue; }   // waits for the step of its new barrier parameter
-      if (bounds) {
-        const double* qb = &hst5[(size_t)B * 5 + (size_t)i * BORDER_BAR_NSTAT];
-        apmax[(size_t)i] = qb[BORDER_BAR_APMAX]; admax[(size_t)i] = qb[BORDER_BAR_ADMAX];
-        hphi0[(size_t)i] -= s.mu * qb[BORDER_BAR_LOGBAR];
-      }
-      if (nsi > 0) {   // the slacks of the inequality stage rows: the same three numbers
-        const double* qs = &hst5[(size_t)B * 5 + (bounds ? (size_t)B * BORDER_BAR_NSTAT : 0) + (size_t)i * BORDER_SLK_NSTAT];
-        apmax[(size_t)i] = std::min(apmax[(size_t)i], qs[BORDER_SLK_APMAX]); admax[(size_t)i] = std::min(admax[(size_t)i], qs[BORDER_SLK_ADMAX]);
-        hphi0[(size_t)i] -= s.mu * qs[BORDER_SLK_LOGS];
-      }
-      if (ni == 0) continue;
-      const double tau = std::max(o.tau_min, 1.0 - s.mu);
-      double lb = 0.0;
-      for (int64_t q = 0; q < ng; ++q) {
-        if (!ineq[(size_t)q]) continue;
-        const size_t e = (size_t)(i * ng + q);
-        const double dnu = dnu_of(i, q);
-        if (hds[e] < 0.0) apmax[(size_t)i] = std::min(apmax[(size_t)i], -tau * hs[e] / hds[e]);
-        if (dnu < 0.0) admax[(size_t)i] = std::min(admax[(size_t)i], -tau * hnu[e] / dnu);
-        lb += std::log(hs[e]);
-      }
-      hphi0[(size_t)i] -= s.mu * lb;
-    }
-    for (int k = 0; k < TRIALS; ++k) {
-      bool undecided = false;
-      for (int64_t i = 0; i < B; ++i) undecided = undecided || (I[(size_t)i].status == 0 && chosen_a[(size_t)i] < 0.0);
-      if (!undecided) break;
-      const double alpha2 = std::ldexp(1.0, -k);
-      for (int64_t i = 0; i < B; ++i) hal[(size_t)i] = (I[(size_t)i].status == 0 && chosen_a[(size_t)i] < 0.0) ? apmax[(size_t)i] * alpha2 : 0.0;
-      if (ni > 0) {
-        for (int64_t i = 0; i < B; ++i)
-          for (int64_t q = 0; q < ng; ++q) {
-            const size_t e = (size_t)(i * ng + q);
-            hst[e] = ineq[(size_t)q] ? hs[e] + hal[(size_t)i] * hds[e] : 0.0;
-          }
-        HIP_TRY(hipMemcpyAsync(dst, hst.data(), (size_t)B * ng * sizeof(double), hipMemcpyHostToDevice, st));
-      }
-      HIP_TRY(hipMemcpyAsync(zt, z, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToDevice, st));
-      HIP_TRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, zt, (const double*)dz, (const double*)dal, Nz, Nz, Nz);
-      dto_batch bt = bz;
-      bt.x = zt;
-      if ((rc = dto_eval_f_batch(h, &bt, df))) return rc;
-      if ((rc = dto_eval_g_batch(h, &bt, dc, Nc))) return rc;
-      if (bounds_or_slk)   // the violation and sum log(gap) of the trial point in one launch, both in the copy of theta (with inequality
+    HIP_TRY(hipMemcpyAsync(G.zt, G.z, (size_t)B * Nz * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(G.dal, G.hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (double*)G.zt, (const double*)G.dz, (const double*)G.dal,
+                       Nz, Nz, Nz);
+    dto_batch bt = G.bz;
+    bt.x = G.zt;
+    int rc;
+    if ((rc = dto_eval_f_batch(G.h, &bt, G.df))) return rc;
+    if ((rc = dto_eval_g_batch(G.h, &bt, G.dc, Nc))) return rc;
+    const double* shift = G.ni > 0 ? (const double*)G.dst : nullptr;
+    if (G.bounds_or_slk)   // the violation and sum log(gap) of the trial point in one launch, both in the copy of theta (with inequality
                            // stage rows: their slacks at alpha in the violation, and sum log of them as a third number)
-        hipLaunchKernelGGL(k_border_trial, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, (const double*)(ni > 0 ? dst : nullptr), Ns, ng,
-                           (const double*)(bounds ? (double*)zt : nullptr), Nz, (const double*)dlo, (const double*)dhi, (double*)dth, slk,
-                           (const double*)dal);
-      else
-        hipLaunchKernelGGL(k_rows_abs_sum, dim3((unsigned)B), dim3(64), 0, st, (const double*)dc, Nc, Nc, dth, (const double*)(ni > 0 ? dst : nullptr), Ns, ng);
-      HIP_TRY(hipMemcpyAsync(hf.data(), df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(hth.data(), dth, hth.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      for (int64_t i = 0; i < B; ++i) {
-        Inst& s = I[(size_t)i];
-        if (s.status != 0 || chosen_a[(size_t)i] >= 0.0) continue;
-        double pk = hf[(size_t)i];
-        const double tk = hth[(size_t)(nth * i)];
-        if (bounds) pk -= s.mu * hth[(size_t)(nth * i + 1)];
-        if (nsi > 0) pk -= s.mu * hth[(size_t)(nth * i + 2)];
-        for (int64_t q = 0; q < ng && ni > 0; ++q)
-          if (ineq[(size_t)q]) pk -= s.mu * std::log(hst[(size_t)(i * ng + q)]);
-        note_most_feasible(best_a[(size_t)i], k, tk);
-        const TrialVerdict v = trial_acceptable(s, th0[(size_t)i], hphi0[(size_t)i], gphid[(size_t)i], hal[(size_t)i], tk, pk);
-        if (v != TRIAL_REJECTED) { chosen_a[(size_t)i] = hal[(size_t)i]; ftype_a[(size_t)i] = v == TRIAL_ACCEPTED_FTYPE; }
-      }
-    }
-    for (int64_t i = 0; i < B; ++i) {
-      hal[(size_t)i] = 0.0;
-      Inst& s = I[(size_t)i];
-      if (s.status != 0) continue;
-      if (barrier && mu_moved[(size_t)i]) continue;   // no step, no iteration: its barrier parameter just moved
-      // (an instance whose trials were all rejected had all TRIALS of them evaluated)
-      hal[(size_t)i] = finish_line_search(s, chosen_a[(size_t)i], ftype_a[(size_t)i] != 0, best_a[(size_t)i], th0[(size_t)i], hphi0[(size_t)i],
-                                          apmax[(size_t)i], TRIALS, okv[(size_t)i] ? 0 : 1);
-      s.iter++;
-    }
-    HIP_TRY(hipMemcpyAsync(dal, hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-    if (bounds_or_slk) {
-      for (int64_t i = 0; i < B; ++i) had[(size_t)i] = hal[(size_t)i] == 0.0 ? 0.0 : admax[(size_t)i];
-      HIP_TRY(hipMemcpyAsync(dad, had.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    if (bounds) {
-      // bound multipliers first (their update reads the old point): alpha_d^max with the kappa_Sigma clamp against the instance's
-      // mu; an instance that takes no step (terminated, or its mu just moved) keeps them
-      hipLaunchKernelGGL(k_wide_update_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (const double*)z, (const double*)dz,
-                         (double*)zl, (double*)zu, (const double*)dlo, (const double*)dhi, (int64_t)0, (const double*)dal, (const double*)dad,
-                         (const double*)dmub, Nz);
-    }
-    hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, z, (const double*)dz, (const double*)dal, Nz, Nz, Nz);
-    if (nsi > 0)   // the multipliers of the inequality stage rows move with alpha_d and are clamped, their slacks with alpha; the other rows as below
-      hipLaunchKernelGGL(k_border_slack_update, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, Nc, slk, (double*)lam, (const double*)dlam,
-                         (const double*)dal, (const double*)dad, kappa_sigma, AXPY_BLOCKS_PER_ROW);
+      hipLaunchKernelGGL(k_border_trial, dim3((unsigned)B), dim3(64), 0, st, (const double*)G.dc, Nc, Nc, shift, Ns, ng,
+                         (const double*)(G.bounds ? (double*)G.zt : nullptr), Nz, (const double*)G.dlo, (const double*)G.dhi, (double*)G.dth, G.slk,
+                         (const double*)G.dal);
     else
-      hipLaunchKernelGGL(k_rows_axpy, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, lam, (const double*)dlam, (const double*)dal, Nc, Nc, Nc);
-    if (ni > 0) {
-      // general rows: equality multipliers move with the primal step, slack / multiplier pairs of the inequality rows with
-      // alpha and the dual fraction-to-the-boundary step, then Ipopt's kappa_sigma safeguard; mirrored into lam
-      for (int64_t i = 0; i < B; ++i) {
-        const double al = hal[(size_t)i];
-        if (I[(size_t)i].status != 0 && al == 0.0) continue;
-        const double ad = al == 0.0 ? 0.0 : admax[(size_t)i];
-        for (int64_t q = 0; q < ng; ++q) {
-          const size_t e = (size_t)(i * ng + q);
-          const double dnu = dnu_of(i, q);
-          if (!ineq[(size_t)q]) { hnu[e] += al * dnu; continue; }
-          hs[e] += al * hds[e];
-          hnu[e] += ad * dnu;
-          const double mu_i = I[(size_t)i].mu;
-          hnu[e] = std::max(std::min(hnu[e], kappa_sigma * mu_i / hs[e]), mu_i / (kappa_sigma * hs[e]));
-        }
-      }
-      if ((rc = put_nu())) return rc;
+      hipLaunchKernelGGL(k_rows_abs_sum, dim3((unsigned)B), dim3(64), 0, st, (const double*)G.dc, Nc, Nc, (double*)G.dth, shift, Ns, ng);
+    HIP_TRY(hipMemcpyAsync(G.hf.data(), G.df, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.hth.data(), G.dth, G.hth.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < B; ++i) {
+      if (!undecided(i)) continue;
+      GlobInst& s = G.I[(size_t)i];
+      double pk = G.hf[(size_t)i];
+      const double tk = G.hth[(size_t)(nth * i)];
+      if (G.bounds) pk -= s.mu * G.hth[(size_t)(nth * i + 1)];
+      if (G.nsi > 0) pk -= s.mu * G.hth[(size_t)(nth * i + 2)];
+      for (int64_t q = 0; q < ng && G.ni > 0; ++q)
+        if (G.ineq[(size_t)q]) pk -= s.mu * std::log(G.hst[(size_t)(i * ng + q)]);
+      note_most_feasible(G.best_a[(size_t)i], k, tk);
+      const TrialVerdict v = trial_acceptable(s, G.th0[(size_t)i], G.hphi0[(size_t)i], G.gphid[(size_t)i], G.hal[(size_t)i], tk, pk);
+      if (v != TRIAL_REJECTED) { G.chosen_a[(size_t)i] = G.hal[(size_t)i]; G.ftype_a[(size_t)i] = v == TRIAL_ACCEPTED_FTYPE; }
     }
-    if (lbfgs) {
-      // the step just taken, and grad_x L at the point it left with the multipliers it arrived at: grad f and J of that point are
-      // still in the step's workspace.  An instance that took no step (alpha = 0) saves nothing and pushes nothing
-      hipLaunchKernelGGL(k_border_qn_save, dim3((unsigned)(((size_t)B * Nz + 255) / 256)), dim3(256), 0, st, B, Nz, L.nnzJ, bs.d_J, bs.d_grad,
-                         (const double*)lam, Nc, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row, (const double*)dz,
-                         (const double*)dal, (double*)qn.s, (double*)qn.gl);
-      HIP_TRY(hipGetLastError());
-      for (int64_t i = 0; i < B; ++i) qn.pending[(size_t)i] = hal[(size_t)i] != 0.0 ? 1 : 0;
-    }
-    if (u.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > u.max_cpu_time) { timed_out = true; break; }
   }
-  HIP_TRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), z, Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
-  if (mu_out) HIP_TRY(hipMemcpy2DAsync(mu_out, ldmuo * sizeof(double), lam, Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
   for (int64_t i = 0; i < B; ++i) {
-    if (status) status[i] = (I[(size_t)i].status == 0 && timed_out) ? DTO_STATUS_CPU_TIME : I[(size_t)i].status;
-    if (iterations) iterations[i] = I[(size_t)i].iter;
+    G.hal[(size_t)i] = 0.0;
+    GlobInst& s = G.I[(size_t)i];
+    if (s.status != 0) continue;
+    if (G.barrier && G.mu_moved[(size_t)i]) continue;   // no step, no iteration: its barrier parameter just moved
+    // (an instance whose trials were all rejected had all TRIALS of them evaluated)
+    G.hal[(size_t)i] = finish_line_search(s, G.chosen_a[(size_t)i], G.ftype_a[(size_t)i] != 0, G.best_a[(size_t)i], G.th0[(size_t)i], G.hphi0[(size_t)i],
+                                          G.apmax[(size_t)i], TRIALS, G.okv[(size_t)i] ? 0 : 1);
+    s.iter++;
   }
   return DTO_OK;
 }
+
+// ---- take the steps: bound multipliers first (their update reads the old point; alpha_d^max with the kappa_Sigma clamp against
+//      the instance's mu), then z, then lam -- with inequality stage rows their multipliers move with alpha_d and are clamped, their
+//      slacks with alpha -- and on the host the general rows: equality multipliers move with the primal step, slack / multiplier pairs
+//      of the inequality rows with alpha and the common alpha_d (difference 6), then Ipopt's kappa_sigma safeguard; mirrored into
+//      lam.  An instance that takes no step (terminated, or its mu just moved) keeps everything
+static int border_loop_take_steps(BorderLoop& G) {
+  const double kappa_sigma = 1e10;
+  const int64_t B = G.B, Nz = G.Nz, Nc = G.Nc, ng = G.ng;
+  hipStream_t st = G.st;
+  const dim3 grid((unsigned)(B * AXPY_BLOCKS_PER_ROW));
+  HIP_TRY(hipMemcpyAsync(G.dal, G.hal.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  if (G.bounds_or_slk) {
+    for (int64_t i = 0; i < B; ++i) G.had[(size_t)i] = G.hal[(size_t)i] == 0.0 ? 0.0 : G.admax[(size_t)i];
+    HIP_TRY(hipMemcpyAsync(G.dad, G.had.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  if (G.bounds)
+    hipLaunchKernelGGL(k_wide_update_bounds, grid, dim3(256), 0, st, (const double*)G.z, (const double*)G.dz, (double*)G.zl, (double*)G.zu,
+                       (const double*)G.dlo, (const double*)G.dhi, (int64_t)0, (const double*)G.dal, (const double*)G.dad, (const double*)G.dmub, Nz);
+  hipLaunchKernelGGL(k_rows_axpy, grid, dim3(256), 0, st, (double*)G.z, (const double*)G.dz, (const double*)G.dal, Nz, Nz, Nz);
+  if (G.nsi > 0)
+    hipLaunchKernelGGL(k_border_slack_update, grid, dim3(256), 0, st, Nc, G.slk, (double*)G.lam, (const double*)G.dlam, (const double*)G.dal,
+                       (const double*)G.dad, kappa_sigma, AXPY_BLOCKS_PER_ROW);
+  else
+    hipLaunchKernelGGL(k_rows_axpy, grid, dim3(256), 0, st, (double*)G.lam, (const double*)G.dlam, (const double*)G.dal, Nc, Nc, Nc);
+  if (G.ni == 0) return DTO_OK;
+  for (int64_t i = 0; i < B; ++i) {
+    const double al = G.hal[(size_t)i];
+    if (!G.running(i) && al == 0.0) continue;
+    const double ad = al == 0.0 ? 0.0 : G.admax[(size_t)i];
+    for (int64_t q = 0; q < ng; ++q) {
+      const size_t e = (size_t)(i * ng + q);
+      const double dnu = G.hdnu[e];
+      if (!G.ineq[(size_t)q]) { G.hnu[e] += al * dnu; continue; }
+      G.hs[e] += al * G.hds[e];
+      G.hnu[e] += ad * dnu;
+      const double mu_i = G.I[(size_t)i].mu;
+      G.hnu[e] = std::max(std::min(G.hnu[e], kappa_sigma * mu_i / G.hs[e]), mu_i / (kappa_sigma * G.hs[e]));
+    }
+  }
+  return G.put_nu();
+}
+
+// ---- limited-memory mode: save the step just taken, and grad_x L at the point it left with the multipliers it arrived at -- grad f
+//      and J of that point are still in the step's workspace.  The pair joins the history when the next step has the derivatives of
+//      the new point (qn_update).  An instance that took no step (alpha = 0) saves nothing and pushes nothing
+static int border_loop_save_pair(BorderLoop& G) {
+  Problem* p = G.p;
+  hipLaunchKernelGGL(k_border_qn_save, dim3((unsigned)(((size_t)G.B * G.Nz + 255) / 256)), dim3(256), 0, G.st, G.B, G.Nz, p->L.nnzJ, G.bs.d_J, G.bs.d_grad,
+                     (const double*)G.lam, G.Nc, (const int*)p->d_csc_ptr, (const int*)p->d_csc_k, (const int*)p->d_csc_row, (const double*)G.dz,
+                     (const double*)G.dal, (double*)G.qn.s, (double*)G.qn.gl);
+  HIP_TRY(hipGetLastError());
+  for (int64_t i = 0; i < G.B; ++i) G.qn.pending[(size_t)i] = G.hal[(size_t)i] != 0.0 ? 1 : 0;
+  return DTO_OK;
+}
+
+// ---- end: the iterate and the multipliers to the caller, status (a running instance that ran out of max_cpu_time:
+//      DTO_STATUS_CPU_TIME) and iteration counts.  The bound multipliers are not returned
+static int border_loop_end(BorderLoop& G, double* x_out, int64_t ldxo, double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations) {
+  const int64_t B = G.B, Nz = G.Nz, Nc = G.Nc;
+  HIP_TRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), G.z, Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, G.st));
+  if (mu_out) HIP_TRY(hipMemcpy2DAsync(mu_out, ldmuo * sizeof(double), G.lam, Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, G.st));
+  HIP_TRY(hipStreamSynchronize(G.st));
+  for (int64_t i = 0; i < B; ++i) {
+    if (status) status[i] = (G.running(i) && G.timed_out) ? DTO_STATUS_CPU_TIME : G.I[(size_t)i].status;
+    if (iterations) iterations[i] = G.I[(size_t)i].iter;
+  }
+  return DTO_OK;
+}
+
+static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
+                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs) {
+  BorderLoop G;   // (its device buffers are released on every return)
+  int rc = border_loop_begin(G, p, opt, b, ldxo, mu_out != nullptr, ldmuo, lbfgs);
+  if (rc) return rc;
+  for (;;) {
+    if ((rc = border_loop_step(G))) return rc;
+    if ((rc = border_loop_point_stats(G))) return rc;
+    if (!border_loop_convergence(G)) break;
+    border_loop_step_limits(G);
+    if ((rc = border_loop_trials(G))) return rc;
+    if ((rc = border_loop_take_steps(G))) return rc;
+    if (G.lbfgs && (rc = border_loop_save_pair(G))) return rc;
+    if (G.user.max_cpu_time > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - G.t_start).count() > G.user.max_cpu_time) {
+      G.timed_out = true;
+      break;
+    }
+  }
+  return border_loop_end(G, x_out, ldxo, mu_out, ldmuo, status, iterations);
+}
+
 
 // ---- what dto_kkt_border_factor and dto_kkt_lbfgs_border share: the workspace of a border of nb rows (border_prepare), and, once
 //      the panel stands in W.g, Y = K^-1 G', the Schur complement and its LU (border_finish)

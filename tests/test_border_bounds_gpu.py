@@ -1,5 +1,6 @@
 """Finite variable bounds beside coupling GeneralConstraint rows on the bordered path, lane-per-instance linear solver
-(csrc/dto_solver.cpp: general_solve_batch, bordered_step_device; csrc/dto_border_kernels.hpp: BorderBar, k_border_bar_stats,
+(csrc/dto_solver.cpp: general_solve_batch = the border_loop_* phases over a BorderLoop, bordered_step_device;
+csrc/dto_border_kernels.hpp: k_border_rx, k_border_sig, k_border_stats, BorderBar, k_border_bar_stats,
 k_border_trial).  The pendulum swing-up of tests/test_general_accumulators_gpu.py, T = 50: Nz = 149 is no multiple of the
 wavefront, so the tail of every per-instance reduction is exercised.
 

@@ -1,4 +1,5 @@
-"""Per-instance parameters (dto_batch.params) on the bordered path (csrc/dto_solver.cpp: general_solve_batch), both linear solvers.
+"""Per-instance parameters (dto_batch.params) on the bordered path (csrc/dto_solver.cpp: general_solve_batch, whose BorderLoop
+keeps the batch with its params / ldp for every phase), both linear solvers.
 
 Lane path: problems.py: build_mpc_pendulum_coupled -- the MPC pendulum of tests/test_solve_gpu.py::test_per_instance_parameters_mpc_batch
 with a coupling row whose right-hand side is a parameter, theta_15 + theta_35 - w[3] <= 0 (a per-rollout budget).  A row that reads

@@ -1,5 +1,6 @@
 """Inequality rows of stage Constraints beside coupling GeneralConstraint rows on the bordered path, lane-per-instance linear solver
-with the device border (csrc/dto_solver.cpp: general_solve_batch, bordered_step_device; csrc/dto_border_kernels.hpp: BorderSlack,
+with the device border (csrc/dto_solver.cpp: general_solve_batch = the border_loop_* phases over a BorderLoop, bordered_step_device;
+csrc/dto_border_kernels.hpp: k_border_rhsc, k_border_stats, BorderSlack,
 k_border_slack_init / _stats / _update, k_border_trial).  The pendulum swing-up of tests/test_border_bounds_gpu.py, T = 50, with a
 speed limit thetadot^2 - v^2 <= 0 as a stage row at EVERY knot (examples/car/car.jl:53-60 style): Nz = 149 variables and
 Ns = 98 + 4 + 50 = 152 dynamics and stage rows, neither a multiple of the wavefront, so the tail of every per-instance reduction is

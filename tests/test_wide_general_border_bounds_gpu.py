@@ -1,5 +1,5 @@
 """Finite variable bounds beside coupling GeneralConstraint rows on the bordered path, tile linear solver (64 states, and 24
-states in the 64-state embedding): csrc/dto_solver.cpp general_solve_batch / bordered_step_tile with the barrier terms of
+states in the 64-state embedding): csrc/dto_solver.cpp general_solve_batch (border_loop_* phases) / bordered_step_tile with the barrier terms of
 csrc/dto_border_kernels.hpp (BorderBar in k_border_point, k_border_bar_stats, k_border_trial).
 
 The problems are those of tests/test_wide_general_border_gpu.py (T = 30, B = 3, knots 10 and 20, the same guesses) with action
