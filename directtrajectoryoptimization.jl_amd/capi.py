@@ -52,6 +52,14 @@ class KktSystem(C.Structure):
                 ("sigma_c", C.c_void_p), ("ldsc", C.c_int64), ("delta_w", C.c_double), ("delta_c", C.c_double)]
 
 
+class CPoint(C.Structure):
+    """dto_point: a primal-dual point of B instances in the caller's device arrays (qn_npairs / qn_sigma: host arrays)."""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("mu", C.c_void_p), ("ldmu", C.c_int64), ("zl", C.c_void_p), ("ldzl", C.c_int64),
+                ("zu", C.c_void_p), ("ldzu", C.c_int64), ("slack", C.c_void_p), ("ldslack", C.c_int64), ("barrier", C.c_void_p),
+                ("qn_s", C.c_void_p), ("ldqs", C.c_int64), ("qn_y", C.c_void_p), ("ldqy", C.c_int64), ("qn_npairs", c_int32_p),
+                ("qn_sigma", c_double_p)]
+
+
 class COptions(C.Structure):
     _fields_ = [("tol", C.c_double), ("s_max", C.c_double), ("max_iter", C.c_int), ("dual_inf_tol", C.c_double),
                 ("constr_viol_tol", C.c_double), ("compl_inf_tol", C.c_double), ("mu_init", C.c_double),
@@ -121,6 +129,8 @@ def lib() -> C.CDLL:
         "dto_kkt_step_batch": [vp, C.POINTER(Batch), vp, C.c_int64, C.c_double, C.c_double, vp, C.c_int64, vp, C.c_int64,
                                C.POINTER(C.c_int)],
         "dto_solve_batch": [vp, C.POINTER(COptions), C.POINTER(Batch), vp, C.c_int64, vp, C.c_int64, c_int32_p, c_int32_p],
+        "dto_solve_batch_warm": [vp, C.POINTER(COptions), C.POINTER(Batch), C.POINTER(CPoint), C.POINTER(CPoint), c_int32_p, c_int32_p],
+        "dto_point_shift": [vp, C.c_int64, C.POINTER(CPoint), C.c_int, vp],
         "dto_solver_begin": [vp, C.POINTER(COptions), C.POINTER(Batch)],
         "dto_solver_begin_warm": [vp, C.POINTER(COptions), C.POINTER(Batch), C.c_double],
         "dto_solver_repack": [vp, C.POINTER(C.c_int), vp],

@@ -18,6 +18,8 @@
 
 #include <cstdint>
 
+#include "dto_point_rules.hpp"
+
 namespace dto {
 
 constexpr int KB_MAX = 16;              // border rows of one panel
@@ -565,6 +567,49 @@ static __global__ void k_border_slack_update(int64_t Nc, BorderSlack sl, double*
       lam[b * Nc + k] += al * dlam[b * Nc + k];
     }
   }
+}
+
+// ---- warm start of the bordered solve loop from a caller's primal-dual point (dto_solve_batch_warm; the rules: warm_var /
+//      warm_slack / shift_source of dto_point_rules.hpp).  One thread per entry, instance-major, no atomics.
+// The variables: x / zl_in / zu_in are the caller's arrays with their leading dimensions (zl_in == NULL: no multipliers given,
+// every one starts on the central path), lo / hi the problem's shared bounds [Nz], mu [B] the barrier parameter per instance
+// (NULL without a barrier).  z [B][Nz] takes the point, zl / zu [B][Nz] the multipliers; zl == NULL when the problem has no finite
+// bound: only the fixed variables move then.
+static __global__ void k_border_warm_vars(int64_t B, int64_t Nz, const double* x, int64_t ldx, const double* zl_in, int64_t ldzl,
+                                          const double* zu_in, int64_t ldzu, const double* lo, const double* hi, const double* mu,
+                                          double bound_push, double bound_frac, double* z, double* zl, double* zu) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * Nz) return;
+  const int64_t b = idx / Nz, k = idx - b * Nz;
+  const bool have = zl != nullptr;
+  const WarmVar w = warm_var(x[b * ldx + k], lo[k], hi[k], have, (have && zl_in) ? zl_in[b * ldzl + k] : 0.0,
+                             (have && zl_in) ? zu_in[b * ldzu + k] : 0.0, mu ? mu[b] : 0.0, bound_push, bound_frac);
+  z[idx] = w.v;
+  if (have) { zl[idx] = w.zl; zu[idx] = w.zu; }
+}
+// The slacks of the inequality stage rows, the warm counterpart of k_border_slack_init: c [B][Nc] the constraint values at the
+// start point, lam [B][Nc] already holds the caller's multipliers, s_in the caller's slacks [B][lds] (NULL: none given).  A masked
+// row keeps (s, nu) when both are positive, else takes warm_slack's start; s = ds = 0 on the other rows.
+static __global__ void k_border_slack_warm(int64_t B, int64_t Nc, BorderSlack sl, const double* c, double* lam, const double* s_in,
+                                           int64_t lds, double bound_push) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * sl.Ns) return;
+  const int64_t b = idx / sl.Ns, k = idx - b * sl.Ns;
+  sl.ds[idx] = 0.0;
+  if (!sl.mask[k]) { sl.s[idx] = 0.0; return; }
+  const WarmSlack w = warm_slack(c[b * Nc + k], s_in ? s_in[b * lds + k] : 0.0, lam[b * Nc + k], sl.mu[b], bound_push);
+  sl.s[idx] = w.s;
+  lam[b * Nc + k] = w.nu;
+}
+// Receding horizon on a caller's arrays (dto_point_shift): k_wide_shift_knots with a leading dimension and an inner count.  `in`
+// holds B * inner vectors of n entries, vector v of instance b at in + (b * inner + v) * ld (inner = 1: x, the multipliers;
+// inner = 6: the secant pairs of the limited-memory history, one launch for all of them); out is compact, [B * inner][n].
+static __global__ void k_point_shift(const double* in, int64_t ld, double* out, int64_t n, int64_t B, int64_t inner, int stride,
+                                     int T_blocks, int last_len, int k, const int* keep) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * inner * n) return;
+  const int64_t row = idx / n, j = idx - row * n;   // row = b * inner + v
+  out[idx] = in[row * ld + shift_source(j, stride, T_blocks, last_len, k, keep && keep[j])];
 }
 
 // A trial point of the line search with bounds, one launch: out[2 b] = sum_k |rows[b][k] (+ shift)|, the sum of k_rows_abs_sum in

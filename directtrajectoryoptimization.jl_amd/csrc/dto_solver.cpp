@@ -17,6 +17,7 @@
 
 #include "../../include/dto.h"
 #include "dto_kkt_kernels.hpp"
+#include "dto_point_rules.hpp"
 #include "dto_im_kernels.hpp"
 #include "dto_wide_kernels.hpp"
 #include "dto_border_kernels.hpp"
@@ -190,7 +191,8 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
                          const double* gdiag = nullptr, const double* gshift = nullptr, const BorderBar* bar = nullptr,
                          const BorderSlack* slk = nullptr);
 static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
-                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs = false);
+                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs = false,
+                               const dto_point* start = nullptr, const dto_point* end = nullptr);
 
 // ---- wide-stage models, the linear solver alone: device copies of what dto_kkt_assemble was given.  The factor itself is in
 //      p->wide_fac, which dto_kkt_step_batch and the solver write too: each of them clears `factored`
@@ -596,25 +598,11 @@ static __global__ void k_wide_init_warm(double* z, double* zl, double* zu, const
   const int64_t b = blockIdx.x / AXPY_BLOCKS_PER_ROW, blk = blockIdx.x % AXPY_BLOCKS_PER_ROW;
   const double m = mu ? mu[b] : 0.0;
   for (int64_t i = blk * blockDim.x + threadIdx.x; i < n; i += (int64_t)AXPY_BLOCKS_PER_ROW * blockDim.x) {
-    double v = z[b * n + i], l = 0.0, u = 0.0;
-    const double a = lo[b * ldb + i], c = hi[b * ldb + i];
-    if (a == c) v = a;
-    else {
-      const bool fl = a > -1e300, fh = c < 1e300;
-      if (fl && fh) {
-        const double pl = fmin(bound_push * fmax(1.0, fabs(a)), bound_frac * (c - a));
-        const double pu = fmin(bound_push * fmax(1.0, fabs(c)), bound_frac * (c - a));
-        v = fmin(fmax(v, a + pl), c - pu);
-      } else if (fl) v = fmax(v, a + bound_push * fmax(1.0, fabs(a)));
-      else if (fh) v = fmin(v, c - bound_push * fmax(1.0, fabs(c)));
-      if (zl) {
-        const double pl = zl[b * n + i], pu = zu[b * n + i];
-        if (fl) l = pl > 0.0 ? pl : m / (v - a);
-        if (fh) u = pu > 0.0 ? pu : m / (c - v);
-      }
-    }
-    z[b * n + i] = v;
-    if (zl) { zl[b * n + i] = l; zu[b * n + i] = u; }
+    // (the rule itself: warm_var of dto_point_rules.hpp, shared with the bordered loop's k_border_warm_vars)
+    const WarmVar w = warm_var(z[b * n + i], lo[b * ldb + i], hi[b * ldb + i], zl != nullptr, zl ? zl[b * n + i] : 0.0, zl ? zu[b * n + i] : 0.0, m,
+                               bound_push, bound_frac);
+    z[b * n + i] = w.v;
+    if (zl) { zl[b * n + i] = w.zl; zu[b * n + i] = w.zu; }
   }
 }
 
@@ -628,14 +616,7 @@ static __global__ void k_wide_shift_knots(const double* in, double* out, int64_t
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const int64_t b = idx / n, j = idx % n;
-  int64_t src = j;
-  const int64_t t = j / stride, r = j % stride;
-  if (t < T_blocks && !(keep && keep[j])) {
-    if (t + k < T_blocks) src = (t + k) * stride + r;
-    else if (r < last_len) src = (int64_t)T_blocks * stride + r;
-    else src = (int64_t)(T_blocks - 1) * stride + r;
-  }
-  out[b * n + j] = in[b * n + src];
+  out[b * n + j] = in[b * n + shift_source(j, stride, T_blocks, last_len, k, keep && keep[j])];
 }
 
 // dto_solver_set_bounds: per-instance bounds lo / hi [B][n] against the problem's own slo / shi [n] -- the same pattern (fixed where
@@ -2417,7 +2398,8 @@ static int bordered_step(Problem* p, const dto_batch* b, const double* mu, int64
 // (BorderBar), k_border_bar_stats reduces what the host rules need to eight numbers per instance that ride the copy of
 // k_border_stats, k_border_trial adds sum log(gap) of a trial point to the launch that sums its violation, and
 // k_wide_init_bounds / k_wide_update_bounds keep the multipliers.  Without a finite bound none of that is allocated or launched.
-// The bound multipliers are not returned.
+// dto_solve_batch returns x and the constraint multipliers; dto_solve_batch_warm hands in a whole primal-dual point and gets one
+// back (bound multipliers, slacks, barrier parameters, the limited-memory history): border_loop_start_point / _end_point.
 // ------------------------------------------------------------------------------------------------
 // out[b] = sum_k |rows[b][k]| in a fixed order (lane-strided partial sums, then a tree): the l1 constraint violation of a trial point
 static __global__ __launch_bounds__(64) void k_rows_abs_sum(const double* rows, int64_t ld, int64_t n, double* out, const double* shift = nullptr,
@@ -2467,6 +2449,7 @@ struct BorderLoop {
   BorderStats bs;                      // what the step of this iteration left
   std::vector<GlobInst> I;             // (mu: finite bounds, inequality general rows and inequality stage rows share one per instance)
   std::vector<double> hz, hmu, had;    // (hz: the start point without bounds, staged here so that its upload needs no wait)
+  std::vector<double> hout;            // (the barrier parameters on their way into a caller's end point)
   // slacks and multipliers of the general rows on the host (the multipliers are mirrored into lam after every update), the slack
   // steps, s / nu, mu / nu and the trial slacks
   std::vector<double> hs, hnu, hds, hgd, hgs, hst;
@@ -2486,10 +2469,101 @@ struct BorderLoop {
   }
 };
 
+// ---- the start of a warm solve (dto_solve_batch_warm, start != NULL; the rules are stated in include/dto.h): the barrier parameter
+//      of every instance, the variables with their bound multipliers (k_border_warm_vars), the multipliers as given, the history.
+//      The slacks follow in border_loop_begin, where the cold start has them.  Every host record is the fresh one of a cold start
+static int border_loop_start_point(BorderLoop& G, const dto_point& s) {
+  const int64_t B = G.B, Nz = G.Nz, Nc = G.Nc, ng = G.ng, Ns = G.Ns;
+  hipStream_t st = G.st;
+  const dto_solver_opts& o = G.o;
+  if (G.barrier) {
+    std::vector<double> hb((size_t)B, 0.0);
+    if (s.barrier) {
+      HIP_TRY(hipMemcpyAsync(hb.data(), s.barrier, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    for (int64_t i = 0; i < B; ++i) G.I[(size_t)i].mu = hb[(size_t)i] > 0.0 ? hb[(size_t)i] : o.mu_init;
+  }
+  if (G.bounds_or_slk) {
+    for (int64_t i = 0; i < B; ++i) G.hmu[(size_t)i] = G.I[(size_t)i].mu;
+    HIP_TRY(hipMemcpyAsync(G.dmub, G.hmu.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  if (!G.bounds) {   // (the shared bounds are on the device with finite bounds only: the fixed variables need them here)
+    HIP_TRY(G.dlo.alloc((size_t)Nz));
+    HIP_TRY(G.dhi.alloc((size_t)Nz));
+    HIP_TRY(hipMemcpyAsync(G.dlo, G.p->L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(G.dhi, G.p->L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  const size_t blocks = ((size_t)B * Nz + 255) / 256;
+  if (blocks > 0x7fffffff) return set_error(DTO_ERR_UNSUPPORTED, "dto_solve_batch_warm: batch too large");
+  hipLaunchKernelGGL(k_border_warm_vars, dim3((unsigned)blocks), dim3(256), 0, st, B, Nz, (const double*)s.x, s.ldx, (const double*)s.zl, s.ldzl,
+                     (const double*)s.zu, s.ldzu, (const double*)G.dlo, (const double*)G.dhi, (const double*)(G.bounds ? (double*)G.dmub : nullptr),
+                     o.bound_push, o.bound_frac, (double*)G.z, (double*)(G.bounds ? (double*)G.zl : nullptr), (double*)(G.bounds ? (double*)G.zu : nullptr));
+  HIP_TRY(hipGetLastError());
+  if (s.mu) {
+    HIP_TRY(hipMemcpy2DAsync(G.lam, Nc * sizeof(double), s.mu, s.ldmu * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
+    if (G.ni > 0)   // the host keeps the multipliers of the general rows (read after the synchronisation of the slack start)
+      HIP_TRY(hipMemcpy2DAsync(G.hnu.data(), ng * sizeof(double), s.mu + Ns, s.ldmu * sizeof(double), ng * sizeof(double), (size_t)B,
+                               hipMemcpyDeviceToHost, st));
+  }
+  if (G.lbfgs && s.qn_s) {
+    HIP_TRY(hipMemcpy2DAsync(G.qn.S, Nz * sizeof(double), s.qn_s, s.ldqs * sizeof(double), Nz * sizeof(double), (size_t)B * QnHistory::M,
+                             hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(G.qn.Y, Nz * sizeof(double), s.qn_y, s.ldqy * sizeof(double), Nz * sizeof(double), (size_t)B * QnHistory::M,
+                             hipMemcpyDeviceToDevice, st));
+    for (int64_t i = 0; i < B; ++i) { G.qn.npairs[(size_t)i] = s.qn_npairs[i]; G.qn.sigma[(size_t)i] = s.qn_sigma[i]; }
+  }
+  return DTO_OK;
+}
+
+// ---- the rest of the point a solve ends at (dto_solve_batch_warm: x and mu are border_loop_end's own copies): strided copies of
+//      what the loop has -- bound multipliers, the slacks of the stage rows from the device and of the general rows from the
+//      host (as put_nu mirrors their multipliers), the barrier parameter of every instance, the history.  What the problem does
+//      not have comes back as zeros.  hout lives in G until border_loop_end has waited for the stream
+static int border_loop_end_point(BorderLoop& G, const dto_point& e) {
+  const int64_t B = G.B, Nz = G.Nz, ng = G.ng, Ns = G.Ns;
+  const size_t D = sizeof(double);
+  hipStream_t st = G.st;
+  if (e.zl) {
+    if (G.bounds) {
+      HIP_TRY(hipMemcpy2DAsync(e.zl, e.ldzl * D, G.zl, Nz * D, Nz * D, (size_t)B, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpy2DAsync(e.zu, e.ldzu * D, G.zu, Nz * D, Nz * D, (size_t)B, hipMemcpyDeviceToDevice, st));
+    } else {
+      HIP_TRY(hipMemset2DAsync(e.zl, e.ldzl * D, 0, Nz * D, (size_t)B, st));
+      HIP_TRY(hipMemset2DAsync(e.zu, e.ldzu * D, 0, Nz * D, (size_t)B, st));
+    }
+  }
+  if (e.slack) {
+    if (G.nsi > 0) HIP_TRY(hipMemcpy2DAsync(e.slack, e.ldslack * D, G.ss, Ns * D, Ns * D, (size_t)B, hipMemcpyDeviceToDevice, st));
+    else if (Ns > 0) HIP_TRY(hipMemset2DAsync(e.slack, e.ldslack * D, 0, Ns * D, (size_t)B, st));
+    if (ng > 0) HIP_TRY(hipMemcpy2DAsync(e.slack + Ns, e.ldslack * D, G.hs.data(), ng * D, ng * D, (size_t)B, hipMemcpyHostToDevice, st));
+  }
+  if (e.barrier) {
+    G.hout.assign((size_t)B, 0.0);
+    for (int64_t i = 0; i < B && G.barrier; ++i) G.hout[(size_t)i] = G.I[(size_t)i].mu;
+    HIP_TRY(hipMemcpyAsync(e.barrier, G.hout.data(), (size_t)B * D, hipMemcpyHostToDevice, st));
+  }
+  if (e.qn_s) {
+    const size_t rows = (size_t)B * QnHistory::M;
+    if (G.lbfgs) {
+      HIP_TRY(hipMemcpy2DAsync(e.qn_s, e.ldqs * D, G.qn.S, Nz * D, Nz * D, rows, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpy2DAsync(e.qn_y, e.ldqy * D, G.qn.Y, Nz * D, Nz * D, rows, hipMemcpyDeviceToDevice, st));
+    } else {
+      HIP_TRY(hipMemset2DAsync(e.qn_s, e.ldqs * D, 0, Nz * D, rows, st));
+      HIP_TRY(hipMemset2DAsync(e.qn_y, e.ldqy * D, 0, Nz * D, rows, st));
+    }
+    for (int64_t i = 0; i < B; ++i) {
+      e.qn_npairs[i] = G.lbfgs ? G.qn.npairs[(size_t)i] : 0;
+      e.qn_sigma[i] = G.lbfgs ? G.qn.sigma[(size_t)i] : 1.0;
+    }
+  }
+  return DTO_OK;
+}
+
 // ---- begin: argument checks, row classification, allocation, the start point (pushed inside finite bounds, fixed variables on
 //      their values), slacks and multipliers of the inequality rows (s = max(-c, 1e-2), nu = 1, mu_init)
 static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, const dto_batch* b, int64_t ldxo, bool want_mu, int64_t ldmuo,
-                             bool lbfgs) {
+                             bool lbfgs, const dto_point* start) {
   int rc = p->ensure_device();
   if (rc) return rc;
   const Layout& L = p->L;
@@ -2499,7 +2573,7 @@ static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, 
   if (lbfgs && (!p->vt->launch_wide || 2 * QnHistory::M + L.Ngen > KB_MAX))
     return set_error(DTO_ERR_UNSUPPORTED, "limited-memory bordered loop: tile path with at most four GeneralConstraint rows");
   if (lbfgs && b->B < 1) return set_error(DTO_ERR_INVALID, "empty batch");
-  if (lbfgs && (b->ldx < Nz || ldxo < Nz || (want_mu && ldmuo < Nc))) return set_error(DTO_ERR_INVALID, "leading dimension too small");
+  if (lbfgs && ((!start && b->ldx < Nz) || ldxo < Nz || (want_mu && ldmuo < Nc))) return set_error(DTO_ERR_INVALID, "leading dimension too small");
   if (lbfgs && L.Nstage != 0) return set_error(DTO_ERR_UNSUPPORTED, "wide-stage models: dynamics rows, GeneralConstraint rows and bounds only");
   // per-instance parameters (dto_batch.params, [B][ldp]): every callback of this loop and both linear solvers read the instance's own
   // (dto_kkt_assemble / wide_kkt_assemble take them from the batch at every call, a further delta_w attempt at the same point included)
@@ -2561,12 +2635,14 @@ static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, 
     HIP_TRY(G.dhi.alloc((size_t)Nz));
     HIP_TRY(hipMemcpyAsync(G.dlo, L.var_lo.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(G.dhi, L.var_hi.data(), Nz * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpy2DAsync(G.z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (double*)G.z, (double*)G.zl, (double*)G.zu,
-                       (const double*)G.dlo, (const double*)G.dhi, (int64_t)0, o.mu_init, o.bound_push, o.bound_frac, Nz);
-    HIP_TRY(hipGetLastError());
+    if (!start) {
+      HIP_TRY(hipMemcpy2DAsync(G.z, Nz * sizeof(double), b->x, b->ldx * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_wide_init_bounds, dim3((unsigned)(B * AXPY_BLOCKS_PER_ROW)), dim3(256), 0, st, (double*)G.z, (double*)G.zl, (double*)G.zu,
+                         (const double*)G.dlo, (const double*)G.dhi, (int64_t)0, o.mu_init, o.bound_push, o.bound_frac, Nz);
+      HIP_TRY(hipGetLastError());
+    }
     G.bar.z = G.z; G.bar.zl = G.zl; G.bar.zu = G.zu; G.bar.lo = G.dlo; G.bar.hi = G.dhi; G.bar.mu = G.dmub;
-  } else {
+  } else if (!start) {
     // the guess, with the fixed variables put on their values
     std::vector<double>& hz = G.hz;
     hz.resize((size_t)B * Nz);
@@ -2577,7 +2653,7 @@ static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, 
         if (L.var_lo[k] == L.var_hi[k]) hz[(size_t)i * Nz + k] = L.var_lo[k];
     HIP_TRY(hipMemcpyAsync(G.z, hz.data(), hz.size() * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  HIP_TRY(hipMemsetAsync(G.lam, 0, (size_t)B * Nc * sizeof(double), st));
+  if (!start || !start->mu) HIP_TRY(hipMemsetAsync(G.lam, 0, (size_t)B * Nc * sizeof(double), st));
   if (lbfgs) {
     if ((rc = ensure_border_csc(p))) return rc;
     if ((rc = G.qn.init(B, Nz, st))) return rc;
@@ -2594,6 +2670,7 @@ static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, 
   G.mu_moved.assign((size_t)B, 0);
   G.bz = *b;
   G.bz.x = G.z; G.bz.ldx = Nz;
+  if (start && (rc = border_loop_start_point(G, *start))) return rc;
   if (nsi > 0) {
     // the same start for the slacks of the inequality stage rows, on the device: s = max(-c, 1e-2), nu = 1 in their entries of lam
     HIP_TRY(G.ss.alloc((size_t)B * Ns));
@@ -2602,8 +2679,12 @@ static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, 
     HIP_TRY(hipMemcpyAsync(G.dsmask, G.smask.data(), (size_t)Ns * sizeof(int), hipMemcpyHostToDevice, st));
     G.slk.s = G.ss; G.slk.ds = G.sds; G.slk.mask = G.dsmask; G.slk.mu = G.dmub; G.slk.Ns = Ns;
     if ((rc = dto_eval_g_batch(G.h, &G.bz, G.dc, Nc))) return rc;
-    hipLaunchKernelGGL(k_border_slack_init, dim3((unsigned)(((size_t)B * Ns + 255) / 256)), dim3(256), 0, st, B, Nc, G.slk, (const double*)G.dc,
-                       (double*)G.lam);
+    if (start)
+      hipLaunchKernelGGL(k_border_slack_warm, dim3((unsigned)(((size_t)B * Ns + 255) / 256)), dim3(256), 0, st, B, Nc, G.slk, (const double*)G.dc,
+                         (double*)G.lam, (const double*)start->slack, start->ldslack, o.bound_push);
+    else
+      hipLaunchKernelGGL(k_border_slack_init, dim3((unsigned)(((size_t)B * Ns + 255) / 256)), dim3(256), 0, st, B, Nc, G.slk, (const double*)G.dc,
+                         (double*)G.lam);
     HIP_TRY(hipGetLastError());
   }
   if (ni > 0) {
@@ -2611,10 +2692,19 @@ static int border_loop_begin(BorderLoop& G, Problem* p, const dto_options* opt, 
     if ((rc = dto_eval_g_batch(G.h, &G.bz, G.dc, Nc))) return rc;
     std::vector<double> hg((size_t)B * ng);
     HIP_TRY(hipMemcpy2DAsync(hg.data(), ng * sizeof(double), G.dc + Ns, Nc * sizeof(double), ng * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, st));
+    if (start && start->slack)   // (hnu holds the caller's multipliers of the general rows: border_loop_start_point)
+      HIP_TRY(hipMemcpy2DAsync(G.hs.data(), ng * sizeof(double), start->slack + Ns, start->ldslack * sizeof(double), ng * sizeof(double), (size_t)B,
+                               hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < B; ++i)
-      for (int64_t q = 0; q < ng; ++q)
-        if (G.ineq[(size_t)q]) { G.hs[(size_t)(i * ng + q)] = std::max(-hg[(size_t)(i * ng + q)], 1e-2); G.hnu[(size_t)(i * ng + q)] = 1.0; }
+      for (int64_t q = 0; q < ng; ++q) {
+        const size_t e = (size_t)(i * ng + q);
+        if (!G.ineq[(size_t)q]) { G.hs[e] = 0.0; continue; }
+        if (start) {   // the warm rule of the stage rows' slacks (k_border_slack_warm), here on the host
+          const WarmSlack w = warm_slack(hg[e], G.hs[e], G.hnu[e], G.I[(size_t)i].mu, o.bound_push);
+          G.hs[e] = w.s; G.hnu[e] = w.nu;
+        } else { G.hs[e] = std::max(-hg[e], 1e-2); G.hnu[e] = 1.0; }
+      }
     if ((rc = G.put_nu())) return rc;
   }
   G.t_start = std::chrono::steady_clock::now();
@@ -2974,11 +3064,14 @@ static int border_loop_save_pair(BorderLoop& G) {
 }
 
 // ---- end: the iterate and the multipliers to the caller, status (a running instance that ran out of max_cpu_time:
-//      DTO_STATUS_CPU_TIME) and iteration counts.  The bound multipliers are not returned
-static int border_loop_end(BorderLoop& G, double* x_out, int64_t ldxo, double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations) {
+//      DTO_STATUS_CPU_TIME) and iteration counts; with an end point (dto_solve_batch_warm) the rest of the primal-dual point
+static int border_loop_end(BorderLoop& G, double* x_out, int64_t ldxo, double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations,
+                           const dto_point* end) {
   const int64_t B = G.B, Nz = G.Nz, Nc = G.Nc;
   HIP_TRY(hipMemcpy2DAsync(x_out, ldxo * sizeof(double), G.z, Nz * sizeof(double), Nz * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, G.st));
   if (mu_out) HIP_TRY(hipMemcpy2DAsync(mu_out, ldmuo * sizeof(double), G.lam, Nc * sizeof(double), Nc * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, G.st));
+  int rc;
+  if (end && (rc = border_loop_end_point(G, *end))) return rc;
   HIP_TRY(hipStreamSynchronize(G.st));
   for (int64_t i = 0; i < B; ++i) {
     if (status) status[i] = (G.running(i) && G.timed_out) ? DTO_STATUS_CPU_TIME : G.I[(size_t)i].status;
@@ -2988,9 +3081,10 @@ static int border_loop_end(BorderLoop& G, double* x_out, int64_t ldxo, double* m
 }
 
 static int general_solve_batch(Problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
-                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs) {
+                               double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations, bool lbfgs, const dto_point* start,
+                               const dto_point* end) {
   BorderLoop G;   // (its device buffers are released on every return)
-  int rc = border_loop_begin(G, p, opt, b, ldxo, mu_out != nullptr, ldmuo, lbfgs);
+  int rc = border_loop_begin(G, p, opt, b, ldxo, mu_out != nullptr, ldmuo, lbfgs, start);
   if (rc) return rc;
   for (;;) {
     if ((rc = border_loop_step(G))) return rc;
@@ -3005,7 +3099,7 @@ static int general_solve_batch(Problem* p, const dto_options* opt, const dto_bat
       break;
     }
   }
-  return border_loop_end(G, x_out, ldxo, mu_out, ldmuo, status, iterations);
+  return border_loop_end(G, x_out, ldxo, mu_out, ldmuo, status, iterations, end);
 }
 
 
@@ -4013,6 +4107,90 @@ int dto_solve_batch(dto_problem* h, const dto_options* opt, const dto_batch* b, 
   int rc = dto_solver_begin(h, opt, b);
   if (rc) return rc;
   return dto_solver_run(h, x_out, ldxo, mu_out, ldmuo, status, iterations, b->stream);
+}
+
+// the argument checks that dto_solve_batch_warm and dto_point_shift share: x, the leading dimensions, zl / zu together, the history
+// whole (host_values: qn_npairs and qn_sigma are read, a start point's)
+static int point_check(const dto::Problem* p, const dto_point* pt, int64_t B, const char* who, bool host_values) {
+  const int64_t Nz = p->L.Nz, Nc = p->L.Nc;
+  const std::string w(who);
+  if (!pt->x) return set_error(DTO_ERR_INVALID, w + ": x is NULL");
+  if ((pt->zl == nullptr) != (pt->zu == nullptr)) return set_error(DTO_ERR_INVALID, w + ": zl and zu are both NULL or both set");
+  const int nq = (pt->qn_s ? 1 : 0) + (pt->qn_y ? 1 : 0) + (pt->qn_npairs ? 1 : 0) + (pt->qn_sigma ? 1 : 0);
+  if (nq != 0 && nq != 4) return set_error(DTO_ERR_INVALID, w + ": qn_s, qn_y, qn_npairs and qn_sigma are all NULL or all set");
+  if (pt->ldx < Nz || (pt->mu && pt->ldmu < Nc) || (pt->zl && (pt->ldzl < Nz || pt->ldzu < Nz)) || (pt->slack && pt->ldslack < Nc) ||
+      (nq && (pt->ldqs < Nz || pt->ldqy < Nz)))
+    return set_error(DTO_ERR_INVALID, w + ": leading dimension too small");
+  for (int64_t i = 0; host_values && nq && i < B; ++i) {
+    if (pt->qn_npairs[i] < 0 || pt->qn_npairs[i] > dto::QnHistory::M) return set_error(DTO_ERR_INVALID, w + ": qn_npairs outside 0..6");
+    if (!(pt->qn_sigma[i] > 0.0) || !std::isfinite(pt->qn_sigma[i])) return set_error(DTO_ERR_INVALID, w + ": qn_sigma must be positive and finite");
+  }
+  return DTO_OK;
+}
+
+int dto_solve_batch_warm(dto_problem* h, const dto_options* opt, const dto_batch* b, const dto_point* start, dto_point* end,
+                         int32_t* status, int32_t* iterations) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p || !b || !end) return set_error(DTO_ERR_INVALID, "null argument");
+  // exactly the problems dto_solve_batch sends to general_solve_batch
+  const bool lbfgs = p->vt->launch_wide && 2 * dto::QnHistory::M + p->L.Ngen <= dto::KB_MAX && opt && opt->hessian_approximation == DTO_HESSIAN_LBFGS;
+  if (!lbfgs && p->L.Ngen == 0)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_solve_batch_warm: the bordered loop's problems only (GeneralConstraint rows, or the tile path's limited-memory "
+                                          "mode); this problem has warm starts through dto_solver_begin_warm");
+  if (b->B < 1) return set_error(DTO_ERR_INVALID, "dto_solve_batch_warm: empty batch");
+  int rc;
+  if ((rc = point_check(p, end, b->B, "dto_solve_batch_warm, end", false))) return rc;
+  if (start && (rc = point_check(p, start, b->B, "dto_solve_batch_warm, start", true))) return rc;
+  if (!start && (!b->x || b->ldx < p->L.Nz)) return set_error(DTO_ERR_INVALID, "dto_solve_batch_warm: a cold start needs b->x with ldx >= num_variables");
+  rc = dto::general_solve_batch(p, opt, b, end->x, end->ldx, end->mu, end->ldmu, status, iterations, lbfgs, start, end);
+  if (rc == DTO_OK) p->hessian_mode_last = lbfgs ? DTO_HESSIAN_LBFGS : DTO_HESSIAN_EXACT;
+  return rc;
+}
+
+int dto_point_shift(dto_problem* h, int64_t B, dto_point* pt, int knots, void* stream) {
+  Problem* p = reinterpret_cast<Problem*>(h);
+  if (!p || !pt || knots < 0) return set_error(DTO_ERR_INVALID, "bad arguments");
+  if (B < 1) return set_error(DTO_ERR_INVALID, "dto_point_shift: empty batch");
+  int rc;
+  if ((rc = point_check(p, pt, B, "dto_point_shift", false))) return rc;
+  const dto::Layout& L = p->L;
+  const int T = L.T;
+  if (knots >= T - 1) return set_error(DTO_ERR_INVALID, "shift by fewer knots than the horizon has");
+  for (int t = 1; t < T; ++t)
+    if (L.nx[t] != L.nx[0] || (t < T - 1 && L.nu[t] != L.nu[0]))
+      return set_error(DTO_ERR_UNSUPPORTED, "dto_point_shift needs the same state / action dimensions at every knot");
+  const int nx = L.nx[0], nu = L.nu[0];
+  const int64_t Nz = L.Nz, Nc = L.Nc;
+  if (L.Ndyn != (int64_t)(T - 1) * nx || Nz != (int64_t)(T - 1) * (nx + nu) + nx)
+    return set_error(DTO_ERR_UNSUPPORTED, "dto_point_shift: unexpected variable / dynamics row count");
+  if (knots == 0) return DTO_OK;
+  if ((rc = p->ensure_device())) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t M = dto::QnHistory::M;
+  const int64_t longest = std::max<int64_t>(B * Nz * (pt->qn_s ? M : 1), pt->mu ? B * Nc : 0);
+  if ((longest + 255) / 256 > 0x7fffffff) return set_error(DTO_ERR_UNSUPPORTED, "dto_point_shift: batch too large");
+  dto::DevBuf<double> tmp;   // the one scratch buffer: every array goes through it and back, in stream order
+  HIP_TRY(tmp.alloc((size_t)longest));
+  auto shift = [&](double* a, int64_t ld, int64_t n, int64_t inner, int stride, int last_len, const int* keep) -> int {
+    if (!a || n == 0) return DTO_OK;
+    const int64_t total = B * inner * n;
+    hipLaunchKernelGGL(dto::k_point_shift, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)a, ld, (double*)tmp, n, B, inner, stride,
+                       T - 1, last_len, knots, keep);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(a, ld * sizeof(double), tmp, n * sizeof(double), n * sizeof(double), (size_t)(B * inner), hipMemcpyDeviceToDevice, st));
+    return DTO_OK;
+  };
+  rc = shift(pt->x, pt->ldx, Nz, 1, nx + nu, nx, nullptr);
+  // dynamics multipliers: T - 1 blocks of n_x rows; the stage and general rows behind them stay, and so do the marked rows
+  if (!rc) rc = shift(pt->mu, pt->ldmu, Nc, 1, nx, 0, (const int*)p->d_shift_keep);
+  if (!rc) rc = shift(pt->zl, pt->ldzl, Nz, 1, nx + nu, nx, nullptr);
+  if (!rc) rc = shift(pt->zu, pt->ldzu, Nz, 1, nx + nu, nx, nullptr);
+  if (!rc) rc = shift(pt->qn_s, pt->ldqs, Nz, M, nx + nu, nx, nullptr);
+  if (!rc) rc = shift(pt->qn_y, pt->ldqy, Nz, M, nx + nu, nx, nullptr);
+  const hipError_t e = hipStreamSynchronize(st);   // tmp is dropped at the return: the launches above must have finished
+  if (rc) return rc;
+  if (e != hipSuccess) return dto::hip_fail(e, "dto_point_shift");
+  return DTO_OK;
 }
 
 int dto_solver_begin_warm(dto_problem* h, const dto_options* opt, const dto_batch* b, double mu0) {

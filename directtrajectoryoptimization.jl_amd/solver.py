@@ -380,6 +380,69 @@ def _c_options(o: "Options", check_every: int = 10, lbfgs: bool = False) -> "cap
     return c
 
 
+@dataclass
+class Point:
+    """dto_point: a primal-dual point of B instances that the CALLER owns, in the solver's layout (Solver.new_point allocates one;
+    Solver.solve_batch_warm reads and writes it, Solver.shift_point moves it).  Every device array is a float64 torch tensor whose
+    rows are contiguous (a view with a larger row stride is fine: the stride is the leading dimension) or a pair
+    (device pointer, leading dimension); None = not given / not wanted.
+    x [B][num_variables], mu [B][num_constraint] (solver row order), zl / zu [B][num_variables] (both or neither),
+    slack [B][num_constraint], barrier [B], qn_s / qn_y [B][6][num_variables] with the host arrays qn_npairs (int32 [B]) and
+    qn_sigma (float64 [B]) -- all four or none."""
+    HISTORY = 6
+    x: object = None
+    mu: object = None
+    zl: object = None
+    zu: object = None
+    slack: object = None
+    barrier: object = None
+    qn_s: object = None
+    qn_y: object = None
+    qn_npairs: object = None
+    qn_sigma: object = None
+
+    def batch(self):
+        return int(self.x.shape[0])
+
+    @staticmethod
+    def _dev(a, rows_per_instance=1):
+        """(pointer, leading dimension) of a device array"""
+        if a is None:
+            return None, 0
+        if isinstance(a, tuple):
+            return int(a[0]) or None, int(a[1])
+        if a.dtype.is_floating_point and a.element_size() != 8:
+            raise ValueError("Point arrays are float64")
+        if a.dim() == 1:
+            if a.numel() > 1 and a.stride(0) != 1:
+                raise ValueError("Point.barrier must be contiguous")
+            return a.data_ptr(), int(a.shape[0])
+        if a.stride(-1) != 1 and a.shape[-1] > 1:
+            raise ValueError("Point arrays need contiguous rows")
+        n = int(a.shape[-1])
+        if a.dim() == 2:
+            return a.data_ptr(), int(a.stride(0)) if a.shape[0] > 1 else n
+        ld = int(a.stride(1))
+        if a.dim() != 3 or a.shape[1] != rows_per_instance or (a.shape[0] > 1 and a.stride(0) != rows_per_instance * ld):
+            raise ValueError("Point history arrays are [B][6][ld] with instance stride 6 * ld")
+        return a.data_ptr(), ld
+
+    def _as_c(self, B):
+        c = capi.CPoint()
+        for name, ldname in (("x", "ldx"), ("mu", "ldmu"), ("zl", "ldzl"), ("zu", "ldzu"), ("slack", "ldslack"), ("qn_s", "ldqs"), ("qn_y", "ldqy")):
+            ptr, ld = self._dev(getattr(self, name), self.HISTORY)
+            setattr(c, name, ptr)
+            setattr(c, ldname, ld)
+        c.barrier = self._dev(self.barrier)[0]
+        for name, dt, ct in (("qn_npairs", np.int32, capi.c_int32_p), ("qn_sigma", np.float64, capi.c_double_p)):
+            v = getattr(self, name)
+            if v is not None:
+                if not (isinstance(v, np.ndarray) and v.dtype == dt and v.flags.c_contiguous and v.shape == (B,)):
+                    raise ValueError(f"Point.{name}: a contiguous host array of {np.dtype(dt).name} [B]")
+                setattr(c, name, v.ctypes.data_as(ct))
+        return c
+
+
 class HessianModeNotice(UserWarning):
     """Issued once per process when a problem built with evaluate_hessian=false is solved with second derivatives anyway."""
 
@@ -679,6 +742,55 @@ class Solver:
                                                  mu_out_ptr or None, ldmuo, status.ctypes.data_as(capi.c_int32_p),
                                                  iters.ctypes.data_as(capi.c_int32_p)))
         return status, iters
+
+    def new_point(self, B, history=None, device="cuda"):
+        """A Point for B instances in the solver's layout, zero-filled torch tensors.  history: with the limited-memory secant
+        pairs (default: when the solver runs in that mode)."""
+        import torch
+        n = self._solve_nlp
+        nz, nc = int(n.num_variables), max(1, int(n.num_constraint))
+        kw = dict(device=device, dtype=torch.float64)
+        pt = Point(x=torch.zeros((B, nz), **kw), mu=torch.zeros((B, nc), **kw), zl=torch.zeros((B, nz), **kw), zu=torch.zeros((B, nz), **kw),
+                   slack=torch.zeros((B, nc), **kw), barrier=torch.zeros(B, **kw))
+        if (self.hessian_mode == "lbfgs") if history is None else history:
+            pt.qn_s = torch.zeros((B, Point.HISTORY, nz), **kw)
+            pt.qn_y = torch.zeros((B, Point.HISTORY, nz), **kw)
+            pt.qn_npairs = np.zeros(B, dtype=np.int32)
+            pt.qn_sigma = np.ones(B)
+        return pt
+
+    def solve_batch_warm(self, B, start, end, stream=0, check_every=10, params_ptr=0, ldp=0, x0_ptr=0, ldx=0):
+        """dto_solve_batch_warm: solve B instances of a problem of the host-driven bordered loop (GeneralConstraint rows on the
+        border, or the tile path's limited-memory mode) from the primal-dual Point `start` and write the whole point the solve ends
+        at to `end` (which may be `start`).  start=None: the cold start of solve_batch from x0_ptr / ldx, the same bits.
+        Points are in the SOLVER's layout: for a 17..63-state problem that is the 64-state embedding -- pad_batch / unpad_batch map
+        x, every other array is passed from one call to the next as it came.  Nothing stays in the handle.
+        Returns (status[B], iterations[B])."""
+        if self.solve_unsupported:
+            raise ValueError(self.solve_unsupported)
+        n = self._solve_nlp
+        b = n._batch(x0_ptr, B, ldx or n.num_variables, stream, params_ptr, ldp)
+        co = _c_options(self.options, check_every, lbfgs=self.hessian_mode == "lbfgs")
+        status = np.zeros(B, dtype=np.int32)
+        iters = np.zeros(B, dtype=np.int32)
+        cs = start._as_c(B) if start is not None else None
+        ce = end._as_c(B)
+        capi.check(n._lib.dto_solve_batch_warm(n._h, C.byref(co), C.byref(b), C.byref(cs) if cs is not None else None, C.byref(ce),
+                                               status.ctypes.data_as(capi.c_int32_p), iters.ctypes.data_as(capi.c_int32_p)))
+        return status, iters
+
+    def shift_point(self, point, knots: int = 1, B=None, stream=0):
+        """dto_point_shift: move a Point `knots` knots forward in place (receding-horizon warm start), the rule of shift_batch on
+        the caller's arrays -- the stage rows an embedded problem carries as dynamics rows are marked so that their multipliers
+        stay with their knots."""
+        n = self._solve_nlp
+        if self._stage_rows is not None and len(self._stage_rows):
+            keep = np.zeros(max(1, n.num_constraint), dtype=np.int32)
+            keep[self._stage_rows] = 1
+            capi.check(n._lib.dto_solver_shift_keep_rows(n._h, keep.ctypes.data_as(capi.c_int32_p), n.num_constraint))
+        B = point.batch() if B is None else B
+        cp = point._as_c(B)
+        capi.check(n._lib.dto_point_shift(n._h, B, C.byref(cp), int(knots), stream or None))
 
     def begin_batch(self, x0_ptr, B, ldx, stream=0, params_ptr=0, ldp=0):
         if self.solve_unsupported:

@@ -448,8 +448,9 @@ int dto_kkt_lbfgs_border_rows(dto_problem* p, int64_t m, const double* s, int64_
  * 17..63-state models through their 64-state embedding; stepwise, warm-started and shifted solves through the entry points below); a
  * GeneralConstraint whose rows couple several knots is solved through a border (general rows and the rows of stage Constraints
  * equalities or inequalities c <= 0, variables free, fixed or bounded on either side -- the problem's shared bounds, by a
- * primal-dual barrier whose bound multipliers are not returned; shared parameters or dto_batch.params, ldp < num_parameters being
- * DTO_ERR_INVALID before anything is written; no warm start; a limited-memory mode on the tile path only, last item below), the
+ * primal-dual barrier; shared parameters or dto_batch.params, ldp < num_parameters being
+ * DTO_ERR_INVALID before anything is written; warm starts, and the bound multipliers, slacks and barrier parameters as outputs,
+ * through dto_solve_batch_warm below; a limited-memory mode on the tile path only, last item below), the
  * filter line-search loop around it
  * driven from the host (dto_kkt_step_batch on such a problem stays the plain Newton step of the bordered system: no barrier
  * terms of the bounds or of inequality rows in it).  All barrier kinds of an instance -- bounds, slacks of inequality general
@@ -463,14 +464,14 @@ int dto_kkt_lbfgs_border_rows(dto_problem* p, int64_t m, const double* s, int64_
  *   panel substitution for all n_g rows and one bordered solve per step (dto_kkt_border_factor / dto_kkt_border_solve inside); at
  *   most 16 general rows (more: DTO_ERR_UNSUPPORTED), no stage rows.  dto_solve_batch, dto_solve and dto_kkt_step_batch take such a
  *   problem; dto_solver_begin / begin_warm / iterate / run / shift and dto_solver_set_bounds return DTO_ERR_UNSUPPORTED for it
- *   (cold starts only, the problem's shared bounds).  dto_solver_hessian_mode reports DTO_HESSIAN_EXACT (with
+ *   (the problem's shared bounds; warm starts and shifts: dto_solve_batch_warm / dto_point_shift).  dto_solver_hessian_mode reports DTO_HESSIAN_EXACT (with
  *   DTO_HESSIAN_EXACT asked for, or more than four general rows), kkt_refinement is ignored;
  * - tile path with dto_options.hessian_approximation = DTO_HESSIAN_LBFGS and at most four general rows (none included): the same
  *   host-driven loop, its step a first-order factorisation with the compact L-BFGS matrix (history 6) as a border of 12 rows; the
  *   general rows share that panel (12 + n_g <= 16: dto_kkt_lbfgs_border_rows), their multipliers enter the secant pairs.  The
  *   history lives on the device, 12 x num_variables doubles per instance (the size is reported if the allocation fails).  The
- *   problem's shared bounds, inequality general rows, shared or per-instance parameters, filter line search (no penalty phase), cold
- *   starts only.  dto_solver_hessian_mode reports DTO_HESSIAN_LBFGS after such a solve. */
+ *   problem's shared bounds, inequality general rows, shared or per-instance parameters, filter line search (no penalty phase); warm
+ *   starts with or without the history through dto_solve_batch_warm.  dto_solver_hessian_mode reports DTO_HESSIAN_LBFGS after such a solve. */
 int dto_solve_batch(dto_problem* p, const dto_options* opt, const dto_batch* b, double* x_out, int64_t ldxo,
                     double* mu_out, int64_t ldmuo, int32_t* status, int32_t* iterations);
 
@@ -519,6 +520,73 @@ int dto_solver_set_bounds(dto_problem* p, int64_t B, const double* lower, int64_
  * Solver sets them from its embedding before every shift).  keep = NULL clears the marks.  The lane-per-instance path keeps its
  * stage rows by itself and ignores the marks. */
 int dto_solver_shift_keep_rows(dto_problem* p, const int32_t* keep, int64_t n);
+
+/* ---- warm-started solves of the bordered path from a point the CALLER owns -----------------------------------------------
+ * A primal-dual point of B instances.  DEVICE arrays of the caller's, instance-major, each with its own leading dimension:
+ *   x       [B][ldx   >= num_variables]
+ *   mu      [B][ldmu  >= num_constraint]  constraint multipliers in the solver's row order (what dto_solve_batch writes to mu_out)
+ *   zl, zu  [B][ldzl / ldzu >= num_variables]  bound multipliers; 0 where a side is infinite or the variable is fixed.  Both NULL
+ *           or both set
+ *   slack   [B][ldslack >= num_constraint]  slacks of the inequality rows (c + s = 0), stage and general; entries of equality rows
+ *           are not read and are written as 0.  May be NULL
+ *   barrier [B]  the barrier parameter of each instance.  May be NULL
+ *   qn_s, qn_y  [B * 6][ldqs / ldqy >= num_variables]  the secant pairs of the limited-memory mode, pair j of instance b in row 6 b + j,
+ *           oldest first (the layout dto_kkt_lbfgs_border takes, m = 6); qn_npairs (int32) and qn_sigma: HOST [B], like status and
+ *           iterations.  All four NULL or all four set. */
+typedef struct dto_point {
+  double* x;
+  int64_t ldx;
+  double* mu;
+  int64_t ldmu;
+  double* zl;
+  int64_t ldzl;
+  double* zu;
+  int64_t ldzu;
+  double* slack;
+  int64_t ldslack;
+  double* barrier;
+  double* qn_s;
+  int64_t ldqs;
+  double* qn_y;
+  int64_t ldqy;
+  int32_t* qn_npairs;
+  double* qn_sigma;
+} dto_point;
+/* dto_solve_batch for the problems its host-driven bordered loop solves -- GeneralConstraint rows that stay on the border (lane
+ * path and tile path), and a tile-path problem with dto_options.hessian_approximation = DTO_HESSIAN_LBFGS and at most four general
+ * rows -- started from `start` and returning the whole point in `end`.  Nothing of the solve stays in the handle: the caller keeps
+ * the point between calls, may shift it (dto_point_shift) and may rotate several batches over one handle.  Any other problem:
+ * DTO_ERR_UNSUPPORTED (the ordinary lane and tile loops have dto_solver_begin_warm); the refusals of dto_solve_batch otherwise.
+ * b: B, params / ldp, stream as for dto_solve_batch; b->x is the guess of a cold start and is not read with start != NULL.
+ * end: x is required, every other array is written where it is set (mu, zl / zu, slack, barrier, the history; without a barrier
+ *   zl = zu = 0, barrier = 0; without the limited-memory mode the history comes back empty: npairs 0, sigma 1).  start and end
+ *   may be the same point.
+ * start == NULL: the cold start of dto_solve_batch, the same launches and the same bits in end->x / end->mu.
+ * start != NULL: x is required (mu == NULL: zero multipliers); the rules of dto_solver_begin_warm --
+ *   - a variable with lo == hi goes to its value; every other one is pushed inside its bounds by bound_push / bound_frac as at a
+ *     cold start;
+ *   - entries of zl / zu that are > 0 are kept; the others, and all of them with zl == NULL, become barrier / gap;
+ *   - the barrier parameter of instance i is start->barrier[i] where that is > 0, else dto_options.mu_init; it is ignored when the
+ *     problem has no finite bound and no inequality row;
+ *   - mu of the equality rows is taken as given; an inequality row keeps (slack, mu) when both are > 0, otherwise
+ *     s = max(-c(x), bound_push max(1, |c(x)|)) and mu = barrier / s;
+ *   - the filter, the inertia-ladder memory, the iteration count and the status of every instance start afresh;
+ *   - the history is used when given (rows of pairs beyond qn_npairs[i] are ignored; the skip and pending counters restart),
+ *     else it starts empty;
+ *   - the loop itself is dto_solve_batch's: it tests convergence before its first step, so a converged point handed back returns
+ *     as it is with 0 iterations.
+ * DTO_ERR_INVALID before anything is written: B < 1, a NULL end or end->x (or start->x), a leading dimension below its row length,
+ * only one of zl / zu, a partial history, qn_npairs outside 0..6 or a qn_sigma that is not positive and finite. */
+int dto_solve_batch_warm(dto_problem* p, const dto_options* opt, const dto_batch* b, const dto_point* start, dto_point* end,
+                         int32_t* status, int32_t* iterations);
+/* dto_solver_shift on a caller's point: block t of x, zl and zu (n_x + n_u variables a knot) and of the dynamics rows of mu (n_x a
+ * knot) takes block min(t + knots, T - 2); the final state is held, the last action repeats.  Multipliers and slacks of stage rows,
+ * rows marked by dto_solver_shift_keep_rows, the general rows behind them and `barrier` stay; each of the 12 history vectors of an
+ * instance shifts like x.  Arrays that are NULL are skipped (x is required).  Any problem with the same state / action dimensions
+ * at every knot, GeneralConstraint rows included; knots >= T - 1: DTO_ERR_INVALID, varying dimensions: DTO_ERR_UNSUPPORTED, the
+ * argument checks of dto_solve_batch_warm.  Out of place through one scratch buffer that is released before the call returns (it
+ * waits for `stream`); nothing is kept in the handle. */
+int dto_point_shift(dto_problem* p, int64_t B, dto_point* pt, int knots, void* stream);
 /* Move the instances that are still running to the leading tiles of the batch so that the following iterations only cover
  * tiles with work (a batch otherwise pays for every tile until its last lane has terminated); results keep coming back in
  * the caller's instance order.  dto_solver_run / dto_solve_batch do this by themselves; a caller that drives

@@ -457,3 +457,67 @@ function resolve_warm!(ev::GPUEvaluator, B::Int, parameters::Matrix{Float64}; op
     dto_device_free(dx); dto_device_free(dpar)
     return X, status, iters
 end
+
+struct DtoPoint                     # include/dto.h: dto_point (DEVICE arrays of the caller's; qn_npairs / qn_sigma: HOST)
+    x::Ptr{Float64}
+    ldx::Int64
+    mu::Ptr{Float64}
+    ldmu::Int64
+    zl::Ptr{Float64}
+    ldzl::Int64
+    zu::Ptr{Float64}
+    ldzu::Int64
+    slack::Ptr{Float64}
+    ldslack::Int64
+    barrier::Ptr{Float64}
+    qn_s::Ptr{Float64}
+    ldqs::Int64
+    qn_y::Ptr{Float64}
+    ldqy::Int64
+    qn_npairs::Ptr{Int32}
+    qn_sigma::Ptr{Float64}
+end
+
+"""
+    solve_point!(ev, B, parameters, start, finish; options = Options())
+
+`dto_solve_batch_warm`: solve the B instances of a problem of the host-driven bordered loop (coupling `GeneralConstraint` rows, or
+a 17..64-state model in the limited-memory mode) from the primal-dual point `start` (a `DtoPoint` of the caller's device arrays;
+`nothing`: cold start from `guess`, num_variables x B) and write the point the solve ends at to `finish`, which may be the same
+point.  Nothing stays in the handle.  Returns (status, iterations).
+"""
+function solve_point!(ev::GPUEvaluator, B::Int, parameters::Matrix{Float64}, start::Union{DtoPoint,Nothing}, finish::DtoPoint;
+                      options = Options(), guess::Union{Matrix{Float64},Nothing} = nothing)
+    opt = DtoOptions(options; limited_memory = !ev.hessian_lagrangian)
+    nz = ev.num_variables
+    dpar = dto_device_array(parameters)
+    dx = guess === nothing ? Ptr{Float64}(C_NULL) : dto_device_array(guess)
+    batch = DtoBatch(B, dx, nz, dpar, size(parameters, 1), C_NULL)
+    status = zeros(Int32, B)
+    iters = zeros(Int32, B)
+    rc = if start === nothing
+        ccall((:dto_solve_batch_warm, libdto), Cint,
+              (Ptr{Cvoid}, Ref{DtoOptions}, Ref{DtoBatch}, Ptr{DtoPoint}, Ref{DtoPoint}, Ptr{Int32}, Ptr{Int32}),
+              ev.handle, opt, batch, C_NULL, finish, status, iters)
+    else
+        ccall((:dto_solve_batch_warm, libdto), Cint,
+              (Ptr{Cvoid}, Ref{DtoOptions}, Ref{DtoBatch}, Ref{DtoPoint}, Ref{DtoPoint}, Ptr{Int32}, Ptr{Int32}),
+              ev.handle, opt, batch, start, finish, status, iters)
+    end
+    dto_device_free(dpar)
+    guess === nothing || dto_device_free(dx)
+    dto_check(rc)
+    return status, iters
+end
+
+"""
+    shift_point!(ev, B, point, knots)
+
+`dto_point_shift`: move the caller's point `knots` knots forward in place (x, bound multipliers, dynamics multipliers and the
+limited-memory history; stage-row and general-row entries and the barrier parameters stay).
+"""
+function shift_point!(ev::GPUEvaluator, B::Int, point::DtoPoint, knots::Int)
+    dto_check(ccall((:dto_point_shift, libdto), Cint, (Ptr{Cvoid}, Int64, Ref{DtoPoint}, Cint, Ptr{Cvoid}),
+                    ev.handle, B, point, knots, C_NULL))
+    return nothing
+end
